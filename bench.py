@@ -12,6 +12,12 @@ RDS chain -> resamplers -> audio filters -> float stereo audio + RDS groups.  In
 on the device and are resident in HBM before the timed region.  With N > 1 every rank owns its
 own channels (no exchange during compute) and float audio and RDS groups of every step are gathered
 over RCCL -- step i to rank i % N (--gather-root 0: to rank 0, every step).  Prints ONE JSON line on rank 0.
+
+A plain run sets up, warms up, times the K steps and prints the line: `value` (MS/s), `ms_per_step` and the FIR
+roofline inside the timed pipeline.  --full adds what takes work of its own after the timed region: the CPU
+baseline, the pinned host-to-device rate (`pcie_inclusive`) and four serialised steps with per-stage events
+(`stage_ms`, `roofline.alone`).  --dump-outputs DIR writes what the last timed step computed (audio of a fixed
+sample of channels, the RDS groups it completed) as .npy files; the inputs depend on the arguments alone.
 """
 import argparse
 import json
@@ -34,6 +40,7 @@ FS = 2.4e6
 D = 11
 N = 65536
 HBM_PEAK_GBS = 8000.0  # MI355X_MICROARCH.md: HBM3E 8.0 TB/s spec
+DUMP_BYTES = 56 << 20  # --dump-outputs: audio rows up to this size (the RDS groups come on top, < 1 MB)
 
 
 def _cpu_topology():
@@ -367,6 +374,15 @@ def main():
     ap.add_argument("--channels", type=int, default=8192, help="channels per GPU")
     ap.add_argument("--ring", type=int, default=10, help="distinct input blocks resident in HBM")
     ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed region also measure the CPU baseline (unless --no-cpu-baseline), the pinned "
+                         "host-to-device rate and, with overlapped calls, four serialised steps with per-stage events "
+                         "(stage_ms, roofline.alone); a plain run does none of these")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write what the last timed step computed to DIR/<name>.npy (float32 audio of a fixed, seeded "
+                         "sample of channels, at most %d MB; float64 RDS groups and channel indices).  The stations "
+                         "of the workload complete their RDS groups on the same calls, so a step may complete none"
+                         % (DUMP_BYTES >> 20))
     ap.add_argument("--lib", default=None,
                     help="development aid: another build of libfmd_hip.so (A/B of compile-time constants)")
     ap.add_argument("--captures", type=int, default=1,
@@ -660,12 +676,13 @@ def main():
     # outputs of step i are consumed after step i+LAG is submitted: the host blocks on nothing younger
     # (3 and 4 measure the same, 244 GS/s on one box: the period is set by the device's work)
     LAG = args.lag
-    state = {"submitted": -1, "finalized": -1}
+    state = {"submitted": -1, "finalized": -1, "groups": None}
 
     def pull_groups(lag):
         nonlocal total_groups
         got = batch.collect_rds_array(cap=4 * RCAP, stream=stream, lag=lag)
         total_groups += int(got.size)
+        state["groups"] = got  # the last pull of drain() (lag 0) holds the last call's groups
 
     def finalize(i, lag):
         """Outputs of step i (call index i+1), complete on the torch stream: with N > 1 its audio and
@@ -893,6 +910,26 @@ def main():
         sys.stderr.write("STEPTIMES wall %.3f ms; call completion (ms since t0): %s\n  intervals: %s\n" % (
             dt * 1e3, " ".join("%.2f" % t for t in ts),
             " ".join("%.2f" % (b - a) for a, b in zip([0.0] + ts[:-1], ts))))
+    if args.dump_outputs and rank == 0:
+        # what a caller of the timed path receives from its last step, before any further step reuses the buffers:
+        # the audio rows of a fixed, seeded sample of channels (all of them when they fit) and the RDS groups that
+        # step completed, as (channel, call_index, b0, b1, b2, b3) rows in channel order
+        last = base + W + K - 1
+        a_last, r_last = out_bufs(last)
+        rows = np.arange(C)
+        if C * nf * 4 > DUMP_BYTES:
+            rows = np.sort(np.random.default_rng(0).choice(C, DUMP_BYTES // (nf * 4), replace=False))
+        d_audio = a_last[torch.from_numpy(rows).to(dev), :nf].cpu().numpy()
+        if use_export:
+            recs = dg.unpack_rds_records(r_last.cpu().numpy())
+            d_groups = np.array([(ch, ci) + bl for ch, ci, bl in recs], dtype=np.float64).reshape(-1, 6)
+        else:
+            g = state["groups"] if state["groups"] is not None else np.zeros(0, dtype=pkg.RDS_GROUP_DTYPE)
+            d_groups = np.column_stack([g["channel"], g["call_index"], g["blocks"]]).astype(np.float64).reshape(-1, 6)
+        d_groups = d_groups[np.lexsort(d_groups.T[::-1])]
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        for name, arr in (("audio", d_audio), ("audio_channels", rows.astype(np.float64)), ("rds_groups", d_groups)):
+            np.save(os.path.join(args.dump_outputs, name + ".npy"), arr)
     if use_export:
         total_groups = int(group_acc.item())  # the root: groups that arrived from every rank
         if rotate:  # every rank was the root of every world-th step
@@ -979,7 +1016,7 @@ def main():
     # events between them -- every kernel alone on the chip (the FIR's figure alone goes beside the
     # in-pipeline one in `roofline`)
     stage_all = None
-    if args.stage_profile or args.concurrency == 2:
+    if args.stage_profile or (args.full and args.concurrency == 2):
         drain()
         if args.concurrency != 0:
             batch.set_concurrency(0)
@@ -993,7 +1030,7 @@ def main():
     # What the host-buffer boundary (fmd_batch_process_host: ProcessStream's own arguments are host
     # pointers) could sustain at best: every IQ byte crosses PCIe once.  Measured here, never `value`.
     pcie = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         hb = torch.empty(256 << 20, dtype=torch.uint8).pin_memory()
         db = torch.empty(256 << 20, dtype=torch.uint8, device=dev)
         db.copy_(hb, non_blocking=True)
@@ -1148,7 +1185,7 @@ def main():
                                               "per tap and output; measured 17.8 (profiles/r3_lone_wave_issue_costs.txt, "
                                               "r3_long_filter_layouts.txt); 78.6 TF = 256 CUs x 4 SIMDs x 32 flop/clk "
                                               "x 2.4 GHz needs two waves per SIMD, which the window does not leave room for")
-        if not args.no_cpu_baseline and world == 1:  # reported at N = 1 only
+        if args.full and not args.no_cpu_baseline and world == 1:  # reported at N = 1 only
             out["cpu_baseline"] = cpu_baseline(if_filter_order=order)
         # RCCL writes its version banner through C stdio, which is block-buffered on a pipe and would
         # otherwise come out at exit, behind the JSON line: flush it first so that the line is the last one

@@ -8,6 +8,7 @@ import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 from __graft_entry__ import ROOT
@@ -117,6 +118,37 @@ def test_single_gpu_invocation_is_unchanged():
     assert out.returncode == 0, out.stderr[-3000:]
     d = json.loads(out.stdout.strip().splitlines()[-1])
     assert d["n_gpus"] == 1 and d["config"]["gather"] == "none (1 GPU)" and "per_rank" not in d
+
+
+def test_plain_run_full_run_and_dumped_outputs(tmp_path):
+    """A plain run measures only its headline (no CPU baseline, no host-to-device rate, no serialised stage steps);
+    --full adds them; --dump-outputs writes the last timed step's outputs, the same bits for the same arguments."""
+    env = {k: v for k, v in os.environ.items()
+           if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
+    base = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--channels", "256", "--steps", "12",
+            "--warmup", "2", "--ring", "4", "--watchdog", "240"]
+
+    def run(*extra):
+        out = subprocess.run(base + list(extra), env=env, cwd=ROOT, capture_output=True, text=True, timeout=280)
+        assert out.returncode == 0, out.stderr[-3000:]
+        return json.loads(out.stdout.strip().splitlines()[-1])
+
+    dumps = [tmp_path / "a", tmp_path / "b"]
+    plain = [run("--dump-outputs", str(p)) for p in dumps]
+    for d in plain:
+        assert d["steps"] == 12 and d["ms_per_step"] > 0 and d["value"] > 0 and d["roofline"]["avg_ms"] > 0
+        assert not {"cpu_baseline", "pcie_inclusive", "stage_ms"} & set(d) and "alone" not in d["roofline"]
+    nf = plain[0]["config"]["audio_floats_per_channel_step"]
+    arrs = [{f: np.load(p / (f + ".npy")) for f in ("audio", "audio_channels", "rds_groups")} for p in dumps]
+    assert arrs[0]["audio"].shape == (256, nf) and arrs[0]["audio"].dtype == np.float32
+    assert np.isfinite(arrs[0]["audio"]).all() and np.abs(arrs[0]["audio"]).max() > 0
+    assert np.array_equal(arrs[0]["audio_channels"], np.arange(256))
+    assert arrs[0]["rds_groups"].ndim == 2 and arrs[0]["rds_groups"].shape[1] == 6
+    assert all(a.dtype in (np.float32, np.float64) for a in arrs[0].values())
+    for f in arrs[0]:
+        assert np.array_equal(arrs[0][f], arrs[1][f]), f
+    full = run("--full", "--no-cpu-baseline")
+    assert "stage_ms" in full and "alone" in full["roofline"] and "cpu_baseline" not in full
 
 
 @pytest.mark.parametrize("workload,steps", [("config5", 8), ("config3", 12)])
