@@ -230,6 +230,37 @@ int fmd_batch_export_rds_device(fmd_batch* b, int32_t* d_records, unsigned cap, 
  * == 0 still means a single capture for the whole batch.  Not while calls are in flight (the device is drained). */
 int fmd_batch_set_channels_per_capture(fmd_batch* b, unsigned channels_per_capture);
 
+/* Moving single channels of a running batch to another station (the reference's host deletes its cFmDecoder
+ * and creates a new one: RadioReceiver.cpp:296-300, 370-374).  All channels of a batch share one clock (tuner
+ * index, decimator and resampler phases, ring positions, RDS oscillator), so a channel cannot become a fresh
+ * decoder in the middle of a batch; the exact equivalent it becomes is this one:
+ *
+ * fmd_batch_retune_channels(b, channels, shifts, n): from the next call on, channel channels[i] decodes exactly
+ * like a decoder that was created with tuning shift shifts[i] (the cFineTuner shift of fmd_batch_create's
+ * tuning_shifts, taken mod table_size like there) when the batch was created, received zero IQ (float zeros) in
+ * every call before this one, and every whole-batch fmd_batch_reset the batch received: audio, getters, RDS
+ * groups and the UECP group decoder's frames and name, bit for bit.  Retuning a channel to its own shift
+ * restarts it on the same station.
+ *  - An edit takes effect at the boundary in front of the next call submitted, whatever the entry point (host,
+ *    device, float or byte input, shared captures).  Several edits before one call apply in the order they were
+ *    made.  Calls already submitted -- also calls in flight under concurrency mode 2 -- are not affected: their
+ *    audio, groups and status records are those of the old tuning.
+ *  - Nothing is synchronised: the call applies the edits on the device, behind the calls before it (a call
+ *    with edits waits for its predecessors to complete instead of overlapping them).
+ *  - Groups of calls before the edit go through the channel's old group decoder state, also when they are
+ *    collected later; the group decoder is reset between the last call before the edit and the first behind
+ *    it.  fmd_batch_get_status's tuning_offset is that of the call the snapshot is of.
+ *  - FMD_ERR_ARG: a null batch or list, a channel out of range or listed twice, a failed batch (fmd_last_error
+ *    says which).  FMD_ERR_STATE: retuning was not enabled.  Same threading rule as the process calls; the
+ *    getters stay safe from any thread.
+ *
+ * fmd_batch_enable_retune(b): the opt-in, only before the first call (FMD_ERR_STATE after it).  It gives the
+ * batch a silent twin -- one channel of the same geometry, fed zeros of every call's size on the batch's
+ * streams -- whose state a retuned channel takes over.  A batch that never calls it runs
+ * exactly as before. */
+int fmd_batch_enable_retune(fmd_batch* b);
+int fmd_batch_retune_channels(fmd_batch* b, const unsigned* channels, const int* shifts, unsigned n);
+
 /* Internal execution.  A call is four independent kernel chains (FIR -> serial demodulator ->
  * {RDS branch, audio branch}); mode selects where they run:
  *   0  all on the caller's stream, in order
@@ -355,6 +386,11 @@ int fmd_batch_debug_set(fmd_batch* b, const char* key, int value);
  * kernels, [2] waiting for them + copy of the audio back, [3] collection of the RDS groups + UECP group
  * decoder callbacks.  Returns the number of calls averaged. */
 int fmd_batch_debug_host_ms(fmd_batch* b, float out[4]);
+/* Test aid (the mutation test of the restart, tests/test_gpu_retune.py): the restarts of the calls that follow
+ * leave out one region of the carried state -- region = its index in kRestartRegions of csrc/fmd_batch.hip (0
+ * state, 1 if_hist, 2 br, 3 mix, 4 halfband, 5 rds_lpf, 6 rds_mf, 7 audio_lpf) -- and a retuned channel is no
+ * longer exact.  -1 (the default) leaves nothing out; other values: FMD_ERR_ARG. */
+int fmd_batch_debug_restart_skip(fmd_batch* b, int region);
 
 const char* fmd_last_error(void);
 const char* fmd_version(void);

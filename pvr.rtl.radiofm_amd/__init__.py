@@ -115,6 +115,7 @@ EXPORTS = [
     "fmd_batch_debug_set_spin_limit", "fmd_batch_debug_timeline", "fmd_batch_debug_set",
     "fmd_batch_debug_stream_conflicts",
     "fmd_batch_debug_host_ms", "fmd_decoder_batch",
+    "fmd_batch_enable_retune", "fmd_batch_retune_channels", "fmd_batch_debug_restart_skip",
 ]
 
 
@@ -149,6 +150,9 @@ def lib():
                                        C.POINTER(vp)]
         L.fmd_batch_destroy.argtypes = [vp]
         L.fmd_batch_reset.argtypes = [vp]
+        L.fmd_batch_enable_retune.argtypes = [vp]
+        L.fmd_batch_retune_channels.argtypes = [vp, vp, vp, u]
+        L.fmd_batch_debug_restart_skip.argtypes = [vp, i]
         L.fmd_batch_channels.restype = u
         L.fmd_batch_channels.argtypes = [vp]
         L.fmd_batch_min_samples.restype = u
@@ -283,6 +287,22 @@ class Batch:
 
     def reset(self):
         _check(lib().fmd_batch_reset(self._h))
+
+    def enable_retune(self):
+        """Opt in to retune() (fmd_batch_enable_retune): only before the first call."""
+        _check(lib().fmd_batch_enable_retune(self._h))
+
+    def retune(self, channels, shifts):
+        """Move channels to new tuner shifts from the next call on (fmd_batch_retune_channels): each then decodes
+        like a decoder created with that shift that received zeros until now."""
+        ch = np.ascontiguousarray(channels, dtype=np.uint32).reshape(-1)
+        sh = np.ascontiguousarray(shifts, dtype=np.int32).reshape(-1)
+        assert ch.size == sh.size
+        _check(lib().fmd_batch_retune_channels(self._h, ch.ctypes.data, sh.ctypes.data, ch.size))
+
+    def debug_restart_skip(self, region):
+        """Test aid: leave one carried region out of the restarts (fmd_batch_debug_restart_skip); -1 = none."""
+        _check(lib().fmd_batch_debug_restart_skip(self._h, region))
 
     def min_samples(self):
         """Smallest call size this batch's geometry accepts (fmd_batch_min_samples)."""

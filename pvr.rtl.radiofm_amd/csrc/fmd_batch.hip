@@ -17,6 +17,7 @@
 #include <cstring>
 #include <deque>
 #include <functional>
+#include <map>
 #include <memory>
 #include <mutex>
 #include <string>
@@ -287,11 +288,56 @@ struct fmd_batch
   DevBuf<unsigned> d_status; // the same record in device memory: what the kernels write (k_status_publish copies)
   unsigned host_seq = 0; // tags of snapshot updates made by the host (create, reset)
 
+  /* Retuning single channels (fmd_batch_enable_retune / fmd_batch_retune_channels).
+   * The caller-facing batch (plain or shell) owns the silent twin -- a one-channel batch of the same geometry on
+   * the same streams, fed zeros of every call's size and reset with the batch -- and the per-channel log of
+   * shift changes (status getters, group decoders).  A batch with buffers of its own (plain or sub-batch) holds
+   * the edits its next call applies and what k_channel_restart needs to apply them. */
+  fmd_params cparams{};                // the create arguments (the twin is made from them)
+  std::unique_ptr<fmd_batch> twin;
+  DevBuf<float2> twin_iq;              // FMD_MAX_BLOCK zeros
+  DevBuf<float> twin_audio;
+  std::mutex log_mu;                   // shift_log: the getters read it from any thread
+  std::vector<std::vector<std::pair<uint32_t, int>>> shift_log; // per channel: (first call, shift), call order
+  std::vector<uint32_t> gdec_epoch;    // per channel: the edit whose reset the group decoder has seen
+  struct Edit
+  {
+    unsigned ch;
+    int shift;
+  };
+  std::vector<Edit> edits;             // pending, in the order they were made (local channel numbers)
+  fmd::RestartTable restart_tab{};
+  int restart_group[fmd::kRestartMaxRegions] = {}; // region of restart_regions each table entry belongs to
+  int restart_skip = -1;               // fmd_batch_debug_set "restart_skip" (mutation test): a region left out
+  unsigned restart_rows_cap = 0;       // distinct tuner rows one restart can carry
+  int2* h_edits = nullptr;             // [NSLOT][C] page-locked staging of the edit list
+  float2* h_rows = nullptr;            // [NSLOT][restart_rows_cap * table_size] ... and of the new tuner rows
+  DevBuf<int2> d_edits;
+  DevBuf<float2> d_rows;
+  hipEvent_t edit_ev[NSLOT] = {};      // behind the copy out of a staging slot
+  bool edit_ev_used[NSLOT] = {};
+  hipEvent_t edit_done = nullptr;      // behind the restart (the twin's next call waits where streams differ)
+  unsigned restart_seq = 0;
+
   ~fmd_batch()
   {
     (void)hipSetDevice(device);
     (void)hipDeviceSynchronize();
     subs.clear(); // (sub-batches first: the streams they run on are this object's)
+    twin.reset();
+    twin_iq.release();
+    twin_audio.release();
+    d_edits.release();
+    d_rows.release();
+    if (h_edits)
+      (void)hipHostFree(h_edits);
+    if (h_rows)
+      (void)hipHostFree(h_rows);
+    for (auto e : edit_ev)
+      if (e)
+        (void)hipEventDestroy(e);
+    if (edit_done)
+      (void)hipEventDestroy(edit_done);
     lut.release();
     hist[0].release();
     hist[1].release();
@@ -555,6 +601,8 @@ int launch_if_stage(fmd_batch* b, const void* d_iq, size_t iq_channel_stride, un
 
 int do_reset(fmd_batch* b)
 {
+  if (b->twin && do_reset(b->twin.get())) // the silent twin receives every whole-batch reset too
+    return -1;
   if (!b->subs.empty())
   {
     for (auto& sb : b->subs)
@@ -800,6 +848,7 @@ int create_one(const fmd_params* params, unsigned n_channels, const int* tuning_
 {
   std::unique_ptr<fmd_batch> b(new fmd_batch);
   b->device = device;
+  b->cparams = *params;
   b->params.sample_rate_if = params->sample_rate_if;
   b->params.tuning_offset = params->tuning_offset;
   b->params.sample_rate_pcm = params->sample_rate_pcm;
@@ -1160,6 +1209,7 @@ int fmd_batch_create(const fmd_params* params, unsigned n_channels, const int* t
     b->sub_ch0.push_back(ch0);
   }
   b->sub_ch0.push_back(n_channels);
+  b->cparams = *params;
   const fmd_batch* s0 = b->subs[0].get();
   b->params = s0->params;
   b->des = s0->des;
@@ -1233,14 +1283,245 @@ unsigned fmd_batch_max_audio_floats(const fmd_batch* b, unsigned samples)
 #include "fmd_batch_if.inc.hpp"      // launch_if_stage: the IF stage's kernel forms
 #include "fmd_batch_process.inc.hpp" // process_device_impl: one call on the batch's streams
 
+namespace
+{
+
+/* The carried regions of a channel: everything a call leaves behind for the next one, per channel.  A retuned
+ * channel takes all of them from the silent twin (k_channel_restart); fmd_batch_debug_set "restart_skip" = index
+ * leaves one out.  Both parities of a double-buffered region are copied: a restart runs when every earlier call
+ * of the batch and of the twin is complete, so neither copy is being read.  What is NOT here is rewritten by
+ * every call before it is read (demod, rlpf, rmf, alp, the half-band chain's tails, the status record) or is
+ * batch-wide (positions, ring phases, the RDS oscillator sequence: the twin has the same ones). */
+const char* const kRestartRegions[] = {
+    "state",     // fstate, istate, r_data: every recurrence, meter and the RDS block assembly
+    "if_hist",   // the IF FIR's delay line (tuned input samples), both hist_sel copies
+    "br",        // the resampler's history rows of the baseband, both parities
+    "mix",       // the first half-band stage's delay line (mixed rows), both parities
+    "halfband",  // the delay lines of the later half-band / CIC stages
+    "rds_lpf",   // the RDS low-pass ring (history rows of rdsraw), both parities
+    "rds_mf",    // the matched filter ring (history rows of rpll)
+    "audio_lpf", // the audio low-pass ring (history rows of rs), both parities
+};
+constexpr int kRestartRegionCount = int(sizeof(kRestartRegions) / sizeof(kRestartRegions[0]));
+
+/* restart_tab of a batch with buffers of its own, copying from the twin `tw` (one channel) */
+int build_restart_table(fmd_batch* x, const fmd_batch* tw)
+{
+  const fmd::Design& d = x->des;
+  fmd::RestartTable& t = x->restart_tab;
+  t.n = 0;
+  auto add = [&](int group, void* dst, const void* src, unsigned rows, unsigned esz, size_t dst_row, size_t dst_ch,
+                 size_t src_row) {
+    if (t.n >= fmd::kRestartMaxRegions)
+      return -1;
+    if (rows == 0)
+      return 0;
+    x->restart_group[t.n] = group;
+    t.r[t.n++] = fmd::RestartRegion{dst, src, rows, esz, dst_row, dst_ch, src_row};
+    return 0;
+  };
+  auto rows2 = [&](int group, const DevBuf<float2>* mine, const DevBuf<float2>* its, unsigned rows) {
+    int bad = 0;
+    for (int q = 0; q < 2; q++)
+      bad |= add(group, mine[q].p, its[q].p, rows, 8, x->CP, 1, tw->CP);
+    return bad;
+  };
+  int bad = 0;
+  bad |= add(0, x->fstate.p, tw->fstate.p, fmd::F_SLOTS, 4, x->CP, 1, tw->CP);
+  bad |= add(0, x->istate.p, tw->istate.p, fmd::I_SLOTS, 4, x->CP, 1, tw->CP);
+  bad |= add(0, x->r_data.p, tw->r_data.p, 4, 2, x->CP, 1, tw->CP);
+  for (int q = 0; q < 2; q++) // channel-major: element j of channel c at c * if_order + j
+    bad |= add(1, x->hist[q].p, tw->hist[q].p, d.if_order, 8, 1, d.if_order, 1);
+  for (int q = 0; q < 2; q++)
+    bad |= add(2, x->brp(q), tw->brp(q), d.rs_order, 8, x->CP, 1, tw->CP);
+  bad |= rows2(3, x->mix, tw->mix, unsigned(d.hb[0].len - 1));
+  for (size_t s = 1; s < d.hb.size(); s++)
+    bad |= add(4, x->hbbuf[s - 1].p, tw->hbbuf[s - 1].p, unsigned(d.hb[s].len - 1), 8, x->CP, 1, tw->CP);
+  bad |= rows2(5, x->rdsraw, tw->rdsraw, unsigned(d.rds_lpf_taps.size() - 1));
+  bad |= add(6, x->rpll.p, tw->rpll.p, unsigned(d.rds_mf_taps.size() - 1), 4, x->CP, 1, tw->CP);
+  bad |= rows2(7, x->rs, tw->rs, unsigned(d.lpf_taps.size() - 1));
+  if (bad)
+    return fail(FMD_ERR_ARG, "fmd_batch_enable_retune: this geometry has more carried regions than the restart takes");
+  // staging of the edit lists: a slot per call index mod NSLOT; at most one tuner row per distinct shift
+  const unsigned T = d.table_size;
+  x->restart_rows_cap = std::min(2 * T - 1, x->C);
+  const size_t rows_per_slot = size_t(x->restart_rows_cap) * T;
+  if (x->d_edits.alloc(size_t(fmd_batch::NSLOT) * x->C) || x->d_rows.alloc(fmd_batch::NSLOT * rows_per_slot))
+    return fail(FMD_ERR_DEVICE, "fmd_batch_enable_retune: device allocation failed");
+  HIPCHK(hipHostMalloc(reinterpret_cast<void**>(&x->h_edits), size_t(fmd_batch::NSLOT) * x->C * sizeof(int2),
+                       hipHostMallocDefault));
+  HIPCHK(hipHostMalloc(reinterpret_cast<void**>(&x->h_rows), fmd_batch::NSLOT * rows_per_slot * sizeof(float2),
+                       hipHostMallocDefault));
+  for (auto& e : x->edit_ev)
+    HIPCHK(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+  HIPCHK(hipEventCreateWithFlags(&x->edit_done, hipEventDisableTiming));
+  return FMD_OK;
+}
+
+/* `s` waits (on the device) for every call of x submitted so far; events already complete are left out */
+hipError_t order_after_calls(fmd_batch* x, hipStream_t s)
+{
+  for (int q = 0; q < fmd_batch::NSLOT; q++)
+  {
+    if (x->slot_call[q] == 0)
+      continue;
+    for (int e : {fmd_batch::EV_INDONE, fmd_batch::EV_HEAVY, fmd_batch::EV_ROLL, fmd_batch::EV_RDS, fmd_batch::EV_AUD})
+    {
+      if (hipEventQuery(x->cev[q][e]) == hipSuccess)
+        continue;
+      (void)hipGetLastError(); // (hipErrorNotReady is an answer)
+      if (hipError_t r = hipStreamWaitEvent(s, x->cev[q][e], 0))
+        return r;
+    }
+  }
+  return hipSuccess;
+}
+
+/* The pending edits of a batch with buffers of its own (plain or sub-batch), submitted in front of its next call:
+ * on the stream its IF FIR will take, behind every earlier call of the batch and of the twin -- so no call in
+ * flight sees a changed byte, and every kernel of the next call (they all run behind its IF FIR) sees the new
+ * state.  The twin's next call goes behind the restart too (it reads the twin as the previous call left it). */
+int submit_restart(fmd_batch* x, fmd_batch* tw, hipStream_t stream)
+{
+  if (x->edits.empty())
+    return FMD_OK;
+  const bool serial_mode = x->concurrency == 0 || x->profiling >= 2;
+  const hipStream_t sF = serial_mode ? stream : x->s_fir;
+  const unsigned T = x->des.table_size;
+  // several edits of one channel before a call apply in order: the last shift is the one that counts.  A table row
+  // depends on the shift's remainder as C++ takes it (sign included: make_tuner_lut reduces shift * i so, and the
+  // angles of s and s - T are different floats), so there are at most 2 T - 1 distinct rows
+  std::map<unsigned, int> last;
+  for (const auto& e : x->edits)
+    last[e.ch] = int((long long)(e.shift) % (long long)T);
+  x->edits.clear();
+  const int slot = int(x->restart_seq++ % fmd_batch::NSLOT);
+  if (x->edit_ev_used[slot]) // the copy of NSLOT restarts ago (long done unless the caller never waits)
+    HIPCHK(hipEventSynchronize(x->edit_ev[slot]));
+  int2* he = x->h_edits + size_t(slot) * x->C;
+  float2* hr = x->h_rows + size_t(slot) * x->restart_rows_cap * T;
+  std::map<int, int> row_of; // shift % T -> row of the staging table
+  unsigned n = 0;
+  for (const auto& [ch, s] : last) // channel order: the kernel's writes of one row go to neighbouring channels
+  {
+    auto it = row_of.find(s);
+    if (it == row_of.end())
+    {
+      const int r = int(row_of.size());
+      it = row_of.emplace(s, r).first;
+      const auto lut = fmd::make_tuner_lut(T, s);
+      std::memcpy(hr + size_t(r) * T, lut.data(), size_t(T) * sizeof(float2));
+    }
+    he[n++] = make_int2(int(ch), it->second);
+  }
+  int2* de = x->d_edits.p + size_t(slot) * x->C;
+  float2* dr = x->d_rows.p + size_t(slot) * x->restart_rows_cap * T;
+  HIPCHK(order_after_calls(x, sF));
+  HIPCHK(order_after_calls(tw, sF));
+  HIPCHK(hipMemcpyAsync(de, he, n * sizeof(int2), hipMemcpyHostToDevice, sF));
+  HIPCHK(hipMemcpyAsync(dr, hr, row_of.size() * T * sizeof(float2), hipMemcpyHostToDevice, sF));
+  HIPCHK(hipEventRecord(x->edit_ev[slot], sF));
+  x->edit_ev_used[slot] = true;
+  fmd::RestartTable tab{};
+  for (int i = 0; i < x->restart_tab.n; i++)
+    if (x->restart_group[i] != x->restart_skip)
+      tab.r[tab.n++] = x->restart_tab.r[i];
+  // a few edits: one workgroup per region; all channels: ~8 rows of every region per workgroup and pass
+  const unsigned blocks = std::min(64u, (n * 8u + 255u) / 256u);
+  hipLaunchKernelGGL(fmd::k_channel_restart, dim3(blocks, tab.n + 1), dim3(256), 0, sF, tab, (const int2*)de, n,
+                     (const float2*)dr, (float2*)x->lut.p, T);
+  HIPCHK(hipGetLastError());
+  if (sF != tw->s_fir)
+  {
+    HIPCHK(hipEventRecord(x->edit_done, sF));
+    HIPCHK(hipStreamWaitEvent(tw->s_fir, x->edit_done, 0));
+  }
+  return FMD_OK;
+}
+
+/* the shift channel c of the caller-facing batch b decodes with in call `ci` */
+int shift_at(fmd_batch* b, unsigned c, uint32_t ci)
+{
+  std::lock_guard<std::mutex> lk(b->log_mu);
+  int s = b->shifts[c];
+  if (c < b->shift_log.size())
+    for (const auto& [k, v] : b->shift_log[c])
+      if (k <= ci)
+        s = v;
+  return s;
+}
+
+/* The group decoder of channel c before a group of call ci: reset once at the first group of a call at or behind
+ * a retune of the channel (groups of earlier calls, collected late, still go through the old state). */
+void gdec_follow_edits(fmd_batch* b, unsigned c, uint32_t ci)
+{
+  uint32_t k_last = 0;
+  {
+    std::lock_guard<std::mutex> lk(b->log_mu);
+    for (const auto& [k, v] : b->shift_log[c])
+      if (k <= ci)
+        k_last = k;
+  }
+  if (k_last > b->gdec_epoch[c])
+  {
+    if (b->gdec[c])
+      b->gdec[c]->reset();
+    b->gdec_epoch[c] = k_last;
+  }
+}
+
+} // namespace
+
 extern "C" {
 
 static int wait_impl(fmd_batch* b, int lag, void* stream_, bool take_lost);
 
 /* One call of any batch: a plain one directly; a shell's as one call of every sub-batch, in channel order, on the
  * same streams (fmd_batch::subs). */
+static int process_shell(fmd_batch* b, const void* d_iq, IqFormat fmt, size_t iq_channel_stride, unsigned samples,
+                         float* d_audio, size_t audio_channel_stride, unsigned* out_floats, void* stream);
+
+/* A batch with retuning enabled: the pending restarts in front of the call, the silent twin's call (zeros of the
+ * same size, on the same streams) behind it.  Without fmd_batch_enable_retune only the plain path runs. */
 static int process_any(fmd_batch* b, const void* d_iq, IqFormat fmt, size_t iq_channel_stride, unsigned samples,
                        float* d_audio, size_t audio_channel_stride, unsigned* out_floats, void* stream)
+{
+  if (!b || !b->twin)
+    return process_shell(b, d_iq, fmt, iq_channel_stride, samples, d_audio, audio_channel_stride, out_floats, stream);
+  if (!d_iq || !d_audio)
+    return fail(FMD_ERR_ARG, "fmd_batch_process_device: null argument");
+  if (samples > FMD_MAX_BLOCK || samples < b->min_samples)
+    return fail(FMD_ERR_SIZE, "samples must be within [fmd_batch_min_samples(), the largest block] = [" +
+                                  std::to_string(b->min_samples) + ", 65536]");
+  if (int rc = check_device_errors(b))
+    return rc;
+  HIPCHK(hipSetDevice(b->device));
+  fmd_batch* tw = b->twin.get();
+  for (fmd_batch* x : is_shell(b) ? [&] {
+         std::vector<fmd_batch*> v;
+         for (auto& sb : b->subs)
+           v.push_back(sb.get());
+         return v;
+       }()
+                                  : std::vector<fmd_batch*>{b})
+    if (int rc = submit_restart(x, tw, static_cast<hipStream_t>(stream)))
+    {
+      mark_failed(b, "a channel restart could not be submitted");
+      return rc;
+    }
+  const int rc =
+      process_shell(b, d_iq, fmt, iq_channel_stride, samples, d_audio, audio_channel_stride, out_floats, stream);
+  if (rc != FMD_OK)
+    return rc;
+  const int trc = process_device_impl(tw, b->twin_iq.p, IQ_F32, 0, samples, b->twin_audio.p,
+                                      b->twin_audio.n, nullptr, stream);
+  if (trc != FMD_OK)
+    mark_failed(b, "the silent twin refused a call the batch took");
+  return trc;
+}
+
+static int process_shell(fmd_batch* b, const void* d_iq, IqFormat fmt, size_t iq_channel_stride, unsigned samples,
+                         float* d_audio, size_t audio_channel_stride, unsigned* out_floats, void* stream)
 {
   if (!b || b->subs.empty())
     return process_device_impl(b, d_iq, fmt, iq_channel_stride, samples, d_audio, audio_channel_stride, out_floats,
@@ -1372,6 +1653,23 @@ int fmd_batch_debug_set_spin_limit(fmd_batch* b, unsigned limit)
   return FMD_OK;
 }
 
+int fmd_batch_debug_restart_skip(fmd_batch* b, int region)
+{
+  if (!b)
+    return fail(FMD_ERR_ARG, "null batch");
+  if (region < -1 || region >= kRestartRegionCount)
+  {
+    std::string names;
+    for (const char* r : kRestartRegions)
+      names += std::string(names.empty() ? "" : ", ") + r;
+    return fail(FMD_ERR_ARG, "fmd_batch_debug_restart_skip: -1 or the index of a region (" + names + ")");
+  }
+  b->restart_skip = region;
+  for (auto& sb : b->subs)
+    sb->restart_skip = region;
+  return FMD_OK;
+}
+
 int fmd_batch_debug_host_ms(fmd_batch* b, float out[4])
 {
   if (!b || !out)
@@ -1453,6 +1751,72 @@ int fmd_batch_debug_set(fmd_batch* b, const char* key, int value)
   }
   else
     return fail(FMD_ERR_ARG, "fmd_batch_debug_set: unknown key '" + k + "'");
+  return FMD_OK;
+}
+
+int fmd_batch_enable_retune(fmd_batch* b)
+{
+  if (!b)
+    return fail(FMD_ERR_ARG, "fmd_batch_enable_retune: null batch");
+  if (b->twin)
+    return FMD_OK;
+  if (b->call_index != 0)
+    return fail(FMD_ERR_STATE, "fmd_batch_enable_retune: only before the batch's first call");
+  HIPCHK(hipSetDevice(b->device));
+  // the twin: one channel of the same geometry on this batch's streams (a shell's: the ones its sub-batches share)
+  fmd_batch* tw = nullptr;
+  const int zero_shift = 0;
+  if (int rc = create_one(&b->cparams, 1, &zero_shift, b->device, nullptr, nullptr, b, &tw))
+    return rc;
+  std::unique_ptr<fmd_batch> twin(tw);
+  twin->concurrency = 2; // ordered by the restarts that read it, never by the caller's stream
+  if (b->twin_iq.alloc(FMD_MAX_BLOCK) || b->twin_audio.alloc(fmd_batch_max_audio_floats(tw, FMD_MAX_BLOCK)))
+    return fail(FMD_ERR_DEVICE, "fmd_batch_enable_retune: device allocation failed");
+  if (is_shell(b))
+  {
+    for (auto& sb : b->subs)
+      if (int rc = build_restart_table(sb.get(), tw))
+        return rc;
+  }
+  else if (int rc = build_restart_table(b, tw))
+    return rc;
+  HIPCHK(hipDeviceSynchronize());
+  {
+    std::lock_guard<std::mutex> lk(b->log_mu);
+    b->shift_log.assign(b->C, {});
+  }
+  b->gdec_epoch.assign(b->C, 0u);
+  b->twin = std::move(twin);
+  return FMD_OK;
+}
+
+int fmd_batch_retune_channels(fmd_batch* b, const unsigned* channels, const int* shifts, unsigned n)
+{
+  if (!b || !channels || !shifts)
+    return fail(FMD_ERR_ARG, "fmd_batch_retune_channels: null argument");
+  if (b->failed)
+    return fail(FMD_ERR_ARG, "fmd_batch_retune_channels: the batch has failed (fmd_batch_reset clears it)");
+  if (!b->twin)
+    return fail(FMD_ERR_STATE, "fmd_batch_retune_channels: retuning is not enabled (fmd_batch_enable_retune)");
+  std::vector<unsigned> seen(channels, channels + n);
+  std::sort(seen.begin(), seen.end());
+  if (n && seen.back() >= b->C)
+    return fail(FMD_ERR_ARG, "fmd_batch_retune_channels: channel " + std::to_string(seen.back()) + " out of range");
+  if (std::adjacent_find(seen.begin(), seen.end()) != seen.end())
+    return fail(FMD_ERR_ARG, "fmd_batch_retune_channels: a channel is listed twice");
+  const uint32_t k = b->call_index + 1; // the call the edit takes effect at
+  std::lock_guard<std::mutex> lk(b->log_mu);
+  for (unsigned i = 0; i < n; i++)
+  {
+    unsigned lc = 0;
+    fmd_batch* ob = owner_of(b, channels[i], &lc);
+    ob->edits.push_back(fmd_batch::Edit{lc, shifts[i]});
+    auto& log = b->shift_log[channels[i]];
+    if (!log.empty() && log.back().first == k)
+      log.back().second = shifts[i];
+    else
+      log.emplace_back(k, shifts[i]);
+  }
   return FMD_OK;
 }
 
@@ -1617,6 +1981,8 @@ int fmd_batch_collect_rds_lagged(fmd_batch* b, fmd_rds_group* out, unsigned cap,
   {
     if (run_group_decoder && r.channel < b->C)
     {
+      if (b->twin)
+        gdec_follow_edits(b, r.channel, r.call_index);
       auto& g = b->gdec[r.channel];
       if (!g)
         g.reset(new fmd::GroupDecoder(&b->cb, b->user, r.channel));
@@ -1781,7 +2147,12 @@ int fmd_batch_get_status(fmd_batch* b, unsigned channel, fmd_status* stt)
   };
   stt->stereo_detected = int(w[fmd::HS_STEREO]);
   // FmDecode.h:146-150
-  const float tuned = float(-b->shifts[channel]) * b->des.fs_if / float(int(b->des.table_size));
+  // the shift of the call the snapshot is of (a retuned channel: fmd_batch_retune_channels); a snapshot the host
+  // wrote (create, reset) is of the newest call
+  const uint32_t snap = (w[fmd::HS_SEQ_END] & 0x80000000u) ? __atomic_load_n(&b->call_index, __ATOMIC_RELAXED)
+                                                            : w[fmd::HS_SEQ_END];
+  const int shift = b->twin ? shift_at(b, channel, snap) : b->shifts[channel];
+  const float tuned = float(-shift) * b->des.fs_if / float(int(b->des.table_size));
   stt->tuning_offset = tuned + f(fmd::HS_BB_MEAN) * b->des.freq_dev;
   stt->interface_level = f(fmd::HS_IF_LEVEL);
   stt->baseband_level = f(fmd::HS_BB_LEVEL);

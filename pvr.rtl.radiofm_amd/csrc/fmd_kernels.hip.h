@@ -25,3 +25,4 @@
 #include "fmd_k_rds.hip.h"
 #include "fmd_k_resample.hip.h"
 #include "fmd_k_tail.hip.h"
+#include "fmd_k_restart.hip.h"
