@@ -455,6 +455,67 @@ int fmd_receiver_pvr_signal_status(fmd_receiver* r, fmd_pvr_signal_status* out);
 /* the decoder inside (status getters, not to be destroyed) */
 fmd_decoder* fmd_receiver_decoder(fmd_receiver* r);
 
+/* ---- band scan: which stations a batch's captures hold ------------------------------ */
+/* The reference has no channel scan (its PVR client declares SetSupportsChannelScan(false), RadioReceiver.cpp:42;
+ * the tuner dialog steps 100 kHz at a time, ChannelSettings.cpp:96-147).  A scan is an averaged power spectrum of
+ * every capture (Welch: nfft-point segments at a hop of nfft/2, periodic Hann window w[n] = 0.5 - 0.5 cos(2 pi n /
+ * nfft)), read on the raster of the decoder's tuner steps.  fs = sample_rate_if, N = nfft, T = table_size.
+ *  - Spectrum: bin i (0 .. N-1) at (i - N/2) fs / N;  P[i] = (1/K) sum over segments |sum_n w[n] x[n]
+ *    e^{-j 2 pi (i - N/2) n / N}|^2 / (N sum w^2), K = the segments accumulated since the last reset (all calls).
+ *    sum_i P[i] is the mean-square IQ power: a full-scale complex tone is 0 dBFS.  A call uses its S = (samples -
+ *    N) / (N/2) + 1 whole segments; the samples behind the last one are not used and nothing carries over.
+ *  - Slots: shift k in [-floor(T/2), -floor(T/2) + T - 1] (fmd_batch_create's tuning_shifts), centred at f(k) =
+ *    -k fs / T.  Slot power = sum of P[i] over the bins within +-half_width_hz of f(k); eligible when |f(k)| +
+ *    half_width_hz <= fs/2 (no wrap-around).  Floor bin = the floor(q (N-1))-th smallest P[i], q = floor_quantile;
+ *    a slot's floor = floor bin x its bin count; snr_db = 10 log10(slot power / slot floor).
+ *  - Candidate: an eligible slot with snr_db >= threshold_db whose power is >= that of every eligible slot within
+ *    +-min_separation_hz and > that of those among them with a smaller shift.  Listed by increasing frequency.
+ * Determinism: the order of every sum depends on (nfft, samples) alone and the totals (double, on the device) add
+ * up in call order, so a capture gives the same bits whatever its row, the capture count or the stream.
+ * Errors: FMD_ERR_ARG (with a sentence) for null arguments, a bad nfft / quantile / width, a stride shorter than
+ * samples with more than one capture, a misaligned pointer (as fmd_batch_process_device[_u8]); FMD_ERR_SIZE for
+ * samples < nfft; FMD_ERR_STATE for a finish with nothing accumulated.  One thread at a time per scan; the calls of
+ * one scan go on one stream (or streams the caller orders).  A scan owns no stream and touches no fmd_batch. */
+typedef struct fmd_scan_params
+{
+  double sample_rate_if;
+  unsigned table_size;      /* slot raster = the cFineTuner step fs / table_size; 0 = 64 (at most 1024) */
+  unsigned nfft;            /* 256..4096, power of two; 0 = 1024 */
+  double half_width_hz;     /* 0 = 100e3; > 0 */
+  double min_separation_hz; /* 0 = 150e3; >= 0 */
+  float threshold_db;       /* 0 = 10 */
+  float floor_quantile;     /* (0, 1); 0 = 0.2 */
+} fmd_scan_params;
+typedef struct fmd_scan_candidate
+{
+  int32_t shift;   /* tuner shift: fmd_batch_create's tuning_shifts / fmd_batch_retune_channels */
+  float offset_hz; /* f(shift) = -shift fs / T, relative to the capture's centre */
+  float power_db;  /* slot power, dBFS */
+  float snr_db;    /* slot power over the slot floor */
+} fmd_scan_candidate;
+typedef struct fmd_scan fmd_scan;
+
+int fmd_scan_create(const fmd_scan_params* p, unsigned n_captures, int device, fmd_scan** out);
+void fmd_scan_destroy(fmd_scan* s);
+/* zeroes the totals (asynchronously on stream) */
+int fmd_scan_reset(fmd_scan* s, void* stream);
+/* returns T; *first_shift (optional) = -floor(T/2), the shift of slot 0 */
+int fmd_scan_slots(const fmd_scan* s, int32_t* first_shift);
+/* Capture g starts at d_iq + 2*g*iq_capture_stride floats (bytes for _u8); byte IQ is converted like the decoder's
+ * (fmd_process_stream_u8).  Asynchronous on stream. */
+int fmd_scan_accumulate_device(fmd_scan* s, const float* d_iq, size_t iq_capture_stride, unsigned samples,
+                               void* stream);
+int fmd_scan_accumulate_device_u8(fmd_scan* s, const uint8_t* d_iq_u8, size_t iq_capture_stride, unsigned samples,
+                                  void* stream);
+int fmd_scan_accumulate_host(fmd_scan* s, const float* iq, size_t iq_capture_stride, unsigned samples);
+/* Outputs (each optional, NULL = not written): psd [G][N], slot_db [G][T] (-inf for an ineligible slot), floor_db
+ * [G] (the floor bin), cand [G][max_cand], counts [G] (the true candidate count, also when max_cand clips the
+ * list).  Does not reset: accumulation may go on. */
+int fmd_scan_finish_device(fmd_scan* s, float* d_psd, float* d_slot_db, float* d_floor_db, fmd_scan_candidate* d_cand,
+                           unsigned max_cand, uint32_t* d_counts, void* stream);
+int fmd_scan_finish_host(fmd_scan* s, float* psd, float* slot_db, float* floor_db, fmd_scan_candidate* cand,
+                         unsigned max_cand, uint32_t* counts);
+
 /* ---- host-only pieces (no GPU needed) ----------------------------------------------- */
 /* UECP group decoder = cRDSGroupDecoder (RDSGroupDecoder.cpp:166-1001). */
 typedef struct fmd_group_decoder fmd_group_decoder;

@@ -92,6 +92,20 @@ class FmdPvrSignalStatus(C.Structure):
                 ("provider_name", C.c_char * 64), ("signal", C.c_int), ("snr", C.c_int)]
 
 
+class FmdScanParams(C.Structure):
+    _fields_ = [("sample_rate_if", C.c_double), ("table_size", C.c_uint), ("nfft", C.c_uint),
+                ("half_width_hz", C.c_double), ("min_separation_hz", C.c_double), ("threshold_db", C.c_float),
+                ("floor_quantile", C.c_float)]
+
+
+class FmdScanCandidate(C.Structure):
+    _fields_ = [("shift", C.c_int32), ("offset_hz", C.c_float), ("power_db", C.c_float), ("snr_db", C.c_float)]
+
+
+SCAN_CANDIDATE_DTYPE = np.dtype([("shift", "<i4"), ("offset_hz", "<f4"), ("power_db", "<f4"), ("snr_db", "<f4")])
+assert SCAN_CANDIDATE_DTYPE.itemsize == C.sizeof(FmdScanCandidate)
+
+
 STREAM_AUDIO, STREAM_RDS, STREAM_CHANGE, STREAM_TIME_BASE = 1, 2, -11, 1000000
 
 EXPORTS = [
@@ -116,6 +130,8 @@ EXPORTS = [
     "fmd_batch_debug_stream_conflicts",
     "fmd_batch_debug_host_ms", "fmd_decoder_batch",
     "fmd_batch_enable_retune", "fmd_batch_retune_channels", "fmd_batch_debug_restart_skip",
+    "fmd_scan_create", "fmd_scan_destroy", "fmd_scan_reset", "fmd_scan_slots", "fmd_scan_accumulate_device",
+    "fmd_scan_accumulate_device_u8", "fmd_scan_accumulate_host", "fmd_scan_finish_device", "fmd_scan_finish_host",
 ]
 
 
@@ -214,6 +230,16 @@ def lib():
         L.fmd_batch_debug_host_ms.argtypes = [vp, vp]
         L.fmd_decoder_batch.restype = vp
         L.fmd_decoder_batch.argtypes = [vp]
+        L.fmd_scan_create.argtypes = [C.POINTER(FmdScanParams), u, i, C.POINTER(vp)]
+        L.fmd_scan_destroy.argtypes = [vp]
+        L.fmd_scan_destroy.restype = None
+        L.fmd_scan_reset.argtypes = [vp, vp]
+        L.fmd_scan_slots.argtypes = [vp, C.POINTER(C.c_int32)]
+        L.fmd_scan_accumulate_device.argtypes = [vp, vp, C.c_size_t, u, vp]
+        L.fmd_scan_accumulate_device_u8.argtypes = [vp, vp, C.c_size_t, u, vp]
+        L.fmd_scan_accumulate_host.argtypes = [vp, vp, C.c_size_t, u]
+        L.fmd_scan_finish_device.argtypes = [vp, vp, vp, vp, vp, u, vp, vp]
+        L.fmd_scan_finish_host.argtypes = [vp, vp, vp, vp, vp, u, vp]
         _LIB = L
     return _LIB
 
@@ -226,6 +252,9 @@ def _check(rc):
     if rc < 0:
         raise FmdError("fmd error %d: %s" % (rc, lib().fmd_last_error().decode()))
     return rc
+
+
+FMD_ERR_ARG_TEXT = "fmd error -1: %s"  # an argument the Python layer refuses itself, worded like _check's
 
 
 FIR_SEQUENTIAL = 0

@@ -1282,6 +1282,7 @@ unsigned fmd_batch_max_audio_floats(const fmd_batch* b, unsigned samples)
 
 #include "fmd_batch_if.inc.hpp"      // launch_if_stage: the IF stage's kernel forms
 #include "fmd_batch_process.inc.hpp" // process_device_impl: one call on the batch's streams
+#include "fmd_scan.inc.hpp"          // fmd_scan_*: the band scan (its own object, the caller's stream)
 
 namespace
 {

@@ -26,3 +26,4 @@
 #include "fmd_k_resample.hip.h"
 #include "fmd_k_tail.hip.h"
 #include "fmd_k_restart.hip.h"
+#include "fmd_k_scan.hip.h"
