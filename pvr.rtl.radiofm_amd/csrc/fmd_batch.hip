@@ -21,6 +21,7 @@
 #include <memory>
 #include <mutex>
 #include <string>
+#include <utility>
 #include <vector>
 
 #include "fmd_design.hpp"
@@ -64,25 +65,82 @@ const char* kStageNames[ST_COUNT] = {"if_fir",      "demod_serial", "rds_halfban
                                      "rds_lpf",     "rds_serial",   "resample",
                                      "audio_lpf",   "audio_tail",   "history_roll"};
 
-template <typename T>
-struct DevBuf
+/* An owning, move-only buffer of n elements: device memory (DevBuf) or page-locked host memory (HostBuf, with the
+ * hipHostMalloc flags of the allocation).  alloc() frees what the buffer holds, then takes max(count, 1) zero-filled
+ * elements; it sets n only on success and leaves p == nullptr, n == 0 on failure. */
+template <typename T, bool HOST>
+struct Buf
 {
   T* p = nullptr;
   size_t n = 0;
-  int alloc(size_t count)
+  Buf() = default;
+  Buf(Buf&& o) noexcept : p(std::exchange(o.p, nullptr)), n(std::exchange(o.n, 0)) {}
+  ~Buf() { release(); }
+  int alloc(size_t count, unsigned host_flags = hipHostMallocDefault)
   {
-    n = count;
-    if (hipMalloc(reinterpret_cast<void**>(&p), std::max<size_t>(count, 1) * sizeof(T)) != hipSuccess)
+    release();
+    const size_t bytes = std::max<size_t>(count, 1) * sizeof(T);
+    void* v = nullptr;
+    if ((HOST ? hipHostMalloc(&v, bytes, host_flags) : hipMalloc(&v, bytes)) != hipSuccess)
       return -1;
-    return hipMemset(p, 0, std::max<size_t>(count, 1) * sizeof(T)) == hipSuccess ? 0 : -1;
+    p = static_cast<T*>(v);
+    if (HOST)
+      std::memset(v, 0, bytes);
+    else if (hipMemset(v, 0, bytes) != hipSuccess)
+    {
+      release();
+      return -1;
+    }
+    n = count;
+    return 0;
   }
   void release()
   {
     if (p)
-      (void)hipFree(p);
+      (void)(HOST ? hipHostFree(p) : hipFree(p));
     p = nullptr;
+    n = 0;
   }
 };
+template <typename T>
+using DevBuf = Buf<T, false>;
+template <typename T>
+using HostBuf = Buf<T, true>;
+
+/* An owning, move-only HIP event; converts to hipEvent_t (null until created). */
+struct Event
+{
+  hipEvent_t e = nullptr;
+  Event() = default;
+  Event(Event&& o) noexcept : e(std::exchange(o.e, nullptr)) {}
+  ~Event() { release(); }
+  hipError_t create(unsigned flags = hipEventDisableTiming)
+  {
+    release();
+    return hipEventCreateWithFlags(&e, flags);
+  }
+  void release()
+  {
+    if (e)
+      (void)hipEventDestroy(e);
+    e = nullptr;
+  }
+  operator hipEvent_t() const { return e; }
+};
+
+/* One launch of a kernel the profiler can time: with ev_start, hipExtLaunchKernelGGL records ev_start / ev_stop at
+ * the kernel's own start and stop (a recorded event would also count the dispatch gap behind it); without, a plain
+ * launch.  Every argument is converted to the kernel's parameter type. */
+template <typename... P, typename... A>
+void launch(void (*kern)(P...), dim3 grid, dim3 block, unsigned lds, hipStream_t s, hipEvent_t ev_start,
+            hipEvent_t ev_stop, A... args)
+{
+  static_assert(sizeof...(P) == sizeof...(A), "kernel argument count");
+  if (ev_start)
+    hipExtLaunchKernelGGL(kern, grid, block, lds, s, ev_start, ev_stop, 0u, static_cast<P>(args)...);
+  else
+    hipLaunchKernelGGL(kern, grid, block, lds, s, static_cast<P>(args)...);
+}
 
 } // namespace
 
@@ -157,8 +215,8 @@ struct fmd_batch
    * from creation; "halfband_chain" = 1 before the first call). */
   static constexpr unsigned kOscH = 64;
   DevBuf<float2> osc_tab[4];
-  float2* h_osc = nullptr;       // [NSLOT][kOscH + Mmax + 8], page-locked
-  hipEvent_t osc_ev[8] = {}; // [NSLOT] behind the copy out of a staging slot
+  HostBuf<float2> h_osc;     // [NSLOT][kOscH + Mmax + 8]
+  Event osc_ev[8];           // [NSLOT] behind the copy out of a staging slot
   bool osc_ev_used[8] = {};
   size_t h_osc_stride = 0;
   float osc_re = 1.0f, osc_im = 0.0f; // CRDSDownConvert: m_Osc1 = (1, 0) (DownConvert.cpp:284)
@@ -192,13 +250,12 @@ struct fmd_batch
   uint32_t drained_call[NSLOT] = {};
   // page-locked staging of fmd_batch_collect_rds: the counts and the records arrive by DMA, no
   // staging kernel, two synchronisations per collect
-  unsigned* h_counts = nullptr;
-  fmd::RdsGroupRec* h_recs = nullptr;
-  size_t h_recs_cap = 0;
+  HostBuf<unsigned> h_counts;
+  HostBuf<fmd::RdsGroupRec> h_recs;
   unsigned queue_cap = 0;
   // fmd_batch_export_rds_device drains a queue asynchronously on the caller's stream: the event tells
   // the next call that appends to the same queue (NSLOT calls later) when it is empty
-  hipEvent_t ev_drained[NSLOT] = {};
+  Event ev_drained[NSLOT];
   bool drained_pending[NSLOT] = {};
   // running row count of one export (k_rds_export): a cursor per call out of a ring, so that two exports
   // on different streams never share one
@@ -210,7 +267,6 @@ struct fmd_batch
 
   // host staging for the host-buffer entry point
   DevBuf<float> h_iq, h_audio;
-  size_t h_iq_cap = 0, h_audio_cap = 0;
 
   std::vector<std::unique_ptr<fmd::GroupDecoder>> gdec;
 
@@ -266,17 +322,16 @@ struct fmd_batch
   bool split_post = false;
   bool serial_exclusive = false; // serial stage owns whole CUs (small batches, see the launch)
   enum { EV_IN, EV_FIR, EV_INDONE, EV_SER, EV_AUD, EV_RDS, EV_HEAVY, EV_RDSH, EV_ALP, EV_DEC, EV_ROLL, EV_N };
-  hipEvent_t cev[NSLOT][EV_N] = {};
-  bool cev_ready = false;
+  Event cev[NSLOT][EV_N];
   uint32_t slot_call[NSLOT] = {}; // call index that last used the slot (0 = never)
-  std::vector<hipEvent_t> ev; // [calls][ST_COUNT + 1]
+  std::vector<Event> ev; // [calls][ST_COUNT + 1]
   unsigned prof_calls = 0;
 
   // Device-side error word (fmd::DevErr bits) in host-mapped memory: kernels OR into it, the host
   // reads it without a copy or a synchronisation.  `failed`: a call broke off after its first launch
   // or a kernel reported an error -- the channel state is no longer trustworthy, every later call is
   // refused until fmd_batch_reset / destroy.
-  unsigned* h_err = nullptr; // [0] fatal bits, [1] recoverable ones (groups lost), see fmd::DevErr
+  HostBuf<unsigned> h_err; // [0] fatal bits, [1] recoverable ones (groups lost), see fmd::DevErr
   bool failed = false;
   std::string fail_msg;
   unsigned spin_limit = 1u << 20; // fmd_batch_debug_set_spin_limit
@@ -284,7 +339,7 @@ struct fmd_batch
   // Status snapshot in host-mapped memory, written by the last kernel of every call
   // (fmd::HostStatusWord): what the getters read -- no device call, no batch bookkeeping touched,
   // so they are safe from any thread while another one is inside a process call.
-  unsigned* h_status = nullptr;
+  HostBuf<unsigned> h_status;
   DevBuf<unsigned> d_status; // the same record in device memory: what the kernels write (k_status_publish copies)
   unsigned host_seq = 0; // tags of snapshot updates made by the host (create, reset)
 
@@ -310,115 +365,26 @@ struct fmd_batch
   int restart_group[fmd::kRestartMaxRegions] = {}; // region of restart_regions each table entry belongs to
   int restart_skip = -1;               // fmd_batch_debug_set "restart_skip" (mutation test): a region left out
   unsigned restart_rows_cap = 0;       // distinct tuner rows one restart can carry
-  int2* h_edits = nullptr;             // [NSLOT][C] page-locked staging of the edit list
-  float2* h_rows = nullptr;            // [NSLOT][restart_rows_cap * table_size] ... and of the new tuner rows
+  HostBuf<int2> h_edits;               // [NSLOT][C] page-locked staging of the edit list
+  HostBuf<float2> h_rows;              // [NSLOT][restart_rows_cap * table_size] ... and of the new tuner rows
   DevBuf<int2> d_edits;
   DevBuf<float2> d_rows;
-  hipEvent_t edit_ev[NSLOT] = {};      // behind the copy out of a staging slot
+  Event edit_ev[NSLOT];                // behind the copy out of a staging slot
   bool edit_ev_used[NSLOT] = {};
-  hipEvent_t edit_done = nullptr;      // behind the restart (the twin's next call waits where streams differ)
+  Event edit_done;                     // behind the restart (the twin's next call waits where streams differ)
   unsigned restart_seq = 0;
 
+  // Everything else frees itself; the sub-batches and the twin run on this batch's streams: they go first.
   ~fmd_batch()
   {
     (void)hipSetDevice(device);
     (void)hipDeviceSynchronize();
-    subs.clear(); // (sub-batches first: the streams they run on are this object's)
+    subs.clear();
     twin.reset();
-    twin_iq.release();
-    twin_audio.release();
-    d_edits.release();
-    d_rows.release();
-    if (h_edits)
-      (void)hipHostFree(h_edits);
-    if (h_rows)
-      (void)hipHostFree(h_rows);
-    for (auto e : edit_ev)
-      if (e)
-        (void)hipEventDestroy(e);
-    if (edit_done)
-      (void)hipEventDestroy(edit_done);
-    lut.release();
-    hist[0].release();
-    hist[1].release();
-    demod[0].release();
-    demod[1].release();
-    mix[0].release();
-    mix[1].release();
-    rdsraw[0].release();
-    rdsraw[1].release();
-    rlpf[0].release();
-    rlpf[1].release();
-    rs[0].release();
-    rs[1].release();
-    alp[0].release();
-    alp[1].release();
-    for (auto& b : hbbuf)
-      b.release();
-    if_coeff.release();
-    rs_coeff.release();
-    br[0].release();
-    br[1].release();
-    rds_lpf_taps.release();
-    mf_taps2.release();
-    audio_taps.release();
-    ktab.release();
-    rsr_tab.release();
-    for (auto& pl : hbf_plans)
-    {
-      pl->steps.release();
-      pl->seg_first.release();
-    }
-    hbf_tail1.release();
-    hbf_tail2.release();
-    for (auto& t : osc_tab)
-      t.release();
-    if (h_osc)
-      (void)hipHostFree(h_osc);
-    for (auto e : osc_ev)
-      if (e)
-        (void)hipEventDestroy(e);
-    rsr_head.release();
-    rsr_steps.release();
-    rpll.release();
-    rmf.release();
-    tap_sync.release();
-    sctab.release();
-    sctab256.release();
-    pidx.release();
-    serial_probe.release();
-    fstate.release();
-    istate.release();
-    r_data.release();
-    for (int q = 0; q < NSLOT; q++)
-    {
-      queue[q].release();
-      if (ev_drained[q])
-        (void)hipEventDestroy(ev_drained[q]);
-    }
-    export_cursor.release();
-    queue_counts.release();
-    if (h_counts)
-      (void)hipHostFree(h_counts);
-    if (h_recs)
-      (void)hipHostFree(h_recs);
-    if (cev_ready)
-      for (auto& row : cev)
-        for (auto& e : row)
-          (void)hipEventDestroy(e);
     if (owns_streams)
       for (hipStream_t st : {s_fir, s_ser, s_post, s_rds, s_lpf})
         if (st)
           (void)hipStreamDestroy(st);
-    h_iq.release();
-    h_audio.release();
-    if (h_err)
-      (void)hipHostFree(h_err);
-    if (h_status)
-      (void)hipHostFree(h_status);
-    d_status.release();
-    for (auto& e : ev)
-      (void)hipEventDestroy(e);
   }
 };
 
@@ -463,10 +429,10 @@ void bind_state(fmd_batch* b)
   b->st.r_data = b->r_data.p;
   b->st.CP = b->CP;
   void* derr = nullptr;
-  if (b->h_err && hipHostGetDevicePointer(&derr, b->h_err, 0) == hipSuccess)
+  if (b->h_err.p && hipHostGetDevicePointer(&derr, b->h_err.p, 0) == hipSuccess)
     b->st.err = static_cast<unsigned*>(derr);
   void* dhs = nullptr;
-  if (b->h_status && hipHostGetDevicePointer(&dhs, b->h_status, 0) == hipSuccess)
+  if (b->h_status.p && hipHostGetDevicePointer(&dhs, b->h_status.p, 0) == hipSuccess)
     b->st.hs = static_cast<unsigned*>(dhs);
   b->st.ds = b->d_status.p;
   // bound of the serial stage's LDS hand-off waits (~0.1 s; fmd_batch_debug_set_spin_limit)
@@ -482,7 +448,7 @@ void host_status_update(fmd_batch* b, const std::function<void(unsigned* rec, si
   const unsigned tag = 0x80000000u | ++b->host_seq;
   for (unsigned c = 0; c < b->C; c++)
   {
-    unsigned* h = b->h_status + c;
+    unsigned* h = b->h_status.p + c;
     __atomic_store_n(&h[fmd::HS_SEQ_BEGIN * CP], tag, __ATOMIC_RELEASE);
     __atomic_thread_fence(__ATOMIC_SEQ_CST);
     edit(h, CP);
@@ -495,7 +461,7 @@ void host_status_update(fmd_batch* b, const std::function<void(unsigned* rec, si
 bool host_status_read(const fmd_batch* b, unsigned channel, unsigned out[fmd::HS_WORDS])
 {
   const size_t CP = b->CP;
-  const unsigned* h = b->h_status + channel;
+  const unsigned* h = b->h_status.p + channel;
   for (int tries = 0; tries < 100000; tries++)
   {
     const unsigned e = __atomic_load_n(&h[fmd::HS_SEQ_END * CP], __ATOMIC_ACQUIRE);
@@ -536,7 +502,7 @@ int check_device_errors(fmd_batch* b)
       }
     return b->failed ? fail(FMD_ERR_DEVICE, b->fail_msg) : FMD_OK;
   }
-  const unsigned e = b->h_err ? __atomic_load_n(&b->h_err[0], __ATOMIC_ACQUIRE) : 0u;
+  const unsigned e = b->h_err.p ? __atomic_load_n(&b->h_err.p[0], __ATOMIC_ACQUIRE) : 0u;
   if (e && !b->failed)
   {
     b->failed = true;
@@ -563,7 +529,7 @@ int take_lost_groups(fmd_batch* b)
     return rc;
   }
   // one exchange: a kernel that ORs the flag in between a load and a store would have its loss wiped
-  if (!b->h_err || !__atomic_exchange_n(&b->h_err[1], 0u, __ATOMIC_ACQ_REL))
+  if (!b->h_err.p || !__atomic_exchange_n(&b->h_err.p[1], 0u, __ATOMIC_ACQ_REL))
     return FMD_OK;
   g_err = "RDS groups were lost: a call's group queue or the export buffer was full (drain every call's "
           "groups with fmd_batch_collect_rds / fmd_batch_export_rds_device, with cap >= the groups queued)";
@@ -638,10 +604,10 @@ int do_reset(fmd_batch* b)
   for (auto& g : b->gdec)
     if (g)
       g->reset();
-  if (b->h_err)
+  if (b->h_err.p)
   {
-    __atomic_store_n(&b->h_err[0], 0u, __ATOMIC_RELEASE);
-    __atomic_store_n(&b->h_err[1], 0u, __ATOMIC_RELEASE);
+    __atomic_store_n(&b->h_err.p[0], 0u, __ATOMIC_RELEASE);
+    __atomic_store_n(&b->h_err.p[1], 0u, __ATOMIC_RELEASE);
   }
   b->failed = false;
   b->fail_msg.clear();
@@ -651,7 +617,7 @@ int do_reset(fmd_batch* b)
     for (int w : {fmd::HS_IF_LEVEL, fmd::HS_BB_MEAN, fmd::HS_BB_LEVEL, fmd::HS_STEREO, fmd::HS_R_STATE})
       if (hipMemset(b->d_status.p + size_t(w) * CP, 0, CP * sizeof(unsigned)) != hipSuccess)
         return -1;
-  if (b->h_status)
+  if (b->h_status.p)
     host_status_update(b, [](unsigned* h, size_t CP) {
       for (int w : {fmd::HS_IF_LEVEL, fmd::HS_BB_MEAN, fmd::HS_BB_LEVEL, fmd::HS_STEREO, fmd::HS_R_STATE})
         __atomic_store_n(&h[size_t(w) * CP], 0u, __ATOMIC_RELAXED);
@@ -757,8 +723,6 @@ fmd_batch::HbfPlan* hbf_plan(fmd_batch* b, unsigned n_in, unsigned S)
   if (b->hbf_plans.size() >= 16) // call sizes keep changing: forget the oldest list
   {
     (void)hipDeviceSynchronize();
-    b->hbf_plans.front()->steps.release();
-    b->hbf_plans.front()->seg_first.release();
     b->hbf_plans.erase(b->hbf_plans.begin());
   }
   b->hbf_plans.push_back(std::move(pl));
@@ -987,12 +951,9 @@ int create_one(const fmd_params* params, unsigned n_channels, const int* tuning_
     for (auto& t : b->osc_tab)
       bad |= t.alloc(size_t(fmd_batch::kOscH) + b->Mmax + 8);
     b->h_osc_stride = size_t(fmd_batch::kOscH) + b->Mmax + 8;
-    bad |= hipHostMalloc(reinterpret_cast<void**>(&b->h_osc), fmd_batch::NSLOT * b->h_osc_stride * sizeof(float2),
-                         hipHostMallocDefault) != hipSuccess;
-    if (!bad)
-      std::memset(b->h_osc, 0, fmd_batch::NSLOT * b->h_osc_stride * sizeof(float2));
+    bad |= b->h_osc.alloc(fmd_batch::NSLOT * b->h_osc_stride);
     for (auto& e : b->osc_ev)
-      bad |= hipEventCreateWithFlags(&e, hipEventDisableTiming) != hipSuccess;
+      bad |= e.create() != hipSuccess;
     // the batch-wide oscillator sequence is only read by k_halfband_chain, which exists for two chains
     const int h0 = (d.hb[0].len - 1) / 2, h1 = (d.hb[1].len - 1) / 2, h2 = (d.hb[2].len - 1) / 2;
     const bool chain_kind = h0 == 7 && ((h1 == 11 && h2 == 21) || (h1 == 9 && h2 == 17));
@@ -1063,8 +1024,7 @@ int create_one(const fmd_params* params, unsigned n_channels, const int* tuning_
   for (int q = 0; q < fmd_batch::NSLOT; q++)
     bad |= b->queue[q].alloc(b->queue_cap);
   bad |= b->queue_counts.alloc(fmd_batch::NSLOT);
-  bad |= hipHostMalloc(reinterpret_cast<void**>(&b->h_counts), fmd_batch::NSLOT * sizeof(unsigned),
-                       hipHostMallocDefault) != hipSuccess;
+  bad |= b->h_counts.alloc(fmd_batch::NSLOT);
   bad |= b->export_cursor.alloc(fmd_batch::kExportCursors);
   if (bad)
     return fail(FMD_ERR_DEVICE, std::string("device allocation failed: ") + hipGetErrorString(hipGetLastError()));
@@ -1089,14 +1049,11 @@ int create_one(const fmd_params* params, unsigned n_channels, const int* tuning_
   }
   // coherent (fine-grained) host memory: the kernels' system-scope writes are visible to the host
   // without a synchronisation, whatever HIP_HOST_COHERENT says
-  if (hipHostMalloc(reinterpret_cast<void**>(&b->h_err), 2 * sizeof(unsigned),
-                    hipHostMallocMapped | hipHostMallocCoherent) != hipSuccess)
+  if (b->h_err.alloc(2, hipHostMallocMapped | hipHostMallocCoherent))
     return fail(FMD_ERR_DEVICE, "host-mapped error word allocation failed");
-  b->h_err[0] = b->h_err[1] = 0u;
-  if (hipHostMalloc(reinterpret_cast<void**>(&b->h_status), size_t(fmd::HS_WORDS) * CP * sizeof(unsigned),
-                    hipHostMallocMapped | hipHostMallocCoherent) != hipSuccess)
+  // (zero-filled: a fresh decoder, all meters zero)
+  if (b->h_status.alloc(size_t(fmd::HS_WORDS) * CP, hipHostMallocMapped | hipHostMallocCoherent))
     return fail(FMD_ERR_DEVICE, "host-mapped status snapshot allocation failed");
-  std::fill_n(b->h_status, size_t(fmd::HS_WORDS) * CP, 0u); // a fresh decoder: all meters zero
   if (b->d_status.alloc(size_t(fmd::HS_WORDS) * CP))
     return fail(FMD_ERR_DEVICE, "status record allocation failed");
   bind_state(b.get());
@@ -1133,10 +1090,9 @@ int create_one(const fmd_params* params, unsigned n_channels, const int* tuning_
   b->serial_exclusive = b->CP <= kSubBatchChannels && b->CP >= 1024;
   for (auto& row : b->cev)
     for (auto& e : row)
-      HIPCHK(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+      HIPCHK(e.create());
   for (auto& e : b->ev_drained)
-    HIPCHK(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-  b->cev_ready = true;
+    HIPCHK(e.create());
   HIPCHK(hipDeviceSynchronize());
   { // can the IF stage of this geometry be launched at all (window in LDS)?  Decided here, once: a
     // process call is then never refused half-way for it
@@ -1349,13 +1305,11 @@ int build_restart_table(fmd_batch* x, const fmd_batch* tw)
   const size_t rows_per_slot = size_t(x->restart_rows_cap) * T;
   if (x->d_edits.alloc(size_t(fmd_batch::NSLOT) * x->C) || x->d_rows.alloc(fmd_batch::NSLOT * rows_per_slot))
     return fail(FMD_ERR_DEVICE, "fmd_batch_enable_retune: device allocation failed");
-  HIPCHK(hipHostMalloc(reinterpret_cast<void**>(&x->h_edits), size_t(fmd_batch::NSLOT) * x->C * sizeof(int2),
-                       hipHostMallocDefault));
-  HIPCHK(hipHostMalloc(reinterpret_cast<void**>(&x->h_rows), fmd_batch::NSLOT * rows_per_slot * sizeof(float2),
-                       hipHostMallocDefault));
+  if (x->h_edits.alloc(size_t(fmd_batch::NSLOT) * x->C) || x->h_rows.alloc(fmd_batch::NSLOT * rows_per_slot))
+    return fail(FMD_ERR_DEVICE, "fmd_batch_enable_retune: page-locked staging allocation failed");
   for (auto& e : x->edit_ev)
-    HIPCHK(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-  HIPCHK(hipEventCreateWithFlags(&x->edit_done, hipEventDisableTiming));
+    HIPCHK(e.create());
+  HIPCHK(x->edit_done.create());
   return FMD_OK;
 }
 
@@ -1399,8 +1353,8 @@ int submit_restart(fmd_batch* x, fmd_batch* tw, hipStream_t stream)
   const int slot = int(x->restart_seq++ % fmd_batch::NSLOT);
   if (x->edit_ev_used[slot]) // the copy of NSLOT restarts ago (long done unless the caller never waits)
     HIPCHK(hipEventSynchronize(x->edit_ev[slot]));
-  int2* he = x->h_edits + size_t(slot) * x->C;
-  float2* hr = x->h_rows + size_t(slot) * x->restart_rows_cap * T;
+  int2* he = x->h_edits.p + size_t(slot) * x->C;
+  float2* hr = x->h_rows.p + size_t(slot) * x->restart_rows_cap * T;
   std::map<int, int> row_of; // shift % T -> row of the staging table
   unsigned n = 0;
   for (const auto& [ch, s] : last) // channel order: the kernel's writes of one row go to neighbouring channels
@@ -1738,7 +1692,7 @@ int fmd_batch_debug_set(fmd_batch* b, const char* key, int value)
     b->hbf_mode = value < 0 ? -1 : (value ? 1 : 0);
     // before the first call a small batch can still start the batch-wide oscillator sequence (and with it
     // the form of the serial stage that writes no mixed rows); later its chain reads mixed rows
-    if (value > 0 && b->call_index == 0 && b->h_osc && b->des.hb.size() == 3 &&
+    if (value > 0 && b->call_index == 0 && b->h_osc.p && b->des.hb.size() == 3 &&
         b->des.hb[0].len - 1 <= int(fmd_batch::kOscH))
       b->osc_on = true;
   }
@@ -1885,7 +1839,7 @@ static int drain_counts(QueueDrain& d, int lag, hipStream_t stream)
       d.todo[d.ntodo++] = q;
     }
   if (d.ntodo)
-    HIPCHK(hipMemcpyAsync(b->h_counts, b->queue_counts.p, fmd_batch::NSLOT * sizeof(unsigned), hipMemcpyDeviceToHost,
+    HIPCHK(hipMemcpyAsync(b->h_counts.p, b->queue_counts.p, fmd_batch::NSLOT * sizeof(unsigned), hipMemcpyDeviceToHost,
                           stream));
   return FMD_OK;
 }
@@ -1895,27 +1849,17 @@ static int drain_records(QueueDrain& d, hipStream_t stream)
   fmd_batch* b = d.b;
   for (int i = 0; i < d.ntodo; i++)
   {
-    d.cnt[i] = std::min(b->h_counts[d.todo[i]], b->queue_cap); // overflow: the oldest queue_cap groups are kept
+    d.cnt[i] = std::min(b->h_counts.p[d.todo[i]], b->queue_cap); // overflow: the oldest queue_cap groups are kept
     d.total += d.cnt[i];
   }
-  if (d.total > b->h_recs_cap)
-  {
-    if (b->h_recs)
-      (void)hipHostFree(b->h_recs);
-    b->h_recs = nullptr;
-    b->h_recs_cap = 0;
-    const size_t want = std::max<size_t>(d.total, size_t(2) * b->C + 1024);
-    if (hipHostMalloc(reinterpret_cast<void**>(&b->h_recs), want * sizeof(fmd::RdsGroupRec), hipHostMallocDefault) !=
-        hipSuccess)
-      return fail(FMD_ERR_DEVICE, "fmd_batch_collect_rds: page-locked staging allocation failed");
-    b->h_recs_cap = want;
-  }
+  if (d.total > b->h_recs.n && b->h_recs.alloc(std::max<size_t>(d.total, size_t(2) * b->C + 1024)))
+    return fail(FMD_ERR_DEVICE, "fmd_batch_collect_rds: page-locked staging allocation failed");
   size_t at = 0;
   for (int i = 0; i < d.ntodo; i++)
     if (d.cnt[i])
     {
       const int q = d.todo[i];
-      HIPCHK(hipMemcpyAsync(b->h_recs + at, b->queue[q].p, size_t(d.cnt[i]) * sizeof(fmd::RdsGroupRec),
+      HIPCHK(hipMemcpyAsync(b->h_recs.p + at, b->queue[q].p, size_t(d.cnt[i]) * sizeof(fmd::RdsGroupRec),
                             hipMemcpyDeviceToHost, stream));
       HIPCHK(hipMemsetAsync(b->qcount(q), 0, sizeof(unsigned), stream));
       at += d.cnt[i];
@@ -1963,7 +1907,7 @@ int fmd_batch_collect_rds_lagged(fmd_batch* b, fmd_rds_group* out, unsigned cap,
       for (int i = 0; i < d.ntodo; i++)
         d.b->drained_call[d.todo[i]] = d.b->slot_call[d.todo[i]];
       const size_t at = recs.size();
-      recs.insert(recs.end(), d.b->h_recs, d.b->h_recs + d.total);
+      recs.insert(recs.end(), d.b->h_recs.p, d.b->h_recs.p + d.total);
       for (size_t i = at; i < recs.size(); i++)
         recs[i].channel += d.ch0;
     }
@@ -2064,20 +2008,9 @@ static int process_host_impl(fmd_batch* b, const void* iq, IqFormat fmt, size_t 
   const unsigned streams = iq_channel_stride ? C / b->cpc : 1u; // input rows: one per channel, per capture, or one
   const size_t iq_floats = (dev_row * streams + 3) / 4;
   const size_t a_stride = (size_t(fmd_batch_max_audio_floats(b, samples)) + 3) & ~size_t(3);
-  if (iq_floats > b->h_iq_cap)
-  {
-    b->h_iq.release();
-    if (b->h_iq.alloc(iq_floats))
-      return fail(FMD_ERR_DEVICE, "staging allocation failed");
-    b->h_iq_cap = iq_floats;
-  }
-  if (a_stride * C > b->h_audio_cap)
-  {
-    b->h_audio.release();
-    if (b->h_audio.alloc(a_stride * C))
-      return fail(FMD_ERR_DEVICE, "staging allocation failed");
-    b->h_audio_cap = a_stride * C;
-  }
+  if ((iq_floats > b->h_iq.n && b->h_iq.alloc(iq_floats)) ||
+      (a_stride * C > b->h_audio.n && b->h_audio.alloc(a_stride * C)))
+    return fail(FMD_ERR_DEVICE, "staging allocation failed");
   using clk = std::chrono::steady_clock;
   auto ms_since = [](clk::time_point t) { return std::chrono::duration<double, std::milli>(clk::now() - t).count(); };
   clk::time_point tp = clk::now();
@@ -2376,7 +2309,7 @@ int fmd_batch_get_stage_ms(fmd_batch* b, float* out, unsigned cap)
       for (unsigned c = 0; c < b->prof_calls; c++)
       {
         float ms = 0;
-        hipEvent_t* es = &b->ev[size_t(c) * (ST_COUNT + 1)];
+        const Event* es = &b->ev[size_t(c) * (ST_COUNT + 1)];
         HIPCHK(hipEventElapsedTime(&ms, es[i], es[i + 1]));
         sum += ms;
       }
@@ -2482,12 +2415,6 @@ int fmd_debug_math(int what, unsigned n, const float* a, const float* b, float* 
     bad |= hipMemcpy(out0, d0.p, size_t(n) * 4, hipMemcpyDeviceToHost) != hipSuccess;
     bad |= hipMemcpy(out1, d1.p, size_t(n) * 4, hipMemcpyDeviceToHost) != hipSuccess;
   }
-  da.release();
-  db.release();
-  d0.release();
-  d1.release();
-  tab.release();
-  tab256.release();
   return bad ? fail(FMD_ERR_DEVICE, "fmd_debug_math: device error") : FMD_OK;
 }
 
@@ -2505,7 +2432,7 @@ int fmd_batch_debug_timeline(fmd_batch* b, float* out, unsigned cap_calls)
   hipEvent_t t0 = b->ev[0];
   for (unsigned c = 0; c < n; c++)
   {
-    hipEvent_t* es = &b->ev[size_t(c) * (ST_COUNT + 1)];
+    const Event* es = &b->ev[size_t(c) * (ST_COUNT + 1)];
     for (int i = 0; i < 10; i++)
     {
       float ms = -1.0f;

@@ -14,11 +14,6 @@ using FirFn = void (*)(const typename IN::elem*, size_t, unsigned, const float2*
                        unsigned, unsigned, const float*, unsigned, unsigned, unsigned, unsigned, float2*,
                        unsigned, unsigned, unsigned, unsigned);
 
-template <class IN>
-using FirFn3 = void (*)(const typename IN::elem*, size_t, unsigned, const float2*, float2*, const float2*,
-                        unsigned, unsigned, const float*, unsigned, unsigned, unsigned, unsigned, float2*,
-                        unsigned, unsigned, unsigned, unsigned);
-
 template <class IN, int TILE, int E, bool RB128 = false>
 int launch_if_stage_t(fmd_batch* b, const void* d_iq, size_t iq_channel_stride, unsigned N, unsigned pos,
                       unsigned M, int q, hipStream_t sF, const std::function<void(int)>& mark,
@@ -70,7 +65,7 @@ int launch_if_stage_t(fmd_batch* b, const void* d_iq, size_t iq_channel_stride, 
   const int fir_nt = fma ? 2 : b->dbg_fir_nt ? b->dbg_fir_nt : (b->concurrency == 2 && b->serial_exclusive ? 2 : 1);
   unsigned nblocks = C * ntiles, ntiles_l = ntiles;
   size_t lds_l = lds;
-  FirFn3<IN> kfn3 = nullptr; // k_if_fir_mt3
+  FirFn<IN> kfn3 = nullptr; // k_if_fir_mt3
   if (TILE == 64 && E == 0 && pow2 && rounds == 7 && fir_nt > 1 && !shfl)
   {
     const unsigned nt = fir_nt >= 8 ? 8u : fir_nt >= 4 ? 4u : fir_nt == 3 ? 3u : 2u;
@@ -103,30 +98,10 @@ int launch_if_stage_t(fmd_batch* b, const void* d_iq, size_t iq_channel_stride, 
                               hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
   const typename IN::elem* x = static_cast<const typename IN::elem*>(d_iq);
   mark(0);
-  // profiled calls: the two events take the kernel's own start and stop (hipExtLaunchKernelGGL),
-  // not the stream's state around it (a recorded event also counts the dispatch gap behind it)
-  if (kfn3 && ev_start)
-    hipExtLaunchKernelGGL(kfn3, dim3(nblocks), dim3(TILE), unsigned(lds_l), sF, ev_start, ev_stop, 0u, x,
-                          iq_channel_stride, N, (const float2*)b->hist[b->hist_sel].p,
-                          (float2*)b->hist[b->hist_sel ^ 1].p, (const float2*)b->lut.p, T, b->lut_idx,
-                          (const float*)b->if_coeff.p, d.if_order, D, pos, M, (float2*)b->demod[q].p,
-                          b->Mstride, ntiles_l, (C % 8 == 0) ? 1u : 0u, b->cpc);
-  else if (kfn3)
-    hipLaunchKernelGGL(kfn3, dim3(nblocks), dim3(TILE), lds_l, sF, x, iq_channel_stride, N,
-                       b->hist[b->hist_sel].p, b->hist[b->hist_sel ^ 1].p, b->lut.p, T, b->lut_idx,
-                       b->if_coeff.p, d.if_order, D, pos, M, b->demod[q].p, b->Mstride, ntiles_l,
-                       (C % 8 == 0) ? 1u : 0u, b->cpc);
-  else if (ev_start)
-    hipExtLaunchKernelGGL(kfn, dim3(nblocks), dim3(TILE), unsigned(lds_l), sF, ev_start, ev_stop, 0u, x,
-                          iq_channel_stride, N, (const float2*)b->hist[b->hist_sel].p,
-                          (float2*)b->hist[b->hist_sel ^ 1].p, (const float2*)b->lut.p, T, b->lut_idx,
-                          (const float*)b->if_coeff.p, d.if_order, D, pos, M, (float2*)b->demod[q].p,
-                          b->Mstride, ntiles_l, (C % 8 == 0) ? 1u : 0u, b->cpc);
-  else
-    hipLaunchKernelGGL(kfn, dim3(nblocks), dim3(TILE), lds_l, sF, x, iq_channel_stride, N,
-                       b->hist[b->hist_sel].p, b->hist[b->hist_sel ^ 1].p, b->lut.p, T, b->lut_idx,
-                       b->if_coeff.p, d.if_order, D, pos, M, b->demod[q].p, b->Mstride, ntiles_l,
-                       (C % 8 == 0) ? 1u : 0u, b->cpc);
+  // profiled calls: the two events take the kernel's own start and stop
+  launch(kfn3 ? kfn3 : kfn, dim3(nblocks), dim3(TILE), unsigned(lds_l), sF, ev_start, ev_stop, x, iq_channel_stride,
+         N, b->hist[b->hist_sel].p, b->hist[b->hist_sel ^ 1].p, b->lut.p, T, b->lut_idx, b->if_coeff.p, d.if_order, D,
+         pos, M, b->demod[q].p, b->Mstride, ntiles_l, (C % 8 == 0) ? 1u : 0u, b->cpc);
   mark(1);
   hipLaunchKernelGGL(fmd::k_if_level<IN>, dim3(C), dim3(64), 0, sF, x, iq_channel_stride, N, b->lut.p, T,
                      b->lut_idx, b->st, b->cpc);

@@ -145,13 +145,9 @@ void launch_light_audio(fmd_batch* b, const fmd_batch::LightJob& j, hipStream_t 
                        0, s, b->rs[j.q].p, b->rs[j.q ^ 1].p, T_alp - 1, j.A, CP);
   }
   const fmd::AudioConsts k = audio_consts(d);
-  if (j.tl0) // profiling level 1: the tail's own start and stop
-    hipExtLaunchKernelGGL(fmd::k_audio_tail, dim3(CP / 64), dim3(64, 1), 0u, s, j.tl0, j.tl1, 0u,
-                          (const float2*)b->alp[j.q].p, j.A, C, CP, k, b->st, j.d_audio, j.audio_stride,
-                          unsigned(j.sq), j.call_index);
-  else
-    hipLaunchKernelGGL(fmd::k_audio_tail, dim3(CP / 64), dim3(64, 1), 0, s, b->alp[j.q].p, j.A, C, CP, k, b->st,
-                       j.d_audio, j.audio_stride, unsigned(j.sq), j.call_index);
+  // (profiling level 1: j.tl0 / j.tl1 take the tail's own start and stop)
+  launch(fmd::k_audio_tail, dim3(CP / 64), dim3(64, 1), 0, s, j.tl0, j.tl1, b->alp[j.q].p, j.A, C, CP, k, b->st,
+         j.d_audio, j.audio_stride, unsigned(j.sq), j.call_index);
   // the record's RDS state is the other half's (same stream: stream order)
   if (j.events && j.status_after_rds && hipStreamWaitEvent(s, b->cev[j.es][fmd_batch::EV_RDS], 0) != hipSuccess)
     mark_failed(b, "hipStreamWaitEvent failed in front of the status record of a call");
@@ -268,7 +264,7 @@ int process_device_impl(fmd_batch* b, const void* d_iq, IqFormat fmt, size_t iq_
   const int sq = int(ci & 3u); // this call's copy of the stereo flag (see ISlot)
   // call k-2 used the same buffers; its events say when they are free again
   const bool have_prev2 = ci > 2;
-  hipEvent_t* pe2 = b->cev[(ci + fmd_batch::NSLOT - 2) % fmd_batch::NSLOT];
+  const Event* pe2 = b->cev[(ci + fmd_batch::NSLOT - 2) % fmd_batch::NSLOT];
   const bool serial_mode = b->concurrency == 0 || b->profiling >= 2;
   /* "stage_mask" (fmd_batch_debug_set; results are WRONG with anything but 63): which parts of a call are
    * launched at all -- 1 IF stage, 2 serial stage, 4 half-band chain, 8 resampler, 16 / 32 the light part's RDS /
@@ -281,7 +277,7 @@ int process_device_impl(fmd_batch* b, const void* d_iq, IqFormat fmt, size_t iq_
   hipStream_t sA = sP, sR = (!serial_mode && b->split_post) ? b->s_rds : sP;
   // one-stream form: the light parts of the post chain go to their own stream (see below)
   hipStream_t sL = serial_mode ? stream : b->s_rds;
-  hipEvent_t* ce = b->cev[es];
+  const Event* ce = b->cev[es];
   // the first failing event operation of the call (checked once, behind the launches)
   hipError_t herr = hipSuccess;
   auto note = [&](hipError_t e) {
@@ -297,18 +293,20 @@ int process_device_impl(fmd_batch* b, const void* d_iq, IqFormat fmt, size_t iq_
       note(hipEventRecord(e, s));
   };
 
-  hipEvent_t* evset = nullptr;
+  const Event* evset = nullptr;
   if (b->profiling && b->prof_calls < kMaxProfCalls)
   {
     const size_t need = size_t(b->prof_calls + 1) * (ST_COUNT + 1);
     while (b->ev.size() < need)
     {
-      hipEvent_t e;
-      HIPCHK(hipEventCreate(&e));
-      b->ev.push_back(e);
+      Event e;
+      HIPCHK(e.create(hipEventDefault));
+      b->ev.push_back(std::move(e));
     }
     evset = &b->ev[size_t(b->prof_calls) * (ST_COUNT + 1)]; // prof_calls advances with call_index
   }
+  // level 1, overlapped calls: events i, i + 1 take a kernel's own start and stop (fmd_batch_debug_timeline)
+  auto timed = [&](int i) -> hipEvent_t { return evset && b->profiling == 1 && !serial_mode ? evset[i].e : nullptr; };
   // level 2: events between all stages (serial mode); level 1: only around the FIR kernel, on
   // the stream that kernel is launched on
   auto mark = [&](int i) { // events 0 and 1 are the FIR kernel's own start and stop (launch_if_stage)
@@ -349,8 +347,8 @@ int process_device_impl(fmd_batch* b, const void* d_iq, IqFormat fmt, size_t iq_
     // submitted eight calls without ever waiting
     if (b->osc_ev_used[es])
       note(hipEventSynchronize(b->osc_ev[es]));
-    float2* h = b->h_osc + size_t(es) * b->h_osc_stride;
-    const float2* hp = b->h_osc + size_t((ci + fmd_batch::NSLOT - 1) % fmd_batch::NSLOT) * b->h_osc_stride;
+    float2* h = b->h_osc.p + size_t(es) * b->h_osc_stride;
+    const float2* hp = b->h_osc.p + size_t((ci + fmd_batch::NSLOT - 1) % fmd_batch::NSLOT) * b->h_osc_stride;
     std::memcpy(h, hp + b->lastM, fmd_batch::kOscH * sizeof(float2)); // the previous call's last entries
     const float oc = d.rds_osc_cos, os = d.rds_osc_sin;
     float2* o = h + fmd_batch::kOscH;
@@ -411,9 +409,9 @@ int process_device_impl(fmd_batch* b, const void* d_iq, IqFormat fmt, size_t iq_
     else
       rc = fmt == IQ_U8
                        ? launch_if_stage<fmd::InU8>(b, d_iq, iq_channel_stride, N, pos, M, q, sF, markfn,
-                                                   evset ? evset[0] : nullptr, evset ? evset[1] : nullptr)
+                                                   evset ? evset[0].e : nullptr, evset ? evset[1].e : nullptr)
                        : launch_if_stage<fmd::InF32>(b, d_iq, iq_channel_stride, N, pos, M, q, sF, markfn,
-                                                    evset ? evset[0] : nullptr, evset ? evset[1] : nullptr);
+                                                    evset ? evset[0].e : nullptr, evset ? evset[1].e : nullptr);
     if (rc != FMD_OK) // cannot happen: the geometry was checked when the batch was created
     {
       mark_failed(b, "the IF stage refused a call after events were recorded");
@@ -443,28 +441,14 @@ int process_device_impl(fmd_batch* b, const void* d_iq, IqFormat fmt, size_t iq_
     auto kser2 = nomix ? (serial_claim ? &fmd::k_demod_serial<2, true, false> : &fmd::k_demod_serial<2, false, false>)
                        : (serial_claim ? &fmd::k_demod_serial<2, true, true> : &fmd::k_demod_serial<2, false, true>);
     auto kser1 = nomix ? &fmd::k_demod_serial<1, false, false> : &fmd::k_demod_serial<1, false, true>;
-
-    if (!(stage_mask & 2u))
-      ; // (energy experiment: no serial stage in this call)
-    else if (b->serial_exclusive && !serial_mode && evset && b->profiling == 1)
-      // profiling level 1: the stage's own start and stop too (fmd_batch_debug_timeline)
-      hipExtLaunchKernelGGL(kser2, dim3((groups + 1) / 2), dim3(256), 0u, sS, evset[2],
-                            evset[3], 0u, (const float2*)b->demod[q].p, b->Mstride, M, C, CP, k, b->st,
-                            b->brp(q), Hbb, b->mix[q].p, Hmix,
-                            (const double*)(b->sctab256.p), sct, unsigned(sq),
-                            (long long*)nullptr, osc_re, osc_im);
-    else if (b->serial_exclusive && !serial_mode)
-      hipLaunchKernelGGL(kser2, dim3((groups + 1) / 2), dim3(256), 0, sS,
-                         (const float2*)b->demod[q].p, b->Mstride, M, C, CP, k, b->st, b->brp(q), Hbb, b->mix[q].p,
-                         Hmix, (const double*)b->sctab256.p, sct, unsigned(sq),
-                         b->serial_probe.p ? b->serial_probe.p + size_t(ci % 8) * 3 * (CP / 64) : (long long*)nullptr,
-                         osc_re, osc_im);
-    else
-      hipLaunchKernelGGL(kser1, dim3(groups), dim3(128), 0, sS, (const float2*)b->demod[q].p,
-                         b->Mstride, M, C, CP, k, b->st, b->brp(q), Hbb, b->mix[q].p, Hmix,
-                         (const double*)b->sctab256.p, sct, unsigned(sq),
-                         b->serial_probe.p ? b->serial_probe.p + size_t(ci % 8) * 3 * (CP / 64) : (long long*)nullptr,
-                         osc_re, osc_im);
+    const bool whole_cu = b->serial_exclusive && !serial_mode;
+    const hipEvent_t t0 = whole_cu ? timed(2) : nullptr, t1 = whole_cu ? timed(3) : nullptr;
+    // (the timed launch takes no serial probe)
+    long long* probe = b->serial_probe.p && !t0 ? b->serial_probe.p + size_t(ci % 8) * 3 * (CP / 64) : nullptr;
+    if (stage_mask & 2u) // (else the energy experiment: no serial stage in this call)
+      launch(whole_cu ? kser2 : kser1, dim3(whole_cu ? (groups + 1) / 2 : groups), dim3(whole_cu ? 256 : 128), 0, sS,
+             t0, t1, b->demod[q].p, b->Mstride, M, C, CP, k, b->st, b->brp(q), Hbb, b->mix[q].p, Hmix, b->sctab256.p,
+             sct, unsigned(sq), probe, osc_re, osc_im);
   }
   signal(ce[fmd_batch::EV_SER], sS);
   mark(2);
@@ -574,17 +558,9 @@ int process_device_impl(fmd_batch* b, const void* d_iq, IqFormat fmt, size_t iq_
       const float2* osc = nomix ? (const float2*)(b->osc_tab[osc_slot].p + (fmd_batch::kOscH - L0H)) : nullptr;
       auto kern = hbf_kind == 0 ? (nomix ? &fmd::k_halfband_chain<7, 11, 21, true> : &fmd::k_halfband_chain<7, 11, 21, false>)
                                 : (nomix ? &fmd::k_halfband_chain<7, 9, 17, true> : &fmd::k_halfband_chain<7, 9, 17, false>);
-      if (evset && b->profiling == 1 && !serial_mode) // its own start and stop (fmd_batch_debug_timeline)
-        hipExtLaunchKernelGGL(kern, dim3(groups, pl->S), dim3(64, 4), 0u, sR, evset[6], evset[7], 0u, in0,
-                              (const float2*)b->hbbuf[0].p, (const float2*)b->hbbuf[1].p, b->rdsraw[q].p, T_lpf - 1,
-                              b->hbf_tail1.p, b->hbf_tail2.p, b->hbcoef[0], b->hbcoef[1], b->hbcoef[2],
-                              (const fmd::HbStep*)pl->steps.p, (const int*)pl->seg_first.p, hb_in[0], n0, n1, C, CP,
-                              osc, 0u);
-      else
-        hipLaunchKernelGGL(kern, dim3(groups, pl->S), dim3(64, 4), 0, sR, in0, (const float2*)b->hbbuf[0].p,
-                           (const float2*)b->hbbuf[1].p, b->rdsraw[q].p, T_lpf - 1, b->hbf_tail1.p, b->hbf_tail2.p,
-                           b->hbcoef[0], b->hbcoef[1], b->hbcoef[2], (const fmd::HbStep*)pl->steps.p,
-                           (const int*)pl->seg_first.p, hb_in[0], n0, n1, C, CP, osc, 0u);
+      launch(kern, dim3(groups, pl->S), dim3(64, 4), 0, sR, timed(6), timed(7), in0, b->hbbuf[0].p, b->hbbuf[1].p,
+             b->rdsraw[q].p, T_lpf - 1, b->hbf_tail1.p, b->hbf_tail2.p, b->hbcoef[0], b->hbcoef[1], b->hbcoef[2],
+             pl->steps.p, pl->seg_first.p, hb_in[0], n0, n1, C, CP, osc, 0u);
       if (nomix) // the next call's stage-0 history, should it take a launch per stage (it reads mixed rows)
         mix_tail = [&, L0H]() {
           hipLaunchKernelGGL(fmd::k_mix_tail, rgrid(L0H), rt, 0, sR,
@@ -707,15 +683,9 @@ int process_device_impl(fmd_batch* b, const void* d_iq, IqFormat fmt, size_t iq_
       const unsigned lds = b->rsr_nbr * 4096u;
       rs_plan(sA); // (already done in front of the half-band chain where the two share a stream)
       auto go = [&](auto kern) {
-        if (evset && b->profiling == 1 && !serial_mode)
-          hipExtLaunchKernelGGL(kern, dim3(W), dim3(64, b->rsr_NW + 1), lds, sA, evset[8], evset[9], 0u,
-                                (const float2*)b->brp(q), Hbb, b->rsr_rb, d.rs_order, (const float*)b->rsr_tab.p,
-                                b->rsr_nbm, (const int*)b->rsr_head.p, (const int*)b->rsr_steps.p, rs_steps, per_wg,
-                                b->rsr_nbr, A, b->rs[q].p, T_alp - 1, C, CP, rsr_prio);
-        else
-        hipLaunchKernelGGL(kern, dim3(W), dim3(64, b->rsr_NW + 1), lds, sA, b->brp(q), Hbb, b->rsr_rb,
-                           d.rs_order, b->rsr_tab.p, b->rsr_nbm, b->rsr_head.p, b->rsr_steps.p, rs_steps, per_wg,
-                           b->rsr_nbr, A, b->rs[q].p, T_alp - 1, C, CP, rsr_prio);
+        launch(kern, dim3(W), dim3(64, b->rsr_NW + 1), lds, sA, timed(8), timed(9), b->brp(q), Hbb, b->rsr_rb,
+               d.rs_order, b->rsr_tab.p, b->rsr_nbm, b->rsr_head.p, b->rsr_steps.p, rs_steps, per_wg, b->rsr_nbr, A,
+               b->rs[q].p, T_alp - 1, C, CP, rsr_prio);
       };
       if (b->rsr_R == 4)
         go(&fmd::k_resample_ring<4, 4>);
@@ -828,11 +798,8 @@ int process_device_impl(fmd_batch* b, const void* d_iq, IqFormat fmt, size_t iq_
       audio_lpf_late();
       signal(ce[fmd_batch::EV_ALP], sl);
     }
-    if (evset && b->profiling == 1)
-    {
-      job.tl0 = evset[4];
-      job.tl1 = evset[5];
-    }
+    job.tl0 = timed(4);
+    job.tl1 = timed(5);
     /* The light part goes out at once: its RDS half behind the RDS half of the heavy part (it runs beside the
      * resampler), the audio tail behind the whole heavy part.  (Until round 3 it was kept back until the NEXT
      * call's serial stage had ended, so that it ran beside that call's heavy part and not beside a FIR -- built

@@ -10,25 +10,14 @@ struct fmd_scan
   double fs = 0.0, sum_w2 = 0.0;
   float threshold_db = 0.0f;
   unsigned long long segments = 0; // K: segments accumulated since the last reset (host count, call order)
-  float* d_win = nullptr;
-  float2* d_tw = nullptr;
-  double* d_totals = nullptr;
-  fmd::ScanSlot* d_slots = nullptr;
-  float* d_scratch = nullptr;
-  size_t scratch_floats = 0;
-  void* d_stage = nullptr; // fmd_scan_accumulate_host / fmd_scan_finish_host
-  size_t stage_bytes = 0;
+  DevBuf<float> d_win;
+  DevBuf<float2> d_tw;
+  DevBuf<double> d_totals;
+  DevBuf<fmd::ScanSlot> d_slots;
+  DevBuf<float> d_scratch;
+  DevBuf<char> d_stage; // fmd_scan_accumulate_host / fmd_scan_finish_host
 
-  ~fmd_scan()
-  {
-    (void)hipSetDevice(device);
-    (void)hipFree(d_win);
-    (void)hipFree(d_tw);
-    (void)hipFree(d_totals);
-    (void)hipFree(d_slots);
-    (void)hipFree(d_scratch);
-    (void)hipFree(d_stage);
-  }
+  ~fmd_scan() { (void)hipSetDevice(device); } // (the buffers free themselves behind it)
 };
 
 namespace
@@ -37,36 +26,21 @@ namespace
 /* Few captures: below this count each capture's chunks are spread over workgroups (scratch + k_scan_reduce). */
 constexpr unsigned kScanSplitBelow = 512;
 
-int scan_grow(fmd_scan* s, void** p, size_t* have, size_t bytes, hipStream_t stream)
-{
-  if (bytes <= *have)
-    return FMD_OK;
-  // the old buffer may still be read by work queued on this stream
-  HIPCHK(hipStreamSynchronize(stream));
-  (void)hipFree(*p);
-  *p = nullptr;
-  *have = 0;
-  if (hipMalloc(p, bytes) != hipSuccess)
-    return fail(FMD_ERR_DEVICE, "fmd_scan: device allocation failed");
-  *have = bytes;
-  return FMD_OK;
-}
-
 template <class In, int N>
 void scan_launch(fmd_scan* s, const void* d_iq, size_t stride, unsigned S, unsigned n_chunks, hipStream_t stream)
 {
   const auto* x = static_cast<const typename In::elem*>(d_iq);
-  if (s->d_scratch && s->G < kScanSplitBelow)
+  if (s->d_scratch.p && s->G < kScanSplitBelow)
   {
     hipLaunchKernelGGL((fmd::k_scan_psd<In, N>), dim3(n_chunks, s->G), dim3(fmd::kScanThreads), 0, stream, x,
-                       stride, S, n_chunks, s->d_win, s->d_tw, s->d_totals, s->d_scratch);
+                       stride, S, n_chunks, s->d_win.p, s->d_tw.p, s->d_totals.p, s->d_scratch.p);
     const size_t n = size_t(s->G) * N;
-    hipLaunchKernelGGL(fmd::k_scan_reduce, dim3(unsigned((n + 255) / 256)), dim3(256), 0, stream, s->d_totals,
-                       s->d_scratch, s->G, unsigned(N), n_chunks);
+    hipLaunchKernelGGL(fmd::k_scan_reduce, dim3(unsigned((n + 255) / 256)), dim3(256), 0, stream, s->d_totals.p,
+                       s->d_scratch.p, s->G, unsigned(N), n_chunks);
   }
   else
     hipLaunchKernelGGL((fmd::k_scan_psd<In, N>), dim3(s->G), dim3(fmd::kScanThreads), 0, stream, x, stride, S,
-                       n_chunks, s->d_win, s->d_tw, s->d_totals, static_cast<float*>(nullptr));
+                       n_chunks, s->d_win.p, s->d_tw.p, s->d_totals.p, static_cast<float*>(nullptr));
 }
 
 template <class In>
@@ -97,13 +71,12 @@ int scan_accumulate(fmd_scan* s, const void* d_iq, bool u8, size_t stride, unsig
   HIPCHK(hipSetDevice(s->device));
   const unsigned S = (samples - s->N) / (s->N / 2) + 1;
   const unsigned n_chunks = (S + fmd::kScanChunk - 1) / fmd::kScanChunk;
-  if (s->G < kScanSplitBelow)
+  const size_t scratch = size_t(s->G) * n_chunks * s->N;
+  if (s->G < kScanSplitBelow && scratch > s->d_scratch.n)
   {
-    size_t have = s->scratch_floats * sizeof(float);
-    if (int rc = scan_grow(s, reinterpret_cast<void**>(&s->d_scratch), &have,
-                           size_t(s->G) * n_chunks * s->N * sizeof(float), stream))
-      return rc;
-    s->scratch_floats = have / sizeof(float);
+    HIPCHK(hipStreamSynchronize(stream)); // the old buffer may still be read by work queued on this stream
+    if (s->d_scratch.alloc(scratch))
+      return fail(FMD_ERR_DEVICE, "fmd_scan: device allocation failed");
   }
   if (u8)
     scan_launch_n<fmd::InU8>(s, d_iq, stride, S, n_chunks, stream);
@@ -121,8 +94,8 @@ int scan_finish(fmd_scan* s, float* d_psd, float* d_slot_db, float* d_floor_db, 
     return fail(FMD_ERR_STATE, "fmd_scan_finish: no segment has been accumulated since the last reset");
   HIPCHK(hipSetDevice(s->device));
   fmd::ScanSlotArgs a{};
-  a.totals = s->d_totals;
-  a.slots = s->d_slots;
+  a.totals = s->d_totals.p;
+  a.slots = s->d_slots.p;
   a.denom = double(s->segments) * double(s->N) * s->sum_w2;
   a.N = s->N;
   a.T = s->T;
@@ -230,16 +203,13 @@ int fmd_scan_create(const fmd_scan_params* p, unsigned n_captures, int device, f
   s->sum_w2 = sw2;
   s->threshold_db = thr;
   s->floor_index = unsigned(std::floor(double(qf) * double(N - 1)));
-  if (hipMalloc(&s->d_win, N * sizeof(float)) != hipSuccess ||
-      hipMalloc(&s->d_tw, N * sizeof(float2)) != hipSuccess ||
-      hipMalloc(&s->d_totals, size_t(n_captures) * N * sizeof(double)) != hipSuccess ||
-      hipMalloc(&s->d_slots, std::max(1u, T) * sizeof(fmd::ScanSlot)) != hipSuccess)
+  // (zero-filled: no segment accumulated yet)
+  if (s->d_win.alloc(N) || s->d_tw.alloc(N) || s->d_totals.alloc(size_t(n_captures) * N) || s->d_slots.alloc(T))
     return fail(FMD_ERR_DEVICE, "fmd_scan_create: device allocation failed");
-  HIPCHK(hipMemcpy(s->d_win, win.data(), N * sizeof(float), hipMemcpyHostToDevice));
-  HIPCHK(hipMemcpy(s->d_tw, tw.data(), N * sizeof(float2), hipMemcpyHostToDevice));
+  HIPCHK(hipMemcpy(s->d_win.p, win.data(), N * sizeof(float), hipMemcpyHostToDevice));
+  HIPCHK(hipMemcpy(s->d_tw.p, tw.data(), N * sizeof(float2), hipMemcpyHostToDevice));
   if (T)
-    HIPCHK(hipMemcpy(s->d_slots, slots.data(), T * sizeof(fmd::ScanSlot), hipMemcpyHostToDevice));
-  HIPCHK(hipMemset(s->d_totals, 0, size_t(n_captures) * N * sizeof(double)));
+    HIPCHK(hipMemcpy(s->d_slots.p, slots.data(), T * sizeof(fmd::ScanSlot), hipMemcpyHostToDevice));
   HIPCHK(hipDeviceSynchronize());
   *out = s.release();
   return FMD_OK;
@@ -257,7 +227,7 @@ int fmd_scan_reset(fmd_scan* s, void* stream)
   if (!s)
     return fail(FMD_ERR_ARG, "fmd_scan_reset: null scan");
   HIPCHK(hipSetDevice(s->device));
-  HIPCHK(hipMemsetAsync(s->d_totals, 0, size_t(s->G) * s->N * sizeof(double), static_cast<hipStream_t>(stream)));
+  HIPCHK(hipMemsetAsync(s->d_totals.p, 0, size_t(s->G) * s->N * sizeof(double), static_cast<hipStream_t>(stream)));
   s->segments = 0;
   return FMD_OK;
 }
@@ -296,10 +266,14 @@ int fmd_scan_accumulate_host(fmd_scan* s, const float* iq, size_t iq_capture_str
   HIPCHK(hipSetDevice(s->device));
   const size_t stride = s->G > 1 ? iq_capture_stride : 0;
   const size_t bytes = (size_t(s->G - 1) * stride + samples) * 2 * sizeof(float);
-  if (int rc = scan_grow(s, &s->d_stage, &s->stage_bytes, bytes, nullptr))
-    return rc;
-  HIPCHK(hipMemcpy(s->d_stage, iq, bytes, hipMemcpyHostToDevice));
-  if (int rc = scan_accumulate(s, static_cast<const float*>(s->d_stage), false, stride, samples, nullptr))
+  if (bytes > s->d_stage.n)
+  {
+    HIPCHK(hipStreamSynchronize(nullptr)); // the old buffer may still be read by work queued on this stream
+    if (s->d_stage.alloc(bytes))
+      return fail(FMD_ERR_DEVICE, "fmd_scan: device allocation failed");
+  }
+  HIPCHK(hipMemcpy(s->d_stage.p, iq, bytes, hipMemcpyHostToDevice));
+  if (int rc = scan_accumulate(s, reinterpret_cast<const float*>(s->d_stage.p), false, stride, samples, nullptr))
     return rc;
   HIPCHK(hipStreamSynchronize(nullptr));
   return FMD_OK;
@@ -327,9 +301,13 @@ int fmd_scan_finish_host(fmd_scan* s, float* psd, float* slot_db, float* floor_d
   const size_t o_slot = (n_psd + 15) & ~size_t(15), o_floor = (o_slot + n_slot + 15) & ~size_t(15),
                o_cand = (o_floor + n_floor + 15) & ~size_t(15), o_counts = (o_cand + n_cand + 15) & ~size_t(15),
                total = std::max<size_t>(16, o_counts + n_counts);
-  if (int rc = scan_grow(s, &s->d_stage, &s->stage_bytes, total, nullptr))
-    return rc;
-  char* base = static_cast<char*>(s->d_stage);
+  if (total > s->d_stage.n)
+  {
+    HIPCHK(hipStreamSynchronize(nullptr)); // the old buffer may still be read by work queued on this stream
+    if (s->d_stage.alloc(total))
+      return fail(FMD_ERR_DEVICE, "fmd_scan: device allocation failed");
+  }
+  char* base = s->d_stage.p;
   if (int rc = scan_finish(s, psd ? reinterpret_cast<float*>(base) : nullptr,
                            slot_db ? reinterpret_cast<float*>(base + o_slot) : nullptr,
                            floor_db ? reinterpret_cast<float*>(base + o_floor) : nullptr,
