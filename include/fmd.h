@@ -261,6 +261,31 @@ int fmd_batch_set_channels_per_capture(fmd_batch* b, unsigned channels_per_captu
 int fmd_batch_enable_retune(fmd_batch* b);
 int fmd_batch_retune_channels(fmd_batch* b, const unsigned* channels, const int* shifts, unsigned n);
 
+/* Resetting single channels of a running batch: the batched form of cFmDecoder::Reset (FmDecode.cpp:326-338),
+ * where fmd_batch_reset resets every channel and drains the device.
+ *
+ * fmd_batch_reset_channels(b, channels, n): from the next call on, channel channels[i] decodes bit for bit like
+ * its own decoder that received the same inputs and a cFmDecoder::Reset() between the last call before this one
+ * and the next: audio, getters, RDS groups and the UECP group decoder's frames and name.  Channels not listed stay
+ * bit-identical to the same run without the call.  Works on every batch (no opt-in).
+ *  - An edit takes effect at the boundary in front of the next call submitted, whatever the entry point (host,
+ *    device, float or byte input, shared captures, sub-batches).  Edits before one call -- resets and, with
+ *    retuning enabled, retunes of the same channels -- apply in the order they were made.  Calls already
+ *    submitted -- also calls in flight under concurrency mode 2 -- are not affected.
+ *  - Nothing is synchronised: the next call applies the resets on the device, behind the calls before it (a call
+ *    with edits waits for its predecessors to complete instead of overlapping them).
+ *  - The getters return the newest completed call's record: the first call behind the reset gives the reset
+ *    decoder's values.  The receiver's audio meter (fmd_batch_get_audio_level) is not touched, as with
+ *    fmd_batch_reset.
+ *  - Groups of calls before the reset go through the channel's old group decoder state, also when they are
+ *    collected later; the group decoder is reset between the last call before the reset and the first behind it.
+ *  - FMD_ERR_ARG: a null batch or list (before the HIP runtime is touched), a channel out of range or listed
+ *    twice, a failed batch (fmd_last_error says which).  Same threading rule as the process calls.
+ * The RDS low-pass and matched filter of a reset channel start their rings afresh while the batch's run on; the
+ * channel keeps its own ring origin for them.  A batch that never calls this runs exactly
+ * as before. */
+int fmd_batch_reset_channels(fmd_batch* b, const unsigned* channels, unsigned n);
+
 /* Internal execution.  A call is four independent kernel chains (FIR -> serial demodulator ->
  * {RDS branch, audio branch}); mode selects where they run:
  *   0  all on the caller's stream, in order
@@ -389,8 +414,13 @@ int fmd_batch_debug_host_ms(fmd_batch* b, float out[4]);
 /* Test aid (the mutation test of the restart, tests/test_gpu_retune.py): the restarts of the calls that follow
  * leave out one region of the carried state -- region = its index in kRestartRegions of csrc/fmd_batch.hip (0
  * state, 1 if_hist, 2 br, 3 mix, 4 halfband, 5 rds_lpf, 6 rds_mf, 7 audio_lpf) -- and a retuned channel is no
- * longer exact.  -1 (the default) leaves nothing out; other values: FMD_ERR_ARG. */
+ * longer exact (the rds_lpf / rds_mf regions include the ring origins).  -1 (the default) leaves nothing out; other
+ * values: FMD_ERR_ARG. */
 int fmd_batch_debug_restart_skip(fmd_batch* b, int region);
+/* Test aid (the teeth test of the single-channel reset, tests/test_gpu_reset_channels.py): on != 0 makes the
+ * resets of the calls that follow leave the channels' ring origins at the batch's phase (0), and a reset channel's
+ * RDS low-pass and matched filter are no longer exact.  0 (the default) restores the origins. */
+int fmd_batch_debug_reset_keep_ring_phase(fmd_batch* b, int on);
 
 const char* fmd_last_error(void);
 const char* fmd_version(void);

@@ -130,6 +130,7 @@ EXPORTS = [
     "fmd_batch_debug_stream_conflicts",
     "fmd_batch_debug_host_ms", "fmd_decoder_batch",
     "fmd_batch_enable_retune", "fmd_batch_retune_channels", "fmd_batch_debug_restart_skip",
+    "fmd_batch_reset_channels", "fmd_batch_debug_reset_keep_ring_phase",
     "fmd_scan_create", "fmd_scan_destroy", "fmd_scan_reset", "fmd_scan_slots", "fmd_scan_accumulate_device",
     "fmd_scan_accumulate_device_u8", "fmd_scan_accumulate_host", "fmd_scan_finish_device", "fmd_scan_finish_host",
 ]
@@ -169,6 +170,8 @@ def lib():
         L.fmd_batch_enable_retune.argtypes = [vp]
         L.fmd_batch_retune_channels.argtypes = [vp, vp, vp, u]
         L.fmd_batch_debug_restart_skip.argtypes = [vp, i]
+        L.fmd_batch_reset_channels.argtypes = [vp, vp, u]
+        L.fmd_batch_debug_reset_keep_ring_phase.argtypes = [vp, i]
         L.fmd_batch_channels.restype = u
         L.fmd_batch_channels.argtypes = [vp]
         L.fmd_batch_min_samples.restype = u
@@ -328,6 +331,16 @@ class Batch:
         sh = np.ascontiguousarray(shifts, dtype=np.int32).reshape(-1)
         assert ch.size == sh.size
         _check(lib().fmd_batch_retune_channels(self._h, ch.ctypes.data, sh.ctypes.data, ch.size))
+
+    def reset_channels(self, channels):
+        """Reset single channels from the next call on (fmd_batch_reset_channels): each then decodes like its own
+        decoder after cFmDecoder::Reset() in front of that call; the other channels do not notice."""
+        ch = np.ascontiguousarray(channels, dtype=np.uint32).reshape(-1)
+        _check(lib().fmd_batch_reset_channels(self._h, ch.ctypes.data, ch.size))
+
+    def debug_reset_keep_ring_phase(self, on):
+        """Test aid: resets that follow leave the ring origins at the batch's phase (not exact)."""
+        _check(lib().fmd_batch_debug_reset_keep_ring_phase(self._h, int(on)))
 
     def debug_restart_skip(self, region):
         """Test aid: leave one carried region out of the restarts (fmd_batch_debug_restart_skip); -1 = none."""

@@ -294,6 +294,7 @@ struct fmd_batch
   {
     unsigned R = 0, A = 0, mf_g = 0, alpf_g = 0;
     unsigned rds_lpf_g = 0;            // ring phase of the RDS low-pass at this call
+    const unsigned* org = nullptr;     // ring origins of the RDS low-pass / matched filter, or null (fmd_batch::org)
     int q = 0, es = 0, sq = 0;
     bool events = true;                // false: everything on the caller's stream, no event is recorded or waited for
     bool lpf_here = false;             // the two complex low-pass filters are part of the light part (layout 2)
@@ -353,19 +354,23 @@ struct fmd_batch
   DevBuf<float2> twin_iq;              // FMD_MAX_BLOCK zeros
   DevBuf<float> twin_audio;
   std::mutex log_mu;                   // shift_log: the getters read it from any thread
-  std::vector<std::vector<std::pair<uint32_t, int>>> shift_log; // per channel: (first call, shift), call order
+  // per channel: (first call, shift) of every call with a retune or reset in front of it, call order; empty until
+  // the first edit (enable_retune or reset_channels sizes it)
+  std::vector<std::vector<std::pair<uint32_t, int>>> shift_log;
   std::vector<uint32_t> gdec_epoch;    // per channel: the edit whose reset the group decoder has seen
   struct Edit
   {
     unsigned ch;
     int shift;
+    bool reset; // fmd_batch_reset_channels (shift unused); else a retune to `shift`
   };
   std::vector<Edit> edits;             // pending, in the order they were made (local channel numbers)
+  bool edits_pending = false;          // caller-facing batch: edits wait in `edits` here or in a sub-batch
   fmd::RestartTable restart_tab{};
   int restart_group[fmd::kRestartMaxRegions] = {}; // region of restart_regions each table entry belongs to
   int restart_skip = -1;               // fmd_batch_debug_set "restart_skip" (mutation test): a region left out
   unsigned restart_rows_cap = 0;       // distinct tuner rows one restart can carry
-  HostBuf<int2> h_edits;               // [NSLOT][C] page-locked staging of the edit list
+  HostBuf<int2> h_edits;               // [NSLOT][2 C] page-locked staging of the edit lists (restarts, resets)
   HostBuf<float2> h_rows;              // [NSLOT][restart_rows_cap * table_size] ... and of the new tuner rows
   DevBuf<int2> d_edits;
   DevBuf<float2> d_rows;
@@ -373,6 +378,13 @@ struct fmd_batch
   bool edit_ev_used[NSLOT] = {};
   Event edit_done;                     // behind the restart (the twin's next call waits where streams differ)
   unsigned restart_seq = 0;
+  /* Resetting single channels (fmd_batch_reset_channels): the ring phase of a channel's RDS
+   * low-pass and matched filter is the batch's (rds_lpf_g, mf_g) minus its origin -- org[c] and org[CP + c], the
+   * batch phases when it was last reset, 0 for a channel that never was.  Until a batch's first reset every origin
+   * is 0 and the ring filters run without them (origins_live); fmd_batch_reset returns to that. */
+  DevBuf<unsigned> org;                // [2][CP]
+  bool origins_live = false;
+  int dbg_reset_keep_phase = 0;        // fmd_batch_debug_reset_keep_ring_phase (test aid): origins stay 0
 
   // Everything else frees itself; the sub-batches and the twin run on this batch's streams: they go first.
   ~fmd_batch()
@@ -550,21 +562,45 @@ int init_signal_state(fmd_batch* b)
   return 0;
 }
 
-template <typename T>
-int zero_rows(T* p, size_t rows, size_t CP)
+/* What cFmDecoder::Reset (FmDecode.cpp:326-338) + cRDSRxSignalProcessor::Reset (RDSProcess.cpp:92-118) clear on
+ * the device, per channel: the demod / RDS recurrences, the T-1 history rows of the RDS low-pass (both parities of
+ * rdsraw) and of the matched filter (rpll), and the status words of the meters Reset clears.  Tuner index,
+ * FIR / resampler histories, pilot PLL, half-band histories, oscillator, de-emphasis, notch, audio LPF and the
+ * block-sync shift register stay, like the reference.  Every region is rows x CP elements, time-major.  ONE list:
+ * do_reset zeroes it for the whole batch, k_channel_reset for the channels fmd_batch_reset_channels lists; the
+ * ring phases that go with it are rds_lpf_g / mf_g (whole batch) and the origins (single channels). */
+std::vector<fmd::ResetRegion> reset_regions(const fmd_batch* b)
 {
-  return hipMemset(p, 0, rows * CP * sizeof(T)) == hipSuccess ? 0 : -1;
+  using namespace fmd;
+  std::vector<ResetRegion> v;
+  auto add = [&](void* p, size_t rows, unsigned esz) {
+    if (p && rows)
+      v.push_back(ResetRegion{p, unsigned(rows), esz});
+  };
+  const ChannelState& s = b->st;
+  for (int slot : {F_IF_LEVEL, F_BB_MEAN, F_BB_LEVEL, F_DC_OFF, F_NCO_INCR, F_NCO_PHASE, F_R_PHASE, F_R_FREQ, F_R_W1,
+                   F_R_W2, F_R_LAST_SYNC, F_R_LAST_SLOPE, F_R_LAST_DATA})
+    add(s.F(slot), 1, 4);
+  for (int slot : {I_STEREO, I_STEREO_Q0, I_STEREO_Q1, I_STEREO_Q2, I_STEREO_Q3, I_R_LAST_BIT, I_R_BITPOS, I_R_BLOCK,
+                   I_R_STATE, I_R_BOFF})
+    add(s.I(slot), 1, 4);
+  for (int q = 0; q < 2; q++)
+    add(b->rdsraw[q].p, b->des.rds_lpf_taps.size() - 1, 8);
+  add(b->rpll.p, b->des.rds_mf_taps.size() - 1, 4);
+  // the getters' snapshot follows: the meters Reset clears read zero, pilot level and the receiver's audio
+  // meter stay (every call rewrites these words before its status record copies them)
+  if (b->d_status.p)
+    for (int w : {HS_IF_LEVEL, HS_BB_MEAN, HS_BB_LEVEL, HS_STEREO, HS_R_STATE})
+      add(b->d_status.p + size_t(w) * b->CP, 1, 4);
+  return v;
 }
 
-/* cFmDecoder::Reset (FmDecode.cpp:326-338) + cRDSRxSignalProcessor::Reset (RDSProcess.cpp:92-118):
- * clears the demod/RDS recurrences and re-initialises the three RDS filters; leaves tuner index,
- * FIR/resampler histories, pilot PLL, half-band histories, oscillator, de-emphasis, notch,
- * audio LPF and the block-sync shift register untouched, like the reference. */
 template <class IN>
 int launch_if_stage(fmd_batch* b, const void* d_iq, size_t iq_channel_stride, unsigned N, unsigned pos,
                     unsigned M, int q, hipStream_t sF, const std::function<void(int)>& mark,
                     hipEvent_t ev_start, hipEvent_t ev_stop);
 
+/* the whole batch: reset_regions, the ring phases, the per-channel ring origins, the group decoders */
 int do_reset(fmd_batch* b)
 {
   if (b->twin && do_reset(b->twin.get())) // the silent twin receives every whole-batch reset too
@@ -581,24 +617,12 @@ int do_reset(fmd_batch* b)
     b->fail_msg.clear();
     return 0;
   }
-  const size_t CP = b->CP;
-  using namespace fmd;
-  const ChannelState& s = b->st;
-  const int fz[] = {F_IF_LEVEL, F_BB_MEAN, F_BB_LEVEL, F_DC_OFF, F_NCO_INCR, F_NCO_PHASE, F_R_PHASE,
-                    F_R_FREQ, F_R_W1, F_R_W2, F_R_LAST_SYNC, F_R_LAST_SLOPE, F_R_LAST_DATA};
-  for (int slot : fz)
-    if (hipMemset(s.F(slot), 0, CP * sizeof(float)) != hipSuccess)
+  for (const fmd::ResetRegion& r : reset_regions(b))
+    if (hipMemset(r.dst, 0, size_t(r.rows) * b->CP * r.esz) != hipSuccess)
       return -1;
-  const int iz[] = {I_STEREO, I_STEREO_Q0, I_STEREO_Q1, I_STEREO_Q2, I_STEREO_Q3, I_R_LAST_BIT, I_R_BITPOS, I_R_BLOCK, I_R_STATE, I_R_BOFF};
-  for (int slot : iz)
-    if (hipMemset(s.I(slot), 0, CP * sizeof(int)) != hipSuccess)
-      return -1;
-  // RDS LPF ring (history rows of rdsraw), matched filter ring, positions
-  if (zero_rows(b->rdsraw[0].p, b->des.rds_lpf_taps.size() - 1, CP) ||
-      zero_rows(b->rdsraw[1].p, b->des.rds_lpf_taps.size() - 1, CP))
+  if (b->org.p && hipMemset(b->org.p, 0, b->org.n * sizeof(unsigned)) != hipSuccess)
     return -1;
-  if (zero_rows(b->rpll.p, b->des.rds_mf_taps.size() - 1, CP))
-    return -1;
+  b->origins_live = false; // every channel in the batch's phase again: the ring filters without origins
   b->rds_lpf_g = 0;
   b->mf_g = 0;
   for (auto& g : b->gdec)
@@ -611,12 +635,7 @@ int do_reset(fmd_batch* b)
   }
   b->failed = false;
   b->fail_msg.clear();
-  // the getters' snapshot follows: the meters Reset clears (FmDecode.cpp:326-338) read zero, pilot
-  // level and the receiver's audio meter stay
-  if (b->d_status.p)
-    for (int w : {fmd::HS_IF_LEVEL, fmd::HS_BB_MEAN, fmd::HS_BB_LEVEL, fmd::HS_STEREO, fmd::HS_R_STATE})
-      if (hipMemset(b->d_status.p + size_t(w) * CP, 0, CP * sizeof(unsigned)) != hipSuccess)
-        return -1;
+  // the host's copy of the snapshot: the words reset_regions zeroes in the device record
   if (b->h_status.p)
     host_status_update(b, [](unsigned* h, size_t CP) {
       for (int w : {fmd::HS_IF_LEVEL, fmd::HS_BB_MEAN, fmd::HS_BB_LEVEL, fmd::HS_STEREO, fmd::HS_R_STATE})
@@ -1056,6 +1075,14 @@ int create_one(const fmd_params* params, unsigned n_channels, const int* tuning_
     return fail(FMD_ERR_DEVICE, "host-mapped status snapshot allocation failed");
   if (b->d_status.alloc(size_t(fmd::HS_WORDS) * CP))
     return fail(FMD_ERR_DEVICE, "status record allocation failed");
+  // single-channel edits (fmd_batch_reset_channels, fmd_batch_retune_channels): the ring origins and the staging of
+  // the edit lists, a slot per call index mod NSLOT with room for every channel's restart and reset
+  if (b->org.alloc(size_t(2) * CP) || b->d_edits.alloc(size_t(fmd_batch::NSLOT) * 2 * C))
+    return fail(FMD_ERR_DEVICE, "device allocation of the channel edit state failed");
+  if (b->h_edits.alloc(size_t(fmd_batch::NSLOT) * 2 * C))
+    return fail(FMD_ERR_DEVICE, "page-locked staging allocation failed");
+  for (auto& e : b->edit_ev)
+    HIPCHK(e.create());
   bind_state(b.get());
   if (!b->st.err || !b->st.hs)
     return fail(FMD_ERR_DEVICE, "host-mapped memory has no device address");
@@ -1295,20 +1322,21 @@ int build_restart_table(fmd_batch* x, const fmd_batch* tw)
   for (size_t s = 1; s < d.hb.size(); s++)
     bad |= add(4, x->hbbuf[s - 1].p, tw->hbbuf[s - 1].p, unsigned(d.hb[s].len - 1), 8, x->CP, 1, tw->CP);
   bad |= rows2(5, x->rdsraw, tw->rdsraw, unsigned(d.rds_lpf_taps.size() - 1));
+  bad |= add(5, x->org.p, tw->org.p, 1, 4, x->CP, 1, tw->CP); // ring origin: the twin's is 0, the batch phase
   bad |= add(6, x->rpll.p, tw->rpll.p, unsigned(d.rds_mf_taps.size() - 1), 4, x->CP, 1, tw->CP);
+  bad |= add(6, x->org.p + x->CP, tw->org.p + tw->CP, 1, 4, x->CP, 1, tw->CP);
   bad |= rows2(7, x->rs, tw->rs, unsigned(d.lpf_taps.size() - 1));
   if (bad)
     return fail(FMD_ERR_ARG, "fmd_batch_enable_retune: this geometry has more carried regions than the restart takes");
-  // staging of the edit lists: a slot per call index mod NSLOT; at most one tuner row per distinct shift
+  // staging of the new tuner rows (the edit lists' is the batch's own): a slot per call index mod NSLOT, at most
+  // one row per distinct shift
   const unsigned T = d.table_size;
   x->restart_rows_cap = std::min(2 * T - 1, x->C);
   const size_t rows_per_slot = size_t(x->restart_rows_cap) * T;
-  if (x->d_edits.alloc(size_t(fmd_batch::NSLOT) * x->C) || x->d_rows.alloc(fmd_batch::NSLOT * rows_per_slot))
+  if (x->d_rows.alloc(fmd_batch::NSLOT * rows_per_slot))
     return fail(FMD_ERR_DEVICE, "fmd_batch_enable_retune: device allocation failed");
-  if (x->h_edits.alloc(size_t(fmd_batch::NSLOT) * x->C) || x->h_rows.alloc(fmd_batch::NSLOT * rows_per_slot))
+  if (x->h_rows.alloc(fmd_batch::NSLOT * rows_per_slot))
     return fail(FMD_ERR_DEVICE, "fmd_batch_enable_retune: page-locked staging allocation failed");
-  for (auto& e : x->edit_ev)
-    HIPCHK(e.create());
   HIPCHK(x->edit_done.create());
   return FMD_OK;
 }
@@ -1333,65 +1361,125 @@ hipError_t order_after_calls(fmd_batch* x, hipStream_t s)
 }
 
 /* The pending edits of a batch with buffers of its own (plain or sub-batch), submitted in front of its next call:
- * on the stream its IF FIR will take, behind every earlier call of the batch and of the twin -- so no call in
- * flight sees a changed byte, and every kernel of the next call (they all run behind its IF FIR) sees the new
- * state.  The twin's next call goes behind the restart too (it reads the twin as the previous call left it). */
-int submit_restart(fmd_batch* x, fmd_batch* tw, hipStream_t stream)
+ * on the stream its IF FIR will take, behind every earlier call of the batch (and of the twin, for restarts) -- so
+ * no call in flight sees a changed byte, and every kernel of the next call (they all run behind its IF FIR) sees the
+ * new state.  Edits of one channel apply in the order they were made: a retune replaces all the state a reset
+ * clears (so a reset in front of it drops out), a reset behind a retune clears the restarted state again.  So the
+ * restarts (k_channel_restart) go first, then the resets (k_channel_reset).  The twin's next call goes behind a
+ * restart too (it reads the twin as the previous call left it). */
+int submit_edits(fmd_batch* x, fmd_batch* tw, hipStream_t stream)
 {
   if (x->edits.empty())
     return FMD_OK;
   const bool serial_mode = x->concurrency == 0 || x->profiling >= 2;
   const hipStream_t sF = serial_mode ? stream : x->s_fir;
   const unsigned T = x->des.table_size;
-  // several edits of one channel before a call apply in order: the last shift is the one that counts.  A table row
-  // depends on the shift's remainder as C++ takes it (sign included: make_tuner_lut reduces shift * i so, and the
-  // angles of s and s - T are different floats), so there are at most 2 T - 1 distinct rows
-  std::map<unsigned, int> last;
+  // what each edited channel ends up with.  The last retune's shift counts; a table row depends on the shift's
+  // remainder as C++ takes it (sign included: make_tuner_lut reduces shift * i so, and the angles of s and s - T
+  // are different floats), so there are at most 2 T - 1 distinct rows
+  struct Fate
+  {
+    bool retune = false, reset = false;
+    int shift = 0;
+  };
+  std::map<unsigned, Fate> fate;
   for (const auto& e : x->edits)
-    last[e.ch] = int((long long)(e.shift) % (long long)T);
+  {
+    Fate& f = fate[e.ch];
+    if (e.reset)
+      f.reset = true;
+    else
+      f = Fate{true, false, int((long long)(e.shift) % (long long)T)};
+  }
   x->edits.clear();
   const int slot = int(x->restart_seq++ % fmd_batch::NSLOT);
-  if (x->edit_ev_used[slot]) // the copy of NSLOT restarts ago (long done unless the caller never waits)
+  if (x->edit_ev_used[slot]) // the copy of NSLOT edits ago (long done unless the caller never waits)
     HIPCHK(hipEventSynchronize(x->edit_ev[slot]));
-  int2* he = x->h_edits.p + size_t(slot) * x->C;
-  float2* hr = x->h_rows.p + size_t(slot) * x->restart_rows_cap * T;
+  int2* he = x->h_edits.p + size_t(slot) * 2 * x->C;
+  float2* hr = x->h_rows.p ? x->h_rows.p + size_t(slot) * x->restart_rows_cap * T : nullptr;
   std::map<int, int> row_of; // shift % T -> row of the staging table
-  unsigned n = 0;
-  for (const auto& [ch, s] : last) // channel order: the kernel's writes of one row go to neighbouring channels
+  unsigned n_rs = 0, n_z = 0;
+  for (const auto& [ch, f] : fate) // channel order: the kernels' writes of one row go to neighbouring channels
   {
-    auto it = row_of.find(s);
+    if (!f.retune)
+      continue;
+    if (!tw) // (fmd_batch_retune_channels refuses a batch without a twin)
+      return fail(FMD_ERR_STATE, "a retune of a batch without retuning enabled");
+    auto it = row_of.find(f.shift);
     if (it == row_of.end())
     {
       const int r = int(row_of.size());
-      it = row_of.emplace(s, r).first;
-      const auto lut = fmd::make_tuner_lut(T, s);
+      it = row_of.emplace(f.shift, r).first;
+      const auto lut = fmd::make_tuner_lut(T, f.shift);
       std::memcpy(hr + size_t(r) * T, lut.data(), size_t(T) * sizeof(float2));
     }
-    he[n++] = make_int2(int(ch), it->second);
+    he[n_rs++] = make_int2(int(ch), it->second);
   }
-  int2* de = x->d_edits.p + size_t(slot) * x->C;
-  float2* dr = x->d_rows.p + size_t(slot) * x->restart_rows_cap * T;
+  for (const auto& [ch, f] : fate)
+    if (f.reset)
+      he[n_rs + n_z++] = make_int2(int(ch), 0);
+  int2* de = x->d_edits.p + size_t(slot) * 2 * x->C;
   HIPCHK(order_after_calls(x, sF));
-  HIPCHK(order_after_calls(tw, sF));
-  HIPCHK(hipMemcpyAsync(de, he, n * sizeof(int2), hipMemcpyHostToDevice, sF));
-  HIPCHK(hipMemcpyAsync(dr, hr, row_of.size() * T * sizeof(float2), hipMemcpyHostToDevice, sF));
+  if (n_rs)
+    HIPCHK(order_after_calls(tw, sF));
+  HIPCHK(hipMemcpyAsync(de, he, (n_rs + n_z) * sizeof(int2), hipMemcpyHostToDevice, sF));
+  float2* dr = nullptr;
+  if (n_rs)
+  {
+    dr = x->d_rows.p + size_t(slot) * x->restart_rows_cap * T;
+    HIPCHK(hipMemcpyAsync(dr, hr, row_of.size() * T * sizeof(float2), hipMemcpyHostToDevice, sF));
+  }
   HIPCHK(hipEventRecord(x->edit_ev[slot], sF));
   x->edit_ev_used[slot] = true;
-  fmd::RestartTable tab{};
-  for (int i = 0; i < x->restart_tab.n; i++)
-    if (x->restart_group[i] != x->restart_skip)
-      tab.r[tab.n++] = x->restart_tab.r[i];
-  // a few edits: one workgroup per region; all channels: ~8 rows of every region per workgroup and pass
-  const unsigned blocks = std::min(64u, (n * 8u + 255u) / 256u);
-  hipLaunchKernelGGL(fmd::k_channel_restart, dim3(blocks, tab.n + 1), dim3(256), 0, sF, tab, (const int2*)de, n,
-                     (const float2*)dr, (float2*)x->lut.p, T);
-  HIPCHK(hipGetLastError());
-  if (sF != tw->s_fir)
+  if (n_rs)
+  {
+    fmd::RestartTable tab{};
+    for (int i = 0; i < x->restart_tab.n; i++)
+      if (x->restart_group[i] != x->restart_skip)
+        tab.r[tab.n++] = x->restart_tab.r[i];
+    // a few edits: one workgroup per region; all channels: ~8 rows of every region per workgroup and pass
+    const unsigned blocks = std::min(64u, (n_rs * 8u + 255u) / 256u);
+    hipLaunchKernelGGL(fmd::k_channel_restart, dim3(blocks, tab.n + 1), dim3(256), 0, sF, tab, (const int2*)de, n_rs,
+                       (const float2*)dr, (float2*)x->lut.p, T);
+    HIPCHK(hipGetLastError());
+  }
+  if (n_z)
+  {
+    fmd::ResetTable tab{};
+    for (const fmd::ResetRegion& r : reset_regions(x))
+    {
+      if (tab.n >= fmd::kResetMaxRegions)
+        return fail(FMD_ERR_ARG, "fmd_batch_reset_channels: more reset regions than k_channel_reset takes");
+      tab.r[tab.n++] = r;
+    }
+    tab.CP = x->CP;
+    tab.origin = x->org.p;
+    // the next call's first RDS-rate sample is sample 0 of the reset channels' rings
+    tab.org_lpf = x->dbg_reset_keep_phase ? 0u : x->rds_lpf_g;
+    tab.org_mf = x->dbg_reset_keep_phase ? 0u : x->mf_g;
+    const unsigned blocks = std::min(64u, (n_z * 8u + 255u) / 256u);
+    hipLaunchKernelGGL(fmd::k_channel_reset, dim3(blocks, tab.n + 1), dim3(256), 0, sF, tab,
+                       (const int2*)(de + n_rs), n_z);
+    HIPCHK(hipGetLastError());
+    x->origins_live = true;
+  }
+  if (n_rs && sF != tw->s_fir)
   {
     HIPCHK(hipEventRecord(x->edit_done, sF));
     HIPCHK(hipStreamWaitEvent(tw->s_fir, x->edit_done, 0));
   }
   return FMD_OK;
+}
+
+/* The batches with buffers of their own behind a caller-facing batch: its sub-batches, or itself */
+std::vector<fmd_batch*> buffer_batches(fmd_batch* b)
+{
+  std::vector<fmd_batch*> v;
+  for (auto& sb : b->subs)
+    v.push_back(sb.get());
+  if (v.empty())
+    v.push_back(b);
+  return v;
 }
 
 /* the shift channel c of the caller-facing batch b decodes with in call `ci` */
@@ -1407,7 +1495,7 @@ int shift_at(fmd_batch* b, unsigned c, uint32_t ci)
 }
 
 /* The group decoder of channel c before a group of call ci: reset once at the first group of a call at or behind
- * a retune of the channel (groups of earlier calls, collected late, still go through the old state). */
+ * a retune or reset of the channel (groups of earlier calls, collected late, still go through the old state). */
 void gdec_follow_edits(fmd_batch* b, unsigned c, uint32_t ci)
 {
   uint32_t k_last = 0;
@@ -1436,12 +1524,12 @@ static int wait_impl(fmd_batch* b, int lag, void* stream_, bool take_lost);
 static int process_shell(fmd_batch* b, const void* d_iq, IqFormat fmt, size_t iq_channel_stride, unsigned samples,
                          float* d_audio, size_t audio_channel_stride, unsigned* out_floats, void* stream);
 
-/* A batch with retuning enabled: the pending restarts in front of the call, the silent twin's call (zeros of the
- * same size, on the same streams) behind it.  Without fmd_batch_enable_retune only the plain path runs. */
+/* Pending single-channel edits (retunes, resets) in front of the call; with retuning enabled, the silent twin's call
+ * (zeros of the same size, on the same streams) behind it.  A batch with neither takes the plain path alone. */
 static int process_any(fmd_batch* b, const void* d_iq, IqFormat fmt, size_t iq_channel_stride, unsigned samples,
                        float* d_audio, size_t audio_channel_stride, unsigned* out_floats, void* stream)
 {
-  if (!b || !b->twin)
+  if (!b || (!b->twin && !b->edits_pending))
     return process_shell(b, d_iq, fmt, iq_channel_stride, samples, d_audio, audio_channel_stride, out_floats, stream);
   if (!d_iq || !d_audio)
     return fail(FMD_ERR_ARG, "fmd_batch_process_device: null argument");
@@ -1452,21 +1540,16 @@ static int process_any(fmd_batch* b, const void* d_iq, IqFormat fmt, size_t iq_c
     return rc;
   HIPCHK(hipSetDevice(b->device));
   fmd_batch* tw = b->twin.get();
-  for (fmd_batch* x : is_shell(b) ? [&] {
-         std::vector<fmd_batch*> v;
-         for (auto& sb : b->subs)
-           v.push_back(sb.get());
-         return v;
-       }()
-                                  : std::vector<fmd_batch*>{b})
-    if (int rc = submit_restart(x, tw, static_cast<hipStream_t>(stream)))
+  for (fmd_batch* x : buffer_batches(b))
+    if (int rc = submit_edits(x, tw, static_cast<hipStream_t>(stream)))
     {
-      mark_failed(b, "a channel restart could not be submitted");
+      mark_failed(b, "a channel edit could not be submitted");
       return rc;
     }
+  b->edits_pending = false;
   const int rc =
       process_shell(b, d_iq, fmt, iq_channel_stride, samples, d_audio, audio_channel_stride, out_floats, stream);
-  if (rc != FMD_OK)
+  if (rc != FMD_OK || !tw)
     return rc;
   const int trc = process_device_impl(tw, b->twin_iq.p, IQ_F32, 0, samples, b->twin_audio.p,
                                       b->twin_audio.n, nullptr, stream);
@@ -1625,6 +1708,16 @@ int fmd_batch_debug_restart_skip(fmd_batch* b, int region)
   return FMD_OK;
 }
 
+int fmd_batch_debug_reset_keep_ring_phase(fmd_batch* b, int on)
+{
+  if (!b)
+    return fail(FMD_ERR_ARG, "null batch");
+  b->dbg_reset_keep_phase = on != 0;
+  for (auto& sb : b->subs)
+    sb->dbg_reset_keep_phase = on != 0;
+  return FMD_OK;
+}
+
 int fmd_batch_debug_host_ms(fmd_batch* b, float out[4])
 {
   if (!b || !out)
@@ -1738,9 +1831,9 @@ int fmd_batch_enable_retune(fmd_batch* b)
   HIPCHK(hipDeviceSynchronize());
   {
     std::lock_guard<std::mutex> lk(b->log_mu);
-    b->shift_log.assign(b->C, {});
+    b->shift_log.resize(b->C); // (resets made before the first call may have started it)
   }
-  b->gdec_epoch.assign(b->C, 0u);
+  b->gdec_epoch.resize(b->C, 0u);
   b->twin = std::move(twin);
   return FMD_OK;
 }
@@ -1765,13 +1858,49 @@ int fmd_batch_retune_channels(fmd_batch* b, const unsigned* channels, const int*
   {
     unsigned lc = 0;
     fmd_batch* ob = owner_of(b, channels[i], &lc);
-    ob->edits.push_back(fmd_batch::Edit{lc, shifts[i]});
+    ob->edits.push_back(fmd_batch::Edit{lc, shifts[i], false});
     auto& log = b->shift_log[channels[i]];
     if (!log.empty() && log.back().first == k)
       log.back().second = shifts[i];
     else
       log.emplace_back(k, shifts[i]);
   }
+  b->edits_pending = true;
+  return FMD_OK;
+}
+
+int fmd_batch_reset_channels(fmd_batch* b, const unsigned* channels, unsigned n)
+{
+  if (!b || !channels)
+    return fail(FMD_ERR_ARG, "fmd_batch_reset_channels: null argument");
+  if (b->failed)
+    return fail(FMD_ERR_ARG, "fmd_batch_reset_channels: the batch has failed (fmd_batch_reset clears it)");
+  std::vector<unsigned> seen(channels, channels + n);
+  std::sort(seen.begin(), seen.end());
+  if (n && seen.back() >= b->C)
+    return fail(FMD_ERR_ARG, "fmd_batch_reset_channels: channel " + std::to_string(seen.back()) + " out of range");
+  if (std::adjacent_find(seen.begin(), seen.end()) != seen.end())
+    return fail(FMD_ERR_ARG, "fmd_batch_reset_channels: a channel is listed twice");
+  if (n == 0)
+    return FMD_OK;
+  const uint32_t k = b->call_index + 1; // the call the edit takes effect at
+  std::lock_guard<std::mutex> lk(b->log_mu);
+  if (b->shift_log.empty())
+  {
+    b->shift_log.resize(b->C);
+    b->gdec_epoch.assign(b->C, 0u);
+  }
+  for (unsigned i = 0; i < n; i++)
+  {
+    unsigned lc = 0;
+    fmd_batch* ob = owner_of(b, channels[i], &lc);
+    ob->edits.push_back(fmd_batch::Edit{lc, 0, true});
+    // the log marks the call for the group decoder; the shift stays what it is
+    auto& log = b->shift_log[channels[i]];
+    if (log.empty() || log.back().first != k)
+      log.emplace_back(k, log.empty() ? b->shifts[channels[i]] : log.back().second);
+  }
+  b->edits_pending = true;
   return FMD_OK;
 }
 
@@ -1926,7 +2055,7 @@ int fmd_batch_collect_rds_lagged(fmd_batch* b, fmd_rds_group* out, unsigned cap,
   {
     if (run_group_decoder && r.channel < b->C)
     {
-      if (b->twin)
+      if (!b->shift_log.empty())
         gdec_follow_edits(b, r.channel, r.call_index);
       auto& g = b->gdec[r.channel];
       if (!g)

@@ -60,17 +60,25 @@ fmd::AudioConsts audio_consts(const fmd::Design& d)
 }
 
 /* One of the post chain's two complex ring-buffer filters (cFirFilter::Process / ProcessTwo: RDS 75-tap low-pass,
- * audio 29-tap low-pass) on stream st; g0 = the ring phase at the call's first sample. */
+ * audio 29-tap low-pass) on stream st; g0 = the ring phase at the call's first sample; origin: the channels' ring
+ * origins where some were reset on their own (fmd_batch::org), else null. */
 void launch_ring2(fmd_batch* b, hipStream_t st, const float2* in, float2* out, unsigned n, unsigned T,
-                  const float* taps, unsigned g0)
+                  const float* taps, unsigned g0, const unsigned* origin = nullptr)
 {
   const unsigned C = b->C, CP = b->CP;
-  if (b->dbg_ring4 && T >= unsigned(fmd::RG))
-    hipLaunchKernelGGL(fmd::k_ring_fir4<float2>, dim3(CP / 64, (n + 4 * fmd::RG - 1) / (4 * fmd::RG)), dim3(64, 4), 0,
-                       st, in, out, n, int(T), taps, g0, C, CP, 0u, 0u);
+  const dim3 g4(CP / 64, (n + 4 * fmd::RG - 1) / (4 * fmd::RG)), gt(CP / 64, (n + fmd::RF_TI - 1) / fmd::RF_TI);
+  const size_t lds = size_t(T - 1 + fmd::RF_TI) * 64 * sizeof(float2);
+  const bool four = b->dbg_ring4 && T >= unsigned(fmd::RG);
+  if (origin && four)
+    hipLaunchKernelGGL(fmd::k_ring_fir4_org<float2>, g4, dim3(64, 4), 0, st, in, out, n, int(T), taps, g0, C, CP, 0u,
+                       0u, origin);
+  else if (origin)
+    hipLaunchKernelGGL(fmd::k_ring_fir_org<float2>, gt, dim3(64, 4), lds, st, in, out, n, int(T), taps, g0, C, CP, 0u,
+                       origin);
+  else if (four)
+    hipLaunchKernelGGL(fmd::k_ring_fir4<float2>, g4, dim3(64, 4), 0, st, in, out, n, int(T), taps, g0, C, CP, 0u, 0u);
   else
-    hipLaunchKernelGGL(fmd::k_ring_fir<float2>, dim3(CP / 64, (n + fmd::RF_TI - 1) / fmd::RF_TI), dim3(64, 4),
-                       size_t(T - 1 + fmd::RF_TI) * 64 * sizeof(float2), st, in, out, n, int(T), taps, g0, C, CP, 0u);
+    hipLaunchKernelGGL(fmd::k_ring_fir<float2>, gt, dim3(64, 4), lds, st, in, out, n, int(T), taps, g0, C, CP, 0u);
 }
 
 /* A call appends its RDS groups to queue[es]; if the queue's previous contents were handed to an
@@ -100,7 +108,7 @@ void launch_light_rds(fmd_batch* b, const fmd_batch::LightJob& j, hipStream_t s)
     if (hipStreamWaitEvent(s, b->cev[j.es][fmd_batch::EV_DEC], 0) != hipSuccess)
       mark_failed(b, "hipStreamWaitEvent failed in front of the RDS low-pass of a call");
     const unsigned T_lpf = unsigned(d.rds_lpf_taps.size());
-    launch_ring2(b, s, b->rdsraw[j.q].p, b->rlpf[j.q].p, j.R, T_lpf, b->rds_lpf_taps.p, j.rds_lpf_g);
+    launch_ring2(b, s, b->rdsraw[j.q].p, b->rlpf[j.q].p, j.R, T_lpf, b->rds_lpf_taps.p, j.rds_lpf_g, j.org);
     hipLaunchKernelGGL(fmd::k_roll<float2>, rgrid(T_lpf - 1), rt, 0, s, b->rdsraw[j.q].p, b->rdsraw[j.q ^ 1].p,
                        T_lpf - 1, j.R, CP);
     if (hipEventRecord(b->cev[j.es][fmd_batch::EV_RDSH], s) != hipSuccess)
@@ -111,12 +119,20 @@ void launch_light_rds(fmd_batch* b, const fmd_batch::LightJob& j, hipStream_t s)
   const FmdSincosTab sct{d.sct_inv_h, d.sct_h_hi, d.sct_h_lo};
   hipLaunchKernelGGL(fmd::k_rds_pll, dim3((CP / 64 + fmd::RP_WAVES - 1) / fmd::RP_WAVES), dim3(64, fmd::RP_WAVES), 0,
                      s, b->rlpf[j.q].p, j.R, C, CP, k, b->st, b->rpll.p, T_mf - 1, b->sctab.p, sct);
-  if (T_mf >= unsigned(fmd::RG))
-    hipLaunchKernelGGL(fmd::k_ring_fir4<float>, dim3(CP / 64, (j.R + 4 * fmd::RG - 1) / (4 * fmd::RG)), dim3(64, 4),
-                       0, s, b->rpll.p, b->rmf.p, j.R, int(T_mf), b->mf_taps2.p, j.mf_g, C, CP, 0u, 3u);
+  const dim3 mf4(CP / 64, (j.R + 4 * fmd::RG - 1) / (4 * fmd::RG)), mft(CP / 64, (j.R + fmd::RF_TI - 1) / fmd::RF_TI);
+  const size_t mf_lds = size_t(T_mf - 1 + fmd::RF_TI) * 64 * sizeof(float);
+  const unsigned* mf_org = j.org ? j.org + CP : nullptr; // (the matched filter's origins: the second row)
+  if (T_mf >= unsigned(fmd::RG) && mf_org)
+    hipLaunchKernelGGL(fmd::k_ring_fir4_org<float>, mf4, dim3(64, 4), 0, s, b->rpll.p, b->rmf.p, j.R, int(T_mf),
+                       b->mf_taps2.p, j.mf_g, C, CP, 0u, 3u, mf_org);
+  else if (T_mf >= unsigned(fmd::RG))
+    hipLaunchKernelGGL(fmd::k_ring_fir4<float>, mf4, dim3(64, 4), 0, s, b->rpll.p, b->rmf.p, j.R, int(T_mf),
+                       b->mf_taps2.p, j.mf_g, C, CP, 0u, 3u);
+  else if (mf_org)
+    hipLaunchKernelGGL(fmd::k_ring_fir_org<float>, mft, dim3(64, 4), mf_lds, s, b->rpll.p, b->rmf.p, j.R, int(T_mf),
+                       b->mf_taps2.p, j.mf_g, C, CP, 0u, mf_org);
   else
-    hipLaunchKernelGGL(fmd::k_ring_fir<float>, dim3(CP / 64, (j.R + fmd::RF_TI - 1) / fmd::RF_TI), dim3(64, 4),
-                       size_t(T_mf - 1 + fmd::RF_TI) * 64 * sizeof(float), s, b->rpll.p, b->rmf.p, j.R, int(T_mf),
+    hipLaunchKernelGGL(fmd::k_ring_fir<float>, mft, dim3(64, 4), mf_lds, s, b->rpll.p, b->rmf.p, j.R, int(T_mf),
                        b->mf_taps2.p, j.mf_g, C, CP, 0u);
   hipLaunchKernelGGL(fmd::k_roll<float>, rgrid(T_mf - 1), rt, 0, s, b->rpll.p, b->rpll.p, T_mf - 1, j.R, CP);
   // Two light streams: the PREVIOUS call's status record (on the audio half's stream) copies the RDS state this
@@ -255,6 +271,9 @@ int process_device_impl(fmd_batch* b, const void* d_iq, IqFormat fmt, size_t iq_
   const unsigned T_lpf = unsigned(d.rds_lpf_taps.size());
   const unsigned T_mf = unsigned(d.rds_mf_taps.size());
   const unsigned T_alp = unsigned(d.lpf_taps.size());
+  // the ring origins of the RDS low-pass and matched filter, once a channel was reset on its own (the audio
+  // low-pass is not reset: it never takes them)
+  const unsigned* rds_org = b->origins_live ? b->org.p : nullptr;
   const unsigned Hbb = d.rs_order;
   // The call's index and everything derived from it (buffer parity, event slot) are locals until the
   // call has been submitted: a call that is refused leaves the batch exactly as it was.
@@ -635,7 +654,7 @@ int process_device_impl(fmd_batch* b, const void* d_iq, IqFormat fmt, size_t iq_
       return;
     }
     auto lpf = [&]() {
-      launch_ring2(b, sLPr, b->rdsraw[q].p, b->rlpf[q].p, R, T_lpf, b->rds_lpf_taps.p, b->rds_lpf_g);
+      launch_ring2(b, sLPr, b->rdsraw[q].p, b->rlpf[q].p, R, T_lpf, b->rds_lpf_taps.p, b->rds_lpf_g, rds_org);
       if (hb_all_normal)
       {
         roll_later(b->rdsraw[q].p, b->rdsraw[q ^ 1].p, T_lpf - 1, R);
@@ -730,6 +749,7 @@ int process_device_impl(fmd_batch* b, const void* d_iq, IqFormat fmt, size_t iq_
   job.R = R;
   job.A = A;
   job.mf_g = b->mf_g;
+  job.org = rds_org;
   job.q = q;
   job.es = es;
   job.sq = sq;

@@ -465,13 +465,51 @@ __global__ __launch_bounds__(256) void k_halfband_chain(
  * in LDS ([row][channel]: conflict-free reads), because every input row is needed by T different
  * outputs and re-reading it from L2 for each made the kernel L2-bandwidth bound.
  * E = float2 for the complex / two-stream filters, float for the RDS matched filter. */
-template <typename E>
-__global__ __launch_bounds__(256) void k_ring_fir(const E* __restrict__ in, E* __restrict__ out,
-                                                  unsigned n, int T, const float* __restrict__ taps,
-                                                  unsigned g0, unsigned C, unsigned CP, unsigned Hout)
+/* Per-channel ring origins (fmd_batch_reset_channels): a channel reset when the batch's
+ * ring phase was origin[c] is origin[c] samples behind the batch, so its output i has phase
+ * (g0 + i - origin[c]) mod T.  ring_wave_g0 gives every lane its own start phase (*lane_g0) and returns the
+ * wave's common one where all of its channels share one origin (the usual case: nothing reset, a capture's
+ * channels or all of them reset together), -1 where they differ.  Lanes past C take lane 0's origin, so that
+ * they never split a wave.  Call it with every lane of the wave active. */
+__device__ __forceinline__ int ring_wave_g0(const unsigned* __restrict__ origin, unsigned c, unsigned C, unsigned g0,
+                                            int T, unsigned* lane_g0)
 {
-  extern __shared__ __attribute__((aligned(16))) unsigned char rtile_raw[];
-  E* rtile = reinterpret_cast<E*>(rtile_raw); // [T - 1 + RF_TI][64]
+  const unsigned o_lane = c < C ? origin[c] : 0u;
+  const unsigned o0 = (unsigned)__builtin_amdgcn_readfirstlane((int)o_lane); // lane 0: a channel of the batch
+  const unsigned o = c < C ? o_lane : o0;
+  *lane_g0 = (g0 + (unsigned)T - o) % (unsigned)T;
+  if (__ballot(o != o0) != 0ull)
+    return -1;
+  return (int)((g0 + (unsigned)T - o0) % (unsigned)T);
+}
+
+/* Output i of one lane with a phase of its own (a wave of mixed origins): the T ages a0, ..., T-1, 0, ..., a0-1 in
+ * one loop of T trips for every lane, the age and the row pointer wrapping per lane.  `now` points at the input of
+ * age 0, age a sits `a * stride` elements before it.  The same products and sums in the same order as the uniform
+ * forms (whose sums start from -0: -0 + k x is k x). */
+template <typename E>
+__device__ __forceinline__ E ring_one_mixed(const E* __restrict__ now, size_t stride, unsigned a0, int T,
+                                            const float* __restrict__ taps)
+{
+  const E* __restrict__ p = now - a0 * stride;
+  E acc = rf_mul(taps[a0], *p);
+  unsigned a = a0;
+  for (int s = 1; s < T; s++)
+  {
+    const bool wrap = a + 1 == (unsigned)T;
+    a = wrap ? 0u : a + 1;
+    p = wrap ? now : p - stride;
+    rf_acc(acc, taps[a], *p);
+  }
+  return acc;
+}
+
+template <typename E, bool ORG>
+__device__ __forceinline__ void ring_fir_tile(E* __restrict__ rtile, const E* __restrict__ in, E* __restrict__ out,
+                                              unsigned n, int T, const float* __restrict__ taps, unsigned g0,
+                                              unsigned C, unsigned CP, unsigned Hout,
+                                              const unsigned* __restrict__ origin)
+{
   const unsigned lane = threadIdx.x;
   const unsigned y = (unsigned)__builtin_amdgcn_readfirstlane((int)threadIdx.y); // 0..3, wave-uniform
   const unsigned c0 = blockIdx.x * 64 + lane;
@@ -483,6 +521,24 @@ __global__ __launch_bounds__(256) void k_ring_fir(const E* __restrict__ in, E* _
   for (unsigned r = y; r < rows; r += 4)
     rtile[r * 64 + lane] = in[(size_t)(i0 + r) * CP + c];
   __syncthreads();
+  unsigned lane_g0 = g0;
+  if constexpr (ORG)
+  { // (the four waves of a workgroup hold the same 64 channels: the same answer in all of them)
+    const int wg0 = ring_wave_g0(origin, c0, C, g0, T, &lane_g0);
+    if (wg0 < 0)
+    {
+      if (c0 >= C)
+        return;
+      for (unsigned q = y; q < nt; q += 4)
+      {
+        const unsigned i = i0 + q;
+        const E* base = rtile + (size_t)((unsigned)T - 1 + q) * 64 + lane;
+        out[(size_t)(Hout + i) * CP + c] = ring_one_mixed<E>(base, 64, (lane_g0 + i) % (unsigned)T, T, taps);
+      }
+      return;
+    }
+    g0 = (unsigned)wg0;
+  }
   if (c0 >= C)
     return;
   for (unsigned q = y; q < nt; q += 4)
@@ -500,6 +556,26 @@ __global__ __launch_bounds__(256) void k_ring_fir(const E* __restrict__ in, E* _
       rf_acc(acc, taps[a], base[-(ptrdiff_t)a * 64]);
     out[(size_t)(Hout + i) * CP + c] = acc;
   }
+}
+
+template <typename E>
+__global__ __launch_bounds__(256) void k_ring_fir(const E* __restrict__ in, E* __restrict__ out,
+                                                  unsigned n, int T, const float* __restrict__ taps,
+                                                  unsigned g0, unsigned C, unsigned CP, unsigned Hout)
+{
+  extern __shared__ __attribute__((aligned(16))) unsigned char rtile_raw[];
+  ring_fir_tile<E, false>(reinterpret_cast<E*>(rtile_raw), in, out, n, T, taps, g0, C, CP, Hout, nullptr);
+}
+
+/* k_ring_fir for a batch with reset channels: per-channel ring origins (RDS low-pass, matched filter) */
+template <typename E>
+__global__ __launch_bounds__(256) void k_ring_fir_org(const E* __restrict__ in, E* __restrict__ out,
+                                                      unsigned n, int T, const float* __restrict__ taps,
+                                                      unsigned g0, unsigned C, unsigned CP, unsigned Hout,
+                                                      const unsigned* __restrict__ origin)
+{
+  extern __shared__ __attribute__((aligned(16))) unsigned char rtile_raw[];
+  ring_fir_tile<E, true>(reinterpret_cast<E*>(rtile_raw), in, out, n, T, taps, g0, C, CP, Hout, origin);
 }
 
 /* The same filter for the two float2 instances on the heavy part of the post chain (RDS low-pass,
@@ -610,6 +686,48 @@ __global__ __launch_bounds__(256) void k_ring_fir4(const E* __restrict__ in, E* 
   unsigned left = min((unsigned)RG, n - i);
   while (left)
   { // as many outputs as stay within one ring period
+    const unsigned room = (unsigned)T - (g0 + i) % (unsigned)T;
+    const unsigned take = min(left, room);
+    ring_dispatch<RG, E>(take, in, out, i, T, taps, g0, c, CP, Hout, store);
+    i += take;
+    left -= take;
+  }
+}
+
+/* k_ring_fir4 for a batch with reset channels: per-channel ring origins (RDS low-pass, matched filter).  A wave
+ * whose channels share one origin runs the groups above with its own g0 (take stays wave-uniform); a mixed wave
+ * takes its outputs one by one, each lane in its own phase (ring_one_mixed). */
+template <typename E>
+__global__ __launch_bounds__(256) void k_ring_fir4_org(const E* __restrict__ in, E* __restrict__ out,
+                                                       unsigned n, int T, const float* __restrict__ taps,
+                                                       unsigned g0, unsigned C, unsigned CP, unsigned Hout,
+                                                       unsigned prio, const unsigned* __restrict__ origin)
+{
+  wave_prio(prio);
+  const unsigned c = blockIdx.x * 64 + threadIdx.x; // < CP: the row buffers are padded
+  const unsigned y = (unsigned)__builtin_amdgcn_readfirstlane((int)threadIdx.y);
+  unsigned i = (blockIdx.y * blockDim.y + y) * RG;
+  if (i >= n)
+    return;
+  const bool store = c < C;
+  unsigned left = min((unsigned)RG, n - i);
+  unsigned lane_g0 = g0;
+  const int wg0 = ring_wave_g0(origin, c, C, g0, T, &lane_g0);
+  if (wg0 < 0)
+  {
+    for (; left; i++, left--)
+    {
+      const unsigned a0 = (lane_g0 + i) % (unsigned)T;
+      const E* __restrict__ now = in + (size_t)((unsigned)T - 1 + i) * CP + c; // age 0
+      const E acc = ring_one_mixed<E>(now, CP, a0, T, taps);
+      if (store)
+        out[(size_t)(Hout + i) * CP + c] = acc;
+    }
+    return;
+  }
+  g0 = (unsigned)wg0;
+  while (left)
+  {
     const unsigned room = (unsigned)T - (g0 + i) % (unsigned)T;
     const unsigned take = min(left, room);
     ring_dispatch<RG, E>(take, in, out, i, T, taps, g0, c, CP, Hout, store);

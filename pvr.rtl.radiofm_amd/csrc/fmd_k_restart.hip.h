@@ -1,8 +1,9 @@
 /*
  * fmd_k_restart.hip.h -- k_channel_restart: restarts single channels of a running batch at a call
- * boundary (fmd_batch_retune_channels).  A retuned channel takes over the carried state of the batch's
- * silent twin (a one-channel batch of the same geometry fed zeros, csrc/fmd_batch.hip) and a new
- * cFineTuner table row; every other channel is left alone.
+ * boundary (fmd_batch_retune_channels); k_channel_reset (below) resets them (fmd_batch_reset_channels).
+ * A retuned channel takes over the carried state of the batch's silent twin (a one-channel batch of
+ * the same geometry fed zeros, csrc/fmd_batch.hip) and a new cFineTuner table row; every other channel
+ * is left alone.
  *
  * What is copied is a list of regions (RestartRegion, built once by the host: the table is in
  * fmd_batch.hip, restart_regions).  A region is one buffer of per-channel state, `rows` elements per
@@ -77,6 +78,60 @@ __global__ __launch_bounds__(256) void k_channel_restart(RestartTable tab, const
       restart_copy<unsigned>(g, edits, n_edits, i);
     else
       restart_copy<unsigned short>(g, edits, n_edits, i);
+  }
+}
+
+/* k_channel_reset: cFmDecoder::Reset (FmDecode.cpp:326-338) of single channels at a call boundary
+ * (fmd_batch_reset_channels).  Every region of a ResetTable is `rows` rows of CP elements of 4 or 8 bytes
+ * (time-major state, channel stride 1); the host builds it from the list fmd_batch_reset's do_reset zeroes for
+ * the whole batch (reset_regions, csrc/fmd_batch.hip).  The listed channels' elements become zero and their two
+ * ring origins (the RDS low-pass's at origin[c], the matched filter's at origin[CP + c]) the batch's ring phases
+ * at the next call's first sample, so that their rings start from slot 0 there like a freshly initialised
+ * cFirFilter (FirFilter.cpp:330-377). */
+constexpr int kResetMaxRegions = 40;
+
+struct ResetRegion
+{
+  void* dst;
+  unsigned rows;
+  unsigned esz; // 4 or 8
+};
+
+struct ResetTable
+{
+  ResetRegion r[kResetMaxRegions];
+  int n;
+  unsigned CP;
+  unsigned* origin;          // [2][CP]
+  unsigned org_lpf, org_mf;  // what the listed channels' origins become
+};
+
+/* blockIdx.y < tab.n: region blockIdx.y for every listed channel (rows x channels elements, grid-stride over x);
+ * blockIdx.y == tab.n: the origins.  channels[e].x is a listed channel (.y unused). */
+__global__ __launch_bounds__(256) void k_channel_reset(ResetTable tab, const int2* __restrict__ channels,
+                                                       unsigned n_ch)
+{
+  const size_t stride = size_t(gridDim.x) * blockDim.x;
+  const size_t first = size_t(blockIdx.x) * blockDim.x + threadIdx.x;
+  if (int(blockIdx.y) == tab.n)
+  {
+    for (size_t e = first; e < n_ch; e += stride)
+    {
+      const unsigned c = unsigned(channels[e].x);
+      tab.origin[c] = tab.org_lpf;
+      tab.origin[size_t(tab.CP) + c] = tab.org_mf;
+    }
+    return;
+  }
+  const ResetRegion g = tab.r[blockIdx.y];
+  const size_t total = size_t(g.rows) * n_ch;
+  for (size_t i = first; i < total; i += stride)
+  {
+    const size_t at = size_t(i / n_ch) * tab.CP + unsigned(channels[i % n_ch].x);
+    if (g.esz == 8)
+      static_cast<unsigned long long*>(g.dst)[at] = 0ull;
+    else
+      static_cast<unsigned*>(g.dst)[at] = 0u;
   }
 }
 
