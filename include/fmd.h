@@ -227,8 +227,50 @@ int fmd_batch_export_rds_device(fmd_batch* b, int32_t* d_records, unsigned cap, 
  * capture is the tuner in front of the IF filter (cFineTuner::Process, FmDecode.cpp:66-82); everything behind it is
  * per channel as ever.  With k > 1 the iq_channel_stride of the process calls is the distance between CAPTURES
  * (G = channels / k input rows instead of one per channel); k = 0 / 1 restores one row per channel.  iq_channel_stride
- * == 0 still means a single capture for the whole batch.  Not while calls are in flight (the device is drained). */
+ * == 0 still means a single capture for the whole batch.  Not while calls are in flight (the device is drained).
+ * It is the contiguous case of the capture map below and replaces any map. */
 int fmd_batch_set_channels_per_capture(fmd_batch* b, unsigned channels_per_capture);
+
+/* Capture maps: any channel reads any capture, and a running channel moves to another capture at a call boundary
+ * with its state carried over -- what the reference's tuner dialog does when it moves the dongle's LO under a
+ * cFmDecoder that keeps running (ChannelSettings.cpp:96-147, 280-289).  DESIGN.md section 9.4.
+ *
+ * fmd_batch_set_capture_map(b, capture_of_channel, n_captures): channel c reads input row capture_of_channel[c];
+ * the process calls (float and byte input, device and host entry points) then take n_captures rows,
+ * iq_channel_stride apart.  Any map: a capture's channels need not be contiguous nor in one sub-batch.  NULL
+ * restores one row per channel; fmd_batch_set_channels_per_capture(b, k) sets the contiguous map c / k and
+ * replaces any map.  iq_channel_stride == 0 still means one capture for every channel.  Not while calls are in
+ * flight (the device is drained).  FMD_ERR_ARG: a null batch, n_captures == 0 with a map, a capture out of range.
+ *
+ * fmd_batch_switch_captures(b, channels, captures, n): from the next call submitted, channel channels[i] reads
+ * capture captures[i]; nothing else about the channel changes.  The channel decodes bit for bit like the same
+ * cFmDecoder whose input stream continues with the new capture's blocks: its IF filter's first outputs mix the old
+ * capture's last tuned samples with the new capture's, and its tuner index, PLLs, RDS sync and UECP group decoder
+ * carry over, so audio, RDS groups (with their call index), getters, UECP frames and PS name all follow.  The
+ * tuner shift stays (the reference never changes a running cFineTuner's; shifts move only through a retune).
+ *  - Works on every batch (no opt-in, no twin).  A batch without a map takes the one its channels-per-capture
+ *    rule gives (channel c reads capture c / k) and the switch on top of it.
+ *  - Nothing waits: a call with switches overlaps the calls before it like any other call.  Calls already
+ *    submitted -- also calls in flight under concurrency mode 2 -- keep the old map.
+ *  - Several edits of one channel before one call (switches, resets, retunes, retunes to a capture) apply in the
+ *    order they were made: the last capture wins.
+ *  - FMD_ERR_ARG: a null batch or list (before the HIP runtime is touched), a channel or capture out of range, a
+ *    channel listed twice, a failed batch (fmd_last_error says which).  Same threading rule as the process calls.
+ *
+ * fmd_batch_retune_channels_to(b, channels, shifts, captures, n): fmd_batch_retune_channels plus a capture: from
+ * the next call on, channel channels[i] decodes like a decoder created with shifts[i] that received zeros until
+ * now, and reads capture captures[i].  Needs fmd_batch_enable_retune (FMD_ERR_STATE otherwise); errors as above.
+ *
+ * fmd_batch_get_capture_map(b, out, cap): writes the captures the next call reads for the first min(cap, channels)
+ * channels and returns the number of input rows the process calls take (n_captures; channels / k without a map). */
+int fmd_batch_set_capture_map(fmd_batch* b, const unsigned* capture_of_channel, unsigned n_captures);
+int fmd_batch_switch_captures(fmd_batch* b, const unsigned* channels, const unsigned* captures, unsigned n);
+int fmd_batch_retune_channels_to(fmd_batch* b, const unsigned* channels, const int* shifts, const unsigned* captures,
+                                 unsigned n);
+int fmd_batch_get_capture_map(fmd_batch* b, unsigned* out, unsigned cap);
+/* Development switch (not for applications): 0 makes the map form of the IF stage walk the channels in channel
+ * order instead of sorted by capture (DESIGN.md section 9.4 measures what the sort is worth); 1 (default) back. */
+int fmd_batch_debug_capture_walk(fmd_batch* b, int on);
 
 /* Moving single channels of a running batch to another station (the reference's host deletes its cFmDecoder
  * and creates a new one: RadioReceiver.cpp:296-300, 370-374).  All channels of a batch share one clock (tuner

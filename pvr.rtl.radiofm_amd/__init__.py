@@ -131,6 +131,8 @@ EXPORTS = [
     "fmd_batch_debug_host_ms", "fmd_decoder_batch",
     "fmd_batch_enable_retune", "fmd_batch_retune_channels", "fmd_batch_debug_restart_skip",
     "fmd_batch_reset_channels", "fmd_batch_debug_reset_keep_ring_phase",
+    "fmd_batch_set_capture_map", "fmd_batch_switch_captures", "fmd_batch_retune_channels_to",
+    "fmd_batch_get_capture_map", "fmd_batch_debug_capture_walk",
     "fmd_scan_create", "fmd_scan_destroy", "fmd_scan_reset", "fmd_scan_slots", "fmd_scan_accumulate_device",
     "fmd_scan_accumulate_device_u8", "fmd_scan_accumulate_host", "fmd_scan_finish_device", "fmd_scan_finish_host",
 ]
@@ -188,6 +190,11 @@ def lib():
         L.fmd_batch_export_rds_device.argtypes = [vp, vp, u, u, i, vp]
         L.fmd_batch_set_concurrency.argtypes = [vp, i]
         L.fmd_batch_set_channels_per_capture.argtypes = [vp, u]
+        L.fmd_batch_set_capture_map.argtypes = [vp, vp, u]
+        L.fmd_batch_switch_captures.argtypes = [vp, vp, vp, u]
+        L.fmd_batch_retune_channels_to.argtypes = [vp, vp, vp, vp, u]
+        L.fmd_batch_get_capture_map.argtypes = [vp, vp, u]
+        L.fmd_batch_debug_capture_walk.argtypes = [vp, i]
         L.fmd_batch_streams_sharing_queue.argtypes = [vp]
         L.fmd_batch_wait.argtypes = [vp, vp]
         L.fmd_batch_wait_lagged.argtypes = [vp, i, vp]
@@ -324,13 +331,52 @@ class Batch:
         """Opt in to retune() (fmd_batch_enable_retune): only before the first call."""
         _check(lib().fmd_batch_enable_retune(self._h))
 
-    def retune(self, channels, shifts):
+    def retune(self, channels, shifts, captures=None):
         """Move channels to new tuner shifts from the next call on (fmd_batch_retune_channels): each then decodes
-        like a decoder created with that shift that received zeros until now."""
+        like a decoder created with that shift that received zeros until now.  With `captures`, each also reads
+        that capture from the next call on (fmd_batch_retune_channels_to)."""
         ch = np.ascontiguousarray(channels, dtype=np.uint32).reshape(-1)
         sh = np.ascontiguousarray(shifts, dtype=np.int32).reshape(-1)
         assert ch.size == sh.size
-        _check(lib().fmd_batch_retune_channels(self._h, ch.ctypes.data, sh.ctypes.data, ch.size))
+        if captures is None:
+            _check(lib().fmd_batch_retune_channels(self._h, ch.ctypes.data, sh.ctypes.data, ch.size))
+            return
+        cp = np.ascontiguousarray(captures, dtype=np.uint32).reshape(-1)
+        assert cp.size == ch.size
+        _check(lib().fmd_batch_retune_channels_to(self._h, ch.ctypes.data, sh.ctypes.data, cp.ctypes.data, ch.size))
+
+    def set_capture_map(self, capture_of, n_captures):
+        """Channel c reads input row capture_of[c] of n_captures (fmd_batch_set_capture_map); None: one row per
+        channel.  The process calls then take [n_captures, N] rows."""
+        if capture_of is None:
+            _check(lib().fmd_batch_set_capture_map(self._h, None, 0))
+        else:
+            m = np.ascontiguousarray(capture_of, dtype=np.uint32).reshape(-1)
+            assert m.size == self.n_channels
+            _check(lib().fmd_batch_set_capture_map(self._h, m.ctypes.data, int(n_captures)))
+        self.channels_per_capture = 1
+
+    def switch_captures(self, channels, captures):
+        """From the next call on, channels[i] reads captures[i] with all its state carried over
+        (fmd_batch_switch_captures)."""
+        ch = np.ascontiguousarray(channels, dtype=np.uint32).reshape(-1)
+        cp = np.ascontiguousarray(captures, dtype=np.uint32).reshape(-1)
+        assert ch.size == cp.size
+        _check(lib().fmd_batch_switch_captures(self._h, ch.ctypes.data, cp.ctypes.data, ch.size))
+
+    def capture_map(self):
+        """(capture of every channel as the next call reads it, number of input rows) (fmd_batch_get_capture_map)."""
+        out = np.zeros(self.n_channels, dtype=np.uint32)
+        n = _check(lib().fmd_batch_get_capture_map(self._h, out.ctypes.data, out.size))
+        return out, n
+
+    def debug_capture_walk(self, on):
+        """Development switch: the map form's IF stage walks the channels sorted by capture (1, default) or in channel
+        order (0) (fmd_batch_debug_capture_walk)."""
+        _check(lib().fmd_batch_debug_capture_walk(self._h, int(on)))
+
+    def _input_rows(self):
+        return _check(lib().fmd_batch_get_capture_map(self._h, None, 0))
 
     def reset_channels(self, channels):
         """Reset single channels from the next call on (fmd_batch_reset_channels): each then decodes like its own
@@ -354,7 +400,8 @@ class Batch:
         return lib().fmd_batch_max_audio_floats(self._h, samples)
 
     def process_host(self, iq, shared=False):
-        """iq: [C, N] complex64 (or [N] when shared).  Returns [C, n_floats] float32 audio."""
+        """iq: [C, N] complex64 ([captures, N] with several channels per capture or a capture map; [N] when
+        shared).  Returns [C, n_floats] float32 audio."""
         iq = np.ascontiguousarray(iq)
         if iq.dtype != np.complex64:
             iq = iq.astype(np.float32).view(np.complex64)
@@ -362,7 +409,7 @@ class Batch:
             n = iq.size
             stride = 0
         else:
-            iq = iq.reshape(self.n_channels // getattr(self, "channels_per_capture", 1), -1)
+            iq = iq.reshape(self._input_rows(), -1)
             n = iq.shape[1]
             stride = n
         a_stride = self.max_audio_floats(n)
@@ -380,7 +427,7 @@ class Batch:
             n = iq_u8.size // 2
             stride = 0
         else:
-            iq_u8 = iq_u8.reshape(self.n_channels // getattr(self, "channels_per_capture", 1), -1)
+            iq_u8 = iq_u8.reshape(self._input_rows(), -1)
             n = iq_u8.shape[1] // 2
             stride = n
         a_stride = self.max_audio_floats(n)

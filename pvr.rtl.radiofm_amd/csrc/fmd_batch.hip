@@ -386,6 +386,22 @@ struct fmd_batch
   bool origins_live = false;
   int dbg_reset_keep_phase = 0;        // fmd_batch_debug_reset_keep_ring_phase (test aid): origins stay 0
 
+  /* The capture map (fmd_batch_set_capture_map / fmd_batch_switch_captures).  Every batch
+   * knows the input rows a call takes (n_cap, 0: no map, the cpc rule).  A batch with buffers of its own holds its
+   * channels' captures as its next call reads them (cmap, local channel numbers, global capture rows) and the walk
+   * table its IF stage reads: (channel, capture) per block row, the channels sorted by capture where capture_walk
+   * is on.  A changed map goes to d_walk in front of the next call's IF stage, on that stage's stream, out of a
+   * page-locked staging slot per call index mod NSLOT: the IF stages of consecutive calls run in order on that
+   * stream (each reads the IF history the previous one wrote), so calls submitted earlier read the old table. */
+  unsigned n_cap = 0;
+  bool map_on = false, map_dirty = false;
+  int capture_walk = 1;                // fmd_batch_debug_capture_walk (development switch)
+  std::vector<unsigned> cmap;          // [C]
+  DevBuf<uint2> d_walk;                // [C]
+  HostBuf<uint2> h_walk;               // [NSLOT][C]
+  Event walk_ev[NSLOT];                // behind the copy out of a staging slot
+  bool walk_ev_used[NSLOT] = {};
+
   // Everything else frees itself; the sub-batches and the twin run on this batch's streams: they go first.
   ~fmd_batch()
   {
@@ -1263,6 +1279,28 @@ unsigned fmd_batch_max_audio_floats(const fmd_batch* b, unsigned samples)
 
 } // extern "C"
 
+namespace
+{
+
+/* The walk table of a batch with buffers of its own (fmd_batch::d_walk): block row i of the IF stage decodes channel
+ * out[i].x from capture out[i].y.  capture_walk on: the channels sorted by capture, stable, so an ordered map walks
+ * like the plain form and the channels the XCDs work on at one time read few captures (an XCD's L2 holds about one
+ * capture's window, as under the cpc rule).  Off: channel order. */
+void build_walk(const fmd_batch* b, uint2* out)
+{
+  const unsigned C = b->C;
+  std::vector<unsigned> order(C);
+  for (unsigned c = 0; c < C; c++)
+    order[c] = c;
+  if (b->capture_walk)
+    std::stable_sort(order.begin(), order.end(),
+                     [&](unsigned a, unsigned z) { return b->cmap[a] < b->cmap[z]; });
+  for (unsigned i = 0; i < C; i++)
+    out[i] = make_uint2(order[i], b->cmap[order[i]]);
+}
+
+} // namespace
+
 #include "fmd_batch_if.inc.hpp"      // launch_if_stage: the IF stage's kernel forms
 #include "fmd_batch_process.inc.hpp" // process_device_impl: one call on the batch's streams
 #include "fmd_scan.inc.hpp"          // fmd_scan_*: the band scan (its own object, the caller's stream)
@@ -1513,6 +1551,76 @@ void gdec_follow_edits(fmd_batch* b, unsigned c, uint32_t ci)
   }
 }
 
+/* input rows channel numbers may name: the map's, or the cpc rule's */
+unsigned capture_rows(const fmd_batch* b)
+{
+  return b->map_on ? b->n_cap : b->C / b->cpc;
+}
+
+/* the capture channel c of the caller-facing batch b reads in its next call */
+unsigned capture_at(fmd_batch* b, unsigned c)
+{
+  if (!b->map_on)
+    return c / b->cpc;
+  unsigned lc = 0;
+  const fmd_batch* ob = owner_of(b, c, &lc);
+  return ob->cmap[lc];
+}
+
+/* a list of distinct channels of b and their captures (either list may be absent) */
+int check_channel_list(fmd_batch* b, const unsigned* channels, const unsigned* captures, unsigned n, const char* who)
+{
+  if (b->failed)
+    return fail(FMD_ERR_ARG, std::string(who) + ": the batch has failed (fmd_batch_reset clears it)");
+  std::vector<unsigned> seen(channels, channels + n);
+  std::sort(seen.begin(), seen.end());
+  if (n && seen.back() >= b->C)
+    return fail(FMD_ERR_ARG, std::string(who) + ": channel " + std::to_string(seen.back()) + " out of range");
+  if (std::adjacent_find(seen.begin(), seen.end()) != seen.end())
+    return fail(FMD_ERR_ARG, std::string(who) + ": a channel is listed twice");
+  const unsigned rows = capture_rows(b);
+  for (unsigned i = 0; captures && i < n; i++)
+    if (captures[i] >= rows)
+      return fail(FMD_ERR_ARG, std::string(who) + ": capture " + std::to_string(captures[i]) + " out of range (" +
+                                   std::to_string(rows) + " captures)");
+  return FMD_OK;
+}
+
+/* Turns the cpc rule into the same map where there is none yet (fmd_batch_switch_captures on such a batch): the walk
+ * staging of every batch with buffers of its own, its channels' rows.  Calls in flight keep the plain form. */
+int ensure_map(fmd_batch* b, const char* who)
+{
+  if (b->map_on)
+    return FMD_OK;
+  HIPCHK(hipSetDevice(b->device));
+  const std::vector<fmd_batch*> xs = buffer_batches(b);
+  for (fmd_batch* x : xs)
+  {
+    if (x->d_walk.n < x->C && x->d_walk.alloc(x->C))
+      return fail(FMD_ERR_DEVICE, std::string(who) + ": device allocation failed");
+    if (x->h_walk.n < size_t(fmd_batch::NSLOT) * x->C && x->h_walk.alloc(size_t(fmd_batch::NSLOT) * x->C))
+      return fail(FMD_ERR_DEVICE, std::string(who) + ": page-locked staging allocation failed");
+    for (Event& e : x->walk_ev)
+      if (!e.e)
+        HIPCHK(e.create());
+  }
+  const unsigned rows = b->C / b->cpc;
+  for (size_t k = 0; k < xs.size(); k++)
+  {
+    fmd_batch* x = xs[k];
+    const unsigned ch0 = is_shell(b) ? b->sub_ch0[k] : 0u;
+    x->cmap.resize(x->C);
+    for (unsigned c = 0; c < x->C; c++)
+      x->cmap[c] = (ch0 + c) / b->cpc;
+    x->map_on = true;
+    x->map_dirty = true;
+    x->n_cap = rows;
+  }
+  b->map_on = true;
+  b->n_cap = rows;
+  return FMD_OK;
+}
+
 } // namespace
 
 extern "C" {
@@ -1575,7 +1683,9 @@ static int process_shell(fmd_batch* b, const void* d_iq, IqFormat fmt, size_t iq
     fmd_batch* sb = b->subs[k].get();
     const unsigned ch0 = b->sub_ch0[k];
     sb->sched_prev2 = b->vheavy[1];
-    const char* iq = static_cast<const char*>(d_iq) + size_t(ch0 / b->cpc) * iq_channel_stride * esz;
+    // (a capture map: every sub-batch takes the first row, its walk names the rows it reads)
+    const size_t row0 = b->map_on ? 0 : ch0 / b->cpc;
+    const char* iq = static_cast<const char*>(d_iq) + row0 * iq_channel_stride * esz;
     const int rc = process_device_impl(sb, iq, fmt, iq_channel_stride, samples,
                                        d_audio + size_t(ch0) * audio_channel_stride, audio_channel_stride, &nf, stream);
     if (rc != FMD_OK)
@@ -1846,12 +1956,8 @@ int fmd_batch_retune_channels(fmd_batch* b, const unsigned* channels, const int*
     return fail(FMD_ERR_ARG, "fmd_batch_retune_channels: the batch has failed (fmd_batch_reset clears it)");
   if (!b->twin)
     return fail(FMD_ERR_STATE, "fmd_batch_retune_channels: retuning is not enabled (fmd_batch_enable_retune)");
-  std::vector<unsigned> seen(channels, channels + n);
-  std::sort(seen.begin(), seen.end());
-  if (n && seen.back() >= b->C)
-    return fail(FMD_ERR_ARG, "fmd_batch_retune_channels: channel " + std::to_string(seen.back()) + " out of range");
-  if (std::adjacent_find(seen.begin(), seen.end()) != seen.end())
-    return fail(FMD_ERR_ARG, "fmd_batch_retune_channels: a channel is listed twice");
+  if (int rc = check_channel_list(b, channels, nullptr, n, "fmd_batch_retune_channels"))
+    return rc;
   const uint32_t k = b->call_index + 1; // the call the edit takes effect at
   std::lock_guard<std::mutex> lk(b->log_mu);
   for (unsigned i = 0; i < n; i++)
@@ -1926,7 +2032,112 @@ int fmd_batch_set_channels_per_capture(fmd_batch* b, unsigned channels_per_captu
   b->cpc = k;
   for (auto& sb : b->subs)
     sb->cpc = k;
+  // the contiguous rule replaces any capture map
+  b->map_on = false;
+  b->n_cap = 0;
+  for (auto& sb : b->subs)
+  {
+    sb->map_on = false;
+    sb->n_cap = 0;
+  }
   return FMD_OK;
+}
+
+
+int fmd_batch_set_capture_map(fmd_batch* b, const unsigned* capture_of_channel, unsigned n_captures)
+{
+  if (!b)
+    return fail(FMD_ERR_ARG, "fmd_batch_set_capture_map: null batch");
+  if (capture_of_channel)
+  {
+    if (n_captures == 0)
+      return fail(FMD_ERR_ARG, "fmd_batch_set_capture_map: no captures");
+    for (unsigned c = 0; c < b->C; c++)
+      if (capture_of_channel[c] >= n_captures)
+        return fail(FMD_ERR_ARG, "fmd_batch_set_capture_map: channel " + std::to_string(c) + " reads capture " +
+                                     std::to_string(capture_of_channel[c]) + " of " + std::to_string(n_captures));
+  }
+  HIPCHK(hipSetDevice(b->device));
+  HIPCHK(hipDeviceSynchronize());
+  if (!capture_of_channel) // one row per channel, as after creation
+    return fmd_batch_set_channels_per_capture(b, 1);
+  b->cpc = 1;
+  for (auto& sb : b->subs)
+    sb->cpc = 1;
+  if (int rc = ensure_map(b, "fmd_batch_set_capture_map"))
+    return rc;
+  const std::vector<fmd_batch*> xs = buffer_batches(b);
+  for (size_t k = 0; k < xs.size(); k++)
+  {
+    fmd_batch* x = xs[k];
+    const unsigned ch0 = is_shell(b) ? b->sub_ch0[k] : 0u;
+    std::copy(capture_of_channel + ch0, capture_of_channel + ch0 + x->C, x->cmap.begin());
+    x->map_dirty = true;
+    x->n_cap = n_captures;
+  }
+  b->n_cap = n_captures;
+  return FMD_OK;
+}
+
+int fmd_batch_debug_capture_walk(fmd_batch* b, int on)
+{
+  if (!b)
+    return fail(FMD_ERR_ARG, "fmd_batch_debug_capture_walk: null batch");
+  b->capture_walk = on != 0;
+  for (fmd_batch* x : buffer_batches(b))
+  { // the next call takes the walk in the new order (calls in flight keep theirs: the copy is ordered like a switch)
+    x->capture_walk = on != 0;
+    x->map_dirty = x->map_on;
+  }
+  return FMD_OK;
+}
+
+int fmd_batch_get_capture_map(fmd_batch* b, unsigned* out, unsigned cap)
+{
+  if (!b || (cap && !out))
+    return fail(FMD_ERR_ARG, "fmd_batch_get_capture_map: null argument");
+  for (unsigned c = 0; c < std::min(cap, b->C); c++)
+    out[c] = capture_at(b, c);
+  return int(capture_rows(b));
+}
+
+int fmd_batch_switch_captures(fmd_batch* b, const unsigned* channels, const unsigned* captures, unsigned n)
+{
+  if (!b || !channels || !captures)
+    return fail(FMD_ERR_ARG, "fmd_batch_switch_captures: null argument");
+  if (int rc = check_channel_list(b, channels, captures, n, "fmd_batch_switch_captures"))
+    return rc;
+  if (n == 0)
+    return FMD_OK;
+  if (int rc = ensure_map(b, "fmd_batch_switch_captures"))
+    return rc;
+  for (unsigned i = 0; i < n; i++)
+  {
+    unsigned lc = 0;
+    fmd_batch* ob = owner_of(b, channels[i], &lc);
+    ob->cmap[lc] = captures[i];
+    ob->map_dirty = true;
+  }
+  return FMD_OK;
+}
+
+int fmd_batch_retune_channels_to(fmd_batch* b, const unsigned* channels, const int* shifts, const unsigned* captures,
+                                 unsigned n)
+{
+  if (!b || !channels || !shifts || !captures)
+    return fail(FMD_ERR_ARG, "fmd_batch_retune_channels_to: null argument");
+  if (!b->twin)
+    return fail(FMD_ERR_STATE, "fmd_batch_retune_channels_to: retuning is not enabled (fmd_batch_enable_retune)");
+  if (int rc = check_channel_list(b, channels, captures, n, "fmd_batch_retune_channels_to"))
+    return rc;
+  if (n == 0)
+    return FMD_OK;
+  if (int rc = ensure_map(b, "fmd_batch_retune_channels_to"))
+    return rc;
+  // the restart and the capture take effect at the same boundary, the next call's
+  if (int rc = fmd_batch_retune_channels(b, channels, shifts, n))
+    return rc;
+  return fmd_batch_switch_captures(b, channels, captures, n);
 }
 
 int fmd_batch_set_concurrency(fmd_batch* b, int mode)
@@ -2134,7 +2345,8 @@ static int process_host_impl(fmd_batch* b, const void* iq, IqFormat fmt, size_t 
   // device copy: one row per channel, rows padded to a whole pair of samples
   const size_t dev_row = (size_t(samples) + 1) / 2 * 2 * esz;
   const size_t dev_iq_stride = iq_channel_stride ? dev_row / esz : 0;
-  const unsigned streams = iq_channel_stride ? C / b->cpc : 1u; // input rows: one per channel, per capture, or one
+  // input rows: one per capture of the map, per channel, per cpc channels, or one
+  const unsigned streams = !iq_channel_stride ? 1u : b->map_on ? b->n_cap : C / b->cpc;
   const size_t iq_floats = (dev_row * streams + 3) / 4;
   const size_t a_stride = (size_t(fmd_batch_max_audio_floats(b, samples)) + 3) & ~size_t(3);
   if ((iq_floats > b->h_iq.n && b->h_iq.alloc(iq_floats)) ||

@@ -384,6 +384,20 @@ int process_device_impl(fmd_batch* b, const void* d_iq, IqFormat fmt, size_t iq_
     note(hipEventRecord(b->osc_ev[es], sF));
     b->osc_ev_used[es] = true;
   }
+  // a capture map that changed since the last call (switches, retunes to a capture, a new map): the walk table goes
+  // to the device on the IF stage's stream, behind every earlier call's IF stage (the level meter included) and in
+  // front of this one's.  No other wait: a call with switches overlaps the calls before it like any other call.
+  if (b->map_on && b->map_dirty)
+  {
+    if (b->walk_ev_used[es]) // the copy of 8 calls ago
+      note(hipEventSynchronize(b->walk_ev[es]));
+    uint2* h = b->h_walk.p + size_t(es) * C;
+    build_walk(b, h);
+    note(hipMemcpyAsync(b->d_walk.p, h, C * sizeof(uint2), hipMemcpyHostToDevice, sF));
+    note(hipEventRecord(b->walk_ev[es], sF));
+    b->walk_ev_used[es] = true;
+    b->map_dirty = false;
+  }
 
   /* ---- K1: tuner + IF decimating FIR  (stream F) ---- */
   /* The input is ready in the order of the caller's stream.  Where that stream has nothing pending (the usual case:

@@ -182,6 +182,16 @@ __device__ __forceinline__ unsigned capture_of(unsigned c, unsigned cpc)
   return cpc > 1u ? (unsigned)__builtin_amdgcn_readfirstlane((int)(c / cpc)) : c;
 }
 
+/* The map form of the IF stage (fmd_batch_set_capture_map): entry i of the walk is the channel of block row i and the
+ * capture it reads -- the channels sorted by capture, dealt over the XCDs like the plain form's channels.  i is
+ * wave-uniform and the table read-only: one scalar load, so the capture's base address stays in SGPRs as above. */
+__device__ __forceinline__ unsigned walk_take(const uint2* __restrict__ walk, unsigned& c)
+{
+  const uint2 w = walk[c];
+  c = w.x;
+  return w.y;
+}
+
 __device__ __forceinline__ float2 cmul(float2 a, float2 b)
 {
   // std::complex<float> product: (ac - bd) + i(ad + bc), four products and two sums, each rounded
