@@ -84,6 +84,19 @@ public:
     return n > 0 ? static_cast<unsigned int>(n) : 0u;
   }
 
+  /* Not in the reference: signed integer IQ as HackRF (8 bits) and Airspy, SDRplay, USRP sc16, .cs16 files (16
+   * bits) deliver it -- buf = 2 * samples values I, Q, I, Q, ..., full scale = [-1, 1) (v * 2^-7, v * 2^-15). */
+  unsigned int ProcessStreamS8(const int8_t* buf, unsigned int samples, float* audio)
+  {
+    const int n = fmd_process_stream_fmt(m_dec, buf, FMD_IQ_S8, samples, audio);
+    return n > 0 ? static_cast<unsigned int>(n) : 0u;
+  }
+  unsigned int ProcessStreamS16(const int16_t* buf, unsigned int samples, float* audio)
+  {
+    const int n = fmd_process_stream_fmt(m_dec, buf, FMD_IQ_S16, samples, audio);
+    return n > 0 ? static_cast<unsigned int>(n) : 0u;
+  }
+
   bool StereoDetected() const { return Status().stereo_detected != 0; }
   RealType GetTuningOffset() const { return Status().tuning_offset; }
   RealType GetInterfaceLevel() const { return Status().interface_level; }

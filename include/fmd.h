@@ -52,6 +52,27 @@ extern "C" {
  * call) must stay below 32768 - 51, the size of its half-band delay lines (DownConvert.cpp:267,
  * :500; it overruns them silently).  Only matters for downsample < 3. */
 
+/* IQ input formats: the `format` argument of the _fmt entry points.  I and Q interleaved, host byte order.
+ *   FMD_IQ_F32  float I, Q      as is                                         8 bytes per IQ sample
+ *   FMD_IQ_U8   uint8_t I, Q    float(b / (255.0 / 2.0) - 1.0) (RTL-SDR, see fmd_process_stream_u8)   2
+ *   FMD_IQ_S8   int8_t I, Q     (float)v * 2^-7   (HackRF, .cs8 files)                               2
+ *   FMD_IQ_S16  int16_t I, Q    (float)v * 2^-15  (Airspy, SDRplay, USRP sc16, .cs16 files)          4
+ * The conversion happens inside the IF kernel (and the scan's first pass).  The two signed conversions are exact
+ * in float, so a call with S8 / S16 input gives the same bits in every output as the float call on the block
+ * converted on the host; -128 and -32768 are exactly -1.0f.  The scale is fixed: a receiver that leaves 12 or 14
+ * bits right-aligned in an int16 decodes correctly and only reads 24 / 12 dB low on interface_level (a
+ * caller-chosen scale or per-batch gain is not offered).
+ * Alignment: IQ pointers and channel / capture strides are multiples of two IQ samples -- 16 bytes of F32, 4
+ * bytes of U8 and S8, 8 bytes of S16.  Strides are counted in IQ samples for every format.
+ * The format is a property of the call, not of the batch, the decoder, the receiver or the scan: all state behind
+ * the tuner is float, so consecutive calls may use different formats.
+ * A format outside 0..3 is refused with FMD_ERR_ARG before anything else is looked at.  The functions without
+ * _fmt (float input) and with _u8 remain and are calls of the _fmt ones with FMD_IQ_F32 / FMD_IQ_U8. */
+#define FMD_IQ_F32 0
+#define FMD_IQ_U8 1
+#define FMD_IQ_S8 2
+#define FMD_IQ_S16 3
+
 /* Constructor arguments of cFmDecoder (FmDecode.h:110-116).  table_size / if_filter_order are
  * the two internal constants BASELINE configs 3 and 5 override; 0 selects the reference
  * values 64 (FmDecode.cpp:249) and 8*downsample (FmDecode.cpp:262). */
@@ -135,6 +156,8 @@ int fmd_process_stream(fmd_decoder* d, const float* iq, unsigned samples, float*
  * reference's float(b / (255.0 / 2.0) - 1.0) inside the IF kernel, so the result equals
  * fmd_process_stream on the converted block; the transfer and the HBM read are 4x smaller. */
 int fmd_process_stream_u8(fmd_decoder* d, const uint8_t* buf, unsigned samples, float* audio);
+/* The same for any input format (FMD_IQ_*): iq = samples (I, Q) pairs of that format. */
+int fmd_process_stream_fmt(fmd_decoder* d, const void* iq, int format, unsigned samples, float* audio);
 int fmd_get_status(fmd_decoder* d, fmd_status* st);
 /* The one-channel batch behind a decoder: for the profiling / development calls below (fmd_batch_set_
  * profiling, fmd_batch_get_stage_ms, fmd_batch_debug_*); not for processing (the decoder owns it). */
@@ -185,6 +208,12 @@ int fmd_batch_process_device_u8(fmd_batch* b, const uint8_t* d_iq_u8, size_t iq_
                                 unsigned samples, float* d_audio, size_t audio_channel_stride,
                                 unsigned* out_floats, void* stream);
 
+/* Same for any input format (FMD_IQ_*): channel c starts iq_channel_stride IQ samples of that format behind
+ * channel c - 1.  Pointer and stride: multiples of two IQ samples (see FMD_IQ_*). */
+int fmd_batch_process_device_fmt(fmd_batch* b, const void* d_iq, int format, size_t iq_channel_stride,
+                                 unsigned samples, float* d_audio, size_t audio_channel_stride,
+                                 unsigned* out_floats, void* stream);
+
 /* Host-buffer call: copies in, runs fmd_batch_process_device, copies audio out, collects RDS
  * groups and runs the UECP group decoder (callbacks fire here).  Synchronous.  Returns FMD_OK, a
  * negative error, or FMD_WARN_RDS_LOST (once) when groups were dropped because a queue was full:
@@ -195,6 +224,9 @@ int fmd_batch_process_host(fmd_batch* b, const float* iq, size_t iq_channel_stri
 int fmd_batch_process_host_u8(fmd_batch* b, const uint8_t* iq_u8, size_t iq_channel_stride,
                               unsigned samples, float* audio, size_t audio_channel_stride,
                               unsigned* out_floats);
+int fmd_batch_process_host_fmt(fmd_batch* b, const void* iq, int format, size_t iq_channel_stride,
+                               unsigned samples, float* audio, size_t audio_channel_stride,
+                               unsigned* out_floats);
 
 /* Copies the queued RDS groups (all channels, call order) to `out`, waits for `stream`.
  * Returns the number of groups (<= cap) or a negative error.  When run_group_decoder != 0
@@ -502,6 +534,8 @@ void fmd_receiver_close(fmd_receiver* r);
  * converted inside the IF kernel when the block is decoded. */
 int fmd_receiver_write_iq(fmd_receiver* r, const float* iq, unsigned samples);
 int fmd_receiver_write_u8(fmd_receiver* r, const uint8_t* buf, unsigned samples);
+/* Any input format (FMD_IQ_*): a queued block carries its format and is decoded with it. */
+int fmd_receiver_write_fmt(fmd_receiver* r, const void* buf, int format, unsigned samples);
 void fmd_receiver_end(fmd_receiver* r);                 /* EndDataBuffer (:438-443)        */
 size_t fmd_receiver_queued_samples(fmd_receiver* r);    /* SourceQueuedSamples (:420-424)  */
 void fmd_receiver_set_stream_change(fmd_receiver* r);   /* SetStreamChange (RadioReceiver.h:83) */
@@ -580,6 +614,12 @@ int fmd_scan_accumulate_device(fmd_scan* s, const float* d_iq, size_t iq_capture
 int fmd_scan_accumulate_device_u8(fmd_scan* s, const uint8_t* d_iq_u8, size_t iq_capture_stride, unsigned samples,
                                   void* stream);
 int fmd_scan_accumulate_host(fmd_scan* s, const float* iq, size_t iq_capture_stride, unsigned samples);
+/* Any input format (FMD_IQ_*), strides in IQ samples.  Signed integer IQ is converted exactly, so its scan has the
+ * bits of the float scan of the converted captures (and the determinism statement above holds for it). */
+int fmd_scan_accumulate_device_fmt(fmd_scan* s, const void* d_iq, int format, size_t iq_capture_stride,
+                                   unsigned samples, void* stream);
+int fmd_scan_accumulate_host_fmt(fmd_scan* s, const void* iq, int format, size_t iq_capture_stride,
+                                 unsigned samples);
 /* Outputs (each optional, NULL = not written): psd [G][N], slot_db [G][T] (-inf for an ineligible slot), floor_db
  * [G] (the floor bin), cand [G][max_cand], counts [G] (the true candidate count, also when max_cand clips the
  * list).  Does not reset: accumulation may go on. */

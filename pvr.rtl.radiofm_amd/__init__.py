@@ -20,6 +20,9 @@ _LIB = None
 FMD_MAX_BLOCK = 65536
 FMD_MIN_BLOCK = 8192
 FMD_WARN_RDS_LOST = 1
+# IQ input formats (include/fmd.h FMD_IQ_*): the `format` argument of the _fmt entry points
+FMD_IQ_F32, FMD_IQ_U8, FMD_IQ_S8, FMD_IQ_S16 = 0, 1, 2, 3
+IQ_BYTES = {FMD_IQ_F32: 8, FMD_IQ_U8: 2, FMD_IQ_S8: 2, FMD_IQ_S16: 4}  # per IQ sample
 
 TAPS = {"demod": 0, "baseband": 1, "pilot38": 2, "mono_rs": 3, "stereo_rs": 4, "rds_lpf": 5,
         "rds_pll": 6, "rds_mf": 7, "rds_sync": 8}
@@ -135,6 +138,8 @@ EXPORTS = [
     "fmd_batch_get_capture_map", "fmd_batch_debug_capture_walk",
     "fmd_scan_create", "fmd_scan_destroy", "fmd_scan_reset", "fmd_scan_slots", "fmd_scan_accumulate_device",
     "fmd_scan_accumulate_device_u8", "fmd_scan_accumulate_host", "fmd_scan_finish_device", "fmd_scan_finish_host",
+    "fmd_batch_process_device_fmt", "fmd_batch_process_host_fmt", "fmd_process_stream_fmt", "fmd_receiver_write_fmt",
+    "fmd_scan_accumulate_device_fmt", "fmd_scan_accumulate_host_fmt",
 ]
 
 
@@ -250,6 +255,12 @@ def lib():
         L.fmd_scan_accumulate_host.argtypes = [vp, vp, C.c_size_t, u]
         L.fmd_scan_finish_device.argtypes = [vp, vp, vp, vp, vp, u, vp, vp]
         L.fmd_scan_finish_host.argtypes = [vp, vp, vp, vp, vp, u, vp]
+        L.fmd_batch_process_device_fmt.argtypes = [vp, vp, i, C.c_size_t, u, vp, C.c_size_t, C.POINTER(u), vp]
+        L.fmd_batch_process_host_fmt.argtypes = [vp, vp, i, C.c_size_t, u, vp, C.c_size_t, C.POINTER(u)]
+        L.fmd_process_stream_fmt.argtypes = [vp, vp, i, u, vp]
+        L.fmd_receiver_write_fmt.argtypes = [vp, vp, i, u]
+        L.fmd_scan_accumulate_device_fmt.argtypes = [vp, vp, i, C.c_size_t, u, vp]
+        L.fmd_scan_accumulate_host_fmt.argtypes = [vp, vp, i, C.c_size_t, u]
         _LIB = L
     return _LIB
 
@@ -265,6 +276,21 @@ def _check(rc):
 
 
 FMD_ERR_ARG_TEXT = "fmd error -1: %s"  # an argument the Python layer refuses itself, worded like _check's
+
+
+def iq_format_of(arr):
+    """(contiguous array, FMD_IQ_* format, array elements per IQ sample) by the array's dtype: complex64 (1 element
+    per sample) or float32 / uint8 / int8 / int16 holding I, Q, I, Q, ... (2).  Any other dtype raises: nothing is
+    converted silently."""
+    a = np.ascontiguousarray(arr)
+    if a.dtype == np.complex64:
+        return a, FMD_IQ_F32, 1
+    fmt = {np.dtype(np.float32): FMD_IQ_F32, np.dtype(np.uint8): FMD_IQ_U8, np.dtype(np.int8): FMD_IQ_S8,
+           np.dtype(np.int16): FMD_IQ_S16}.get(a.dtype)
+    if fmt is None:
+        raise FmdError(FMD_ERR_ARG_TEXT % ("no IQ format for dtype %s (complex64, float32, uint8, int8, int16)"
+                                           % a.dtype))
+    return a, fmt, 2
 
 
 FIR_SEQUENTIAL = 0
@@ -437,10 +463,34 @@ class Batch:
                                                audio.ctypes.data, a_stride, C.byref(nf)))
         return audio[:, :nf.value]
 
-    def process_device(self, d_iq_ptr, iq_stride, samples, d_audio_ptr, audio_stride, stream=None,
-                       u8=False):
-        """iq_stride in IQ samples; u8=True: d_iq_ptr holds RTL-SDR byte pairs."""
+    def process_host_fmt(self, iq, shared=False):
+        """iq: [C, N] complex64, or [C, 2N] float32 / uint8 / int8 / int16 holding I, Q, I, Q, ... (rows as for
+        process_host; one row when shared); the input format is the array's dtype (fmd_batch_process_host_fmt).
+        Signed integers are v * 2^-7 / v * 2^-15: the same bits as process_host on the converted block."""
+        iq, fmt, per = iq_format_of(iq)
+        if shared:
+            n = iq.size // per
+            stride = 0
+        else:
+            iq = iq.reshape(self._input_rows(), -1)
+            n = iq.shape[1] // per
+            stride = n
+        a_stride = self.max_audio_floats(n)
+        audio = np.zeros((self.n_channels, a_stride), dtype=np.float32)
         nf = C.c_uint()
+        _check(lib().fmd_batch_process_host_fmt(self._h, iq.ctypes.data, fmt, stride, n, audio.ctypes.data,
+                                                a_stride, C.byref(nf)))
+        return audio[:, :nf.value]
+
+    def process_device(self, d_iq_ptr, iq_stride, samples, d_audio_ptr, audio_stride, stream=None,
+                       u8=False, fmt=None):
+        """iq_stride in IQ samples; u8=True: d_iq_ptr holds RTL-SDR byte pairs; fmt (FMD_IQ_*): the input format,
+        through fmd_batch_process_device_fmt."""
+        nf = C.c_uint()
+        if fmt is not None:
+            _check(lib().fmd_batch_process_device_fmt(self._h, d_iq_ptr, int(fmt), iq_stride, samples, d_audio_ptr,
+                                                      audio_stride, C.byref(nf), stream))
+            return nf.value
         fn = lib().fmd_batch_process_device_u8 if u8 else lib().fmd_batch_process_device
         _check(fn(self._h, d_iq_ptr, iq_stride, samples, d_audio_ptr, audio_stride, C.byref(nf),
                   stream))
@@ -631,6 +681,21 @@ class FmDecoder:
         n = _check(lib().fmd_process_stream_u8(self._h, buf.ctypes.data, n_iq, audio.ctypes.data))
         return audio[:n]
 
+    def _process_stream_fmt(self, buf, dtype, fmt):
+        buf = np.ascontiguousarray(buf, dtype=dtype)
+        n_iq = buf.size // 2
+        audio = np.empty(2 * n_iq, dtype=np.float32)
+        n = _check(lib().fmd_process_stream_fmt(self._h, buf.ctypes.data, fmt, n_iq, audio.ctypes.data))
+        return audio[:n]
+
+    def ProcessStreamS8(self, buf):
+        """buf = I,Q int8 pairs, v * 2^-7 (HackRF, .cs8): the bits of ProcessStream on the converted block."""
+        return self._process_stream_fmt(buf, np.int8, FMD_IQ_S8)
+
+    def ProcessStreamS16(self, buf):
+        """buf = I,Q int16 pairs, v * 2^-15 (Airspy, SDRplay, USRP sc16, .cs16)."""
+        return self._process_stream_fmt(buf, np.int16, FMD_IQ_S16)
+
     def _status(self):
         st = FmdStatus()
         _check(lib().fmd_get_status(self._h, C.byref(st)))
@@ -715,6 +780,12 @@ class Receiver:
     def write_u8(self, buf):
         buf = np.ascontiguousarray(buf, dtype=np.uint8)
         _check(lib().fmd_receiver_write_u8(self._h, buf.ctypes.data, buf.size // 2))
+
+    def write(self, buf):
+        """One block in the format of its dtype (complex64, or float32 / uint8 / int8 / int16 I, Q pairs): a queued
+        block carries its format (fmd_receiver_write_fmt)."""
+        buf, fmt, per = iq_format_of(buf)
+        _check(lib().fmd_receiver_write_fmt(self._h, buf.ctypes.data, fmt, buf.size // per))
 
     def end(self):
         lib().fmd_receiver_end(self._h)

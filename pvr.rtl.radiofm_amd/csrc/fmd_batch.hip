@@ -1676,7 +1676,7 @@ static int process_shell(fmd_batch* b, const void* d_iq, IqFormat fmt, size_t iq
     return fail(FMD_ERR_ARG, "fmd_batch_process_device: null argument");
   if (int rc = check_device_errors(b))
     return rc;
-  const size_t esz = fmt == IQ_U8 ? 2 : 8; // bytes per IQ sample
+  const size_t esz = iq_esz(fmt); // bytes per IQ sample
   unsigned nf = 0;
   for (size_t k = 0; k < b->subs.size(); k++)
   {
@@ -1712,19 +1712,30 @@ static int process_shell(fmd_batch* b, const void* d_iq, IqFormat fmt, size_t iq
   return FMD_OK;
 }
 
+int fmd_batch_process_device_fmt(fmd_batch* b, const void* d_iq, int format, size_t iq_channel_stride,
+                                 unsigned samples, float* d_audio, size_t audio_channel_stride,
+                                 unsigned* out_floats, void* stream)
+{
+  if (!iq_format_ok(format))
+    return fail(FMD_ERR_ARG, "fmd_batch_process_device_fmt: format must be one of FMD_IQ_F32, _U8, _S8, _S16 (0..3)");
+  return process_any(b, d_iq, IqFormat(format), iq_channel_stride, samples, d_audio, audio_channel_stride, out_floats,
+                     stream);
+}
+
 int fmd_batch_process_device(fmd_batch* b, const float* d_iq, size_t iq_channel_stride,
                              unsigned samples, float* d_audio, size_t audio_channel_stride,
                              unsigned* out_floats, void* stream)
 {
-  return process_any(b, d_iq, IQ_F32, iq_channel_stride, samples, d_audio, audio_channel_stride, out_floats, stream);
+  return fmd_batch_process_device_fmt(b, d_iq, FMD_IQ_F32, iq_channel_stride, samples, d_audio, audio_channel_stride,
+                                      out_floats, stream);
 }
 
 int fmd_batch_process_device_u8(fmd_batch* b, const uint8_t* d_iq_u8, size_t iq_channel_stride,
                                 unsigned samples, float* d_audio, size_t audio_channel_stride,
                                 unsigned* out_floats, void* stream)
 {
-  return process_any(b, d_iq_u8, IQ_U8, iq_channel_stride, samples, d_audio, audio_channel_stride, out_floats,
-                     stream);
+  return fmd_batch_process_device_fmt(b, d_iq_u8, FMD_IQ_U8, iq_channel_stride, samples, d_audio,
+                                      audio_channel_stride, out_floats, stream);
 }
 
 /* slots whose call is at least `lag` calls old (lag 0 = every call submitted so far) */
@@ -2341,7 +2352,7 @@ static int process_host_impl(fmd_batch* b, const void* iq, IqFormat fmt, size_t 
     return fail(FMD_ERR_ARG, "fmd_batch_process_host: null argument");
   HIPCHK(hipSetDevice(b->device));
   const unsigned C = b->C;
-  const size_t esz = fmt == IQ_U8 ? 2 : 8; // bytes per IQ sample
+  const size_t esz = iq_esz(fmt); // bytes per IQ sample
   // device copy: one row per channel, rows padded to a whole pair of samples
   const size_t dev_row = (size_t(samples) + 1) / 2 * 2 * esz;
   const size_t dev_iq_stride = iq_channel_stride ? dev_row / esz : 0;
@@ -2389,19 +2400,28 @@ static int process_host_impl(fmd_batch* b, const void* iq, IqFormat fmt, size_t 
   return take_lost_groups(b); // FMD_OK, or FMD_WARN_RDS_LOST once: audio and state are intact
 }
 
+int fmd_batch_process_host_fmt(fmd_batch* b, const void* iq, int format, size_t iq_channel_stride, unsigned samples,
+                               float* audio, size_t audio_channel_stride, unsigned* out_floats)
+{
+  if (!iq_format_ok(format))
+    return fail(FMD_ERR_ARG, "fmd_batch_process_host_fmt: format must be one of FMD_IQ_F32, _U8, _S8, _S16 (0..3)");
+  return process_host_impl(b, iq, IqFormat(format), iq_channel_stride, samples, audio, audio_channel_stride,
+                           out_floats);
+}
+
 int fmd_batch_process_host(fmd_batch* b, const float* iq, size_t iq_channel_stride, unsigned samples,
                            float* audio, size_t audio_channel_stride, unsigned* out_floats)
 {
-  return process_host_impl(b, iq, IQ_F32, iq_channel_stride, samples, audio, audio_channel_stride,
-                           out_floats);
+  return fmd_batch_process_host_fmt(b, iq, FMD_IQ_F32, iq_channel_stride, samples, audio, audio_channel_stride,
+                                    out_floats);
 }
 
 int fmd_batch_process_host_u8(fmd_batch* b, const uint8_t* iq_u8, size_t iq_channel_stride,
                               unsigned samples, float* audio, size_t audio_channel_stride,
                               unsigned* out_floats)
 {
-  return process_host_impl(b, iq_u8, IQ_U8, iq_channel_stride, samples, audio, audio_channel_stride,
-                           out_floats);
+  return fmd_batch_process_host_fmt(b, iq_u8, FMD_IQ_U8, iq_channel_stride, samples, audio, audio_channel_stride,
+                                    out_floats);
 }
 
 /* The getters read the status snapshot the last kernel of every call leaves in host memory: no HIP
@@ -2694,22 +2714,25 @@ int fmd_reset(fmd_decoder* d)
   return d ? fmd_batch_reset(d->b) : fail(FMD_ERR_ARG, "null decoder");
 }
 
-int fmd_process_stream(fmd_decoder* d, const float* iq, unsigned samples, float* audio)
+int fmd_process_stream_fmt(fmd_decoder* d, const void* iq, int format, unsigned samples, float* audio)
 {
+  if (!iq_format_ok(format))
+    return fail(FMD_ERR_ARG, "fmd_process_stream_fmt: format must be one of FMD_IQ_F32, _U8, _S8, _S16 (0..3)");
   if (!d)
     return fail(FMD_ERR_ARG, "null decoder");
   unsigned nf = 0;
-  int rc = fmd_batch_process_host(d->b, iq, 0, samples, audio, 0, &nf);
+  int rc = fmd_batch_process_host_fmt(d->b, iq, format, 0, samples, audio, 0, &nf);
   return rc < 0 ? rc : int(nf); // (a groups-lost warning does not touch the audio: fmd_last_error has it)
+}
+
+int fmd_process_stream(fmd_decoder* d, const float* iq, unsigned samples, float* audio)
+{
+  return fmd_process_stream_fmt(d, iq, FMD_IQ_F32, samples, audio);
 }
 
 int fmd_process_stream_u8(fmd_decoder* d, const uint8_t* buf, unsigned samples, float* audio)
 {
-  if (!d)
-    return fail(FMD_ERR_ARG, "null decoder");
-  unsigned nf = 0;
-  int rc = fmd_batch_process_host_u8(d->b, buf, 0, samples, audio, 0, &nf);
-  return rc < 0 ? rc : int(nf); // (a groups-lost warning does not touch the audio: fmd_last_error has it)
+  return fmd_process_stream_fmt(d, buf, FMD_IQ_U8, samples, audio);
 }
 
 fmd_batch* fmd_decoder_batch(fmd_decoder* d)
@@ -2870,11 +2893,22 @@ void fmd_receiver_close(fmd_receiver* r)
   delete r;
 }
 
+int fmd_receiver_write_fmt(fmd_receiver* r, const void* buf, int format, unsigned samples)
+{
+  if (!iq_format_ok(format))
+    return fail(FMD_ERR_ARG, "fmd_receiver_write_fmt: format must be one of FMD_IQ_F32, _U8, _S8, _S16 (0..3)");
+  if (!r || (!buf && samples))
+    return fail(FMD_ERR_ARG, "fmd_receiver_write_fmt: null argument");
+  if (!r->r.Write(buf, samples, format))
+    return fail(FMD_ERR_DEVICE, "fmd_receiver_write_fmt: no page-locked memory for the block");
+  return FMD_OK;
+}
+
 int fmd_receiver_write_iq(fmd_receiver* r, const float* iq, unsigned samples)
 {
   if (!r || (!iq && samples))
     return fail(FMD_ERR_ARG, "fmd_receiver_write_iq: null argument");
-  if (!r->r.Write(iq, samples, false))
+  if (!r->r.Write(iq, samples, FMD_IQ_F32))
     return fail(FMD_ERR_DEVICE, "fmd_receiver_write_iq: no page-locked memory for the block");
   return FMD_OK;
 }
@@ -2883,7 +2917,7 @@ int fmd_receiver_write_u8(fmd_receiver* r, const uint8_t* buf, unsigned samples)
 {
   if (!r || (!buf && samples))
     return fail(FMD_ERR_ARG, "fmd_receiver_write_u8: null argument");
-  if (!r->r.Write(buf, samples, true))
+  if (!r->r.Write(buf, samples, FMD_IQ_U8))
     return fail(FMD_ERR_DEVICE, "fmd_receiver_write_u8: no page-locked memory for the block");
   return FMD_OK;
 }

@@ -175,8 +175,42 @@ void launch_light_audio(fmd_batch* b, const fmd_batch::LightJob& j, hipStream_t 
 enum IqFormat
 {
   IQ_F32 = 0, // complex<float>, the ProcessStream argument (FmDecode.h:135)
-  IQ_U8 = 1   // RTL-SDR byte pairs, converted like ReadAsyncCB (RTL_SDR_Source.cpp:207-211)
+  IQ_U8 = 1,  // RTL-SDR byte pairs, converted like ReadAsyncCB (RTL_SDR_Source.cpp:207-211)
+  IQ_S8 = 2,  // signed 8-bit pairs, v * 2^-7 (fmd_s8_to_f32)
+  IQ_S16 = 3  // signed 16-bit pairs in host byte order, v * 2^-15 (fmd_s16_to_f32)
 };
+static_assert(IQ_F32 == FMD_IQ_F32 && IQ_U8 == FMD_IQ_U8 && IQ_S8 == FMD_IQ_S8 && IQ_S16 == FMD_IQ_S16,
+              "the plan's formats are the C ABI's");
+
+/* bytes per IQ sample */
+inline size_t iq_esz(IqFormat fmt)
+{
+  return fmt == IQ_F32 ? 8 : fmt == IQ_S16 ? 4 : 2;
+}
+
+/* the `format` argument of the _fmt entry points: 0..3, checked before anything else is touched */
+inline bool iq_format_ok(int format)
+{
+  return format >= FMD_IQ_F32 && format <= FMD_IQ_S16;
+}
+
+/* launch_if_stage<IN> of the call's format */
+inline int launch_if_stage_fmt(IqFormat fmt, fmd_batch* b, const void* d_iq, size_t iq_channel_stride, unsigned N,
+                               unsigned pos, unsigned M, int q, hipStream_t sF, const std::function<void(int)>& mark,
+                               hipEvent_t ev_start, hipEvent_t ev_stop)
+{
+  switch (fmt)
+  {
+  case IQ_U8:
+    return launch_if_stage<fmd::InU8>(b, d_iq, iq_channel_stride, N, pos, M, q, sF, mark, ev_start, ev_stop);
+  case IQ_S8:
+    return launch_if_stage<fmd::InS8>(b, d_iq, iq_channel_stride, N, pos, M, q, sF, mark, ev_start, ev_stop);
+  case IQ_S16:
+    return launch_if_stage<fmd::InS16>(b, d_iq, iq_channel_stride, N, pos, M, q, sF, mark, ev_start, ev_stop);
+  default:
+    return launch_if_stage<fmd::InF32>(b, d_iq, iq_channel_stride, N, pos, M, q, sF, mark, ev_start, ev_stop);
+  }
+}
 
 int process_device_impl(fmd_batch* b, const void* d_iq, IqFormat fmt, size_t iq_channel_stride,
                         unsigned samples, float* d_audio, size_t audio_channel_stride,
@@ -189,7 +223,7 @@ int process_device_impl(fmd_batch* b, const void* d_iq, IqFormat fmt, size_t iq_
                                   std::to_string(b->min_samples) + ", 65536]");
   // a lane loads two IQ samples at a time: every channel's stream has to start on a pair boundary
   {
-    const size_t pair = fmt == IQ_U8 ? 4 : 16;
+    const size_t pair = 2 * iq_esz(fmt);
     if ((reinterpret_cast<uintptr_t>(d_iq) % pair) || ((iq_channel_stride * (pair / 2)) % pair))
       return fail(FMD_ERR_ARG, "IQ pointer and channel stride must be multiples of two IQ samples");
   }
@@ -440,11 +474,8 @@ int process_device_impl(fmd_batch* b, const void* d_iq, IqFormat fmt, size_t iq_
     if (!(stage_mask & 1u))
       markfn(1); // (energy experiment: this call leaves the IF stage out -- see "stage_mask")
     else
-      rc = fmt == IQ_U8
-                       ? launch_if_stage<fmd::InU8>(b, d_iq, iq_channel_stride, N, pos, M, q, sF, markfn,
-                                                   evset ? evset[0].e : nullptr, evset ? evset[1].e : nullptr)
-                       : launch_if_stage<fmd::InF32>(b, d_iq, iq_channel_stride, N, pos, M, q, sF, markfn,
-                                                    evset ? evset[0].e : nullptr, evset ? evset[1].e : nullptr);
+      rc = launch_if_stage_fmt(fmt, b, d_iq, iq_channel_stride, N, pos, M, q, sF, markfn,
+                               evset ? evset[0].e : nullptr, evset ? evset[1].e : nullptr);
     if (rc != FMD_OK) // cannot happen: the geometry was checked when the batch was created
     {
       mark_failed(b, "the IF stage refused a call after events were recorded");

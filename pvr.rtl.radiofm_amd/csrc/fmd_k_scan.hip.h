@@ -24,7 +24,7 @@
 #pragma once
 
 #include "fmd_k_common.hip.h"
-#include "fmd_k_if.hip.h" // InF32 / InU8: the decoder's input formats (byte IQ converted by fmd_u8_to_f32)
+#include "fmd_k_if.hip.h" // InF32 / InU8 / InS8 / InS16: the decoder's input formats (fmd_u8_to_f32, fmd_s8_to_f32, ...)
 
 namespace fmd
 {

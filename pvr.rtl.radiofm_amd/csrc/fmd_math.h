@@ -25,6 +25,7 @@
  *    is the correctly rounded float of 2b/255 - 1.  Computed as b*c_hi - 1 (exact: c_hi has 9
  *    significant bits) plus b*c_lo with one rounding, c_hi + c_lo = 2/255 to 2^-48; all 256
  *    inputs are checked in the CPU tests.
+ *  - fmd_s8_to_f32() / fmd_s16_to_f32(): signed integer IQ, v * 2^-7 and v * 2^-15 (exact).
  *
  * Usable from host C (CPU sweep of the restatement) and from HIP device code.
  */
@@ -120,6 +121,17 @@ FMD_HD float fmd_u8_to_f32(unsigned b)
   const float f = (float)b;
   const float s = __builtin_fmaf(f, 0x1.01p-7f, -1.0f); /* exact */
   return __builtin_fmaf(f, 0x1.010102p-23f, s);
+}
+
+/* Signed integer IQ (HackRF: 8 bits; Airspy, SDRplay, USRP sc16, .cs16 files: 16 bits): full scale is
+ * [-1, 1), -128 and -32768 give -1.0f.  An integer of at most 16 bits times a power of two: exact. */
+FMD_HD float fmd_s8_to_f32(int v)
+{
+  return (float)v * 0x1p-7f;
+}
+FMD_HD float fmd_s16_to_f32(int v)
+{
+  return (float)v * 0x1p-15f;
 }
 
 FMD_HD float fmd_atanf(float x)

@@ -73,7 +73,7 @@ struct IqBlock
   bool pinned = false;
   size_t capacity = 0;  // bytes
   unsigned samples = 0;
-  bool bytes_in = false; // RTL-SDR (I, Q) byte pairs instead of complex<float>
+  int format = FMD_IQ_F32; // how the source delivered it (FMD_IQ_*): every block is decoded with its own
   IqBlock* next = nullptr;
 };
 
@@ -108,14 +108,14 @@ public:
 
   /* copies `bytes` bytes into a recycled (or new) pinned block and appends it; false = out of
    * memory */
-  bool push(const void* data, size_t bytes, unsigned samples, bool bytes_in)
+  bool push(const void* data, size_t bytes, unsigned samples, int format)
   {
     IqBlock* blk = take_free(bytes);
     if (!blk)
       return false;
     std::memcpy(blk->mem, data, bytes);
     blk->samples = samples;
-    blk->bytes_in = bytes_in;
+    blk->format = format;
     blk->next = nullptr;
     {
       std::lock_guard<std::mutex> g(m_lock);
@@ -323,11 +323,12 @@ public:
   }
 
   /* source side */
-  bool Write(const void* data, unsigned samples, bool bytes_in)
+  bool Write(const void* data, unsigned samples, int format)
   {
     if (!samples)
       return true; // empty deliveries are ignored (RadioReceiver.cpp:428)
-    return m_blocks.push(data, size_t(samples) * (bytes_in ? 2 : 8), samples, bytes_in);
+    const size_t esz = format == FMD_IQ_F32 ? 8 : format == FMD_IQ_S16 ? 4 : 2; // bytes per IQ sample
+    return m_blocks.push(data, size_t(samples) * esz, samples, format);
   }
   void End() { m_blocks.close(); }
   size_t QueuedSamples() { return m_blocks.backlog(); }
@@ -363,9 +364,7 @@ public:
     int floats;
     {
       std::lock_guard<std::mutex> g(m_status_lock); // status read-outs see whole calls only
-      floats = blk->bytes_in
-                   ? fmd_process_stream_u8(m_decoder, static_cast<const uint8_t*>(blk->mem), blk->samples, pcm)
-                   : fmd_process_stream(m_decoder, static_cast<const float*>(blk->mem), blk->samples, pcm);
+      floats = fmd_process_stream_fmt(m_decoder, blk->mem, blk->format, blk->samples, pcm);
     }
     m_blocks.recycle(blk);
     if (floats < 0)

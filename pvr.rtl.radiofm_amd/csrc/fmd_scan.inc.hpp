@@ -56,11 +56,11 @@ void scan_launch_n(fmd_scan* s, const void* d_iq, size_t stride, unsigned S, uns
   }
 }
 
-int scan_accumulate(fmd_scan* s, const void* d_iq, bool u8, size_t stride, unsigned samples, void* stream_)
+int scan_accumulate(fmd_scan* s, const void* d_iq, IqFormat fmt, size_t stride, unsigned samples, void* stream_)
 {
   if (!s || !d_iq)
     return fail(FMD_ERR_ARG, "fmd_scan_accumulate: null scan or IQ pointer");
-  const size_t pair = u8 ? 4 : 16;
+  const size_t pair = 2 * iq_esz(fmt);
   if (reinterpret_cast<uintptr_t>(d_iq) % pair || (s->G > 1 && stride % 2))
     return fail(FMD_ERR_ARG, "fmd_scan_accumulate: IQ pointer and capture stride must be multiples of two IQ samples");
   if (s->G > 1 && stride < samples)
@@ -77,11 +77,17 @@ int scan_accumulate(fmd_scan* s, const void* d_iq, bool u8, size_t stride, unsig
     HIPCHK(hipStreamSynchronize(stream)); // the old buffer may still be read by work queued on this stream
     if (s->d_scratch.alloc(scratch))
       return fail(FMD_ERR_DEVICE, "fmd_scan: device allocation failed");
+    // alloc() zero-fills on the null stream, which a non-blocking caller's stream is not ordered behind: without
+    // this the fill could land on partials the kernels below have already written
+    HIPCHK(hipStreamSynchronize(nullptr));
   }
-  if (u8)
-    scan_launch_n<fmd::InU8>(s, d_iq, stride, S, n_chunks, stream);
-  else
-    scan_launch_n<fmd::InF32>(s, d_iq, stride, S, n_chunks, stream);
+  switch (fmt)
+  {
+  case IQ_U8: scan_launch_n<fmd::InU8>(s, d_iq, stride, S, n_chunks, stream); break;
+  case IQ_S8: scan_launch_n<fmd::InS8>(s, d_iq, stride, S, n_chunks, stream); break;
+  case IQ_S16: scan_launch_n<fmd::InS16>(s, d_iq, stride, S, n_chunks, stream); break;
+  default: scan_launch_n<fmd::InF32>(s, d_iq, stride, S, n_chunks, stream); break;
+  }
   HIPCHK(hipGetLastError());
   s->segments += S;
   return FMD_OK;
@@ -241,20 +247,36 @@ int fmd_scan_slots(const fmd_scan* s, int32_t* first_shift)
   return int(s->T);
 }
 
+int fmd_scan_accumulate_device_fmt(fmd_scan* s, const void* d_iq, int format, size_t iq_capture_stride,
+                                   unsigned samples, void* stream)
+{
+  if (!iq_format_ok(format))
+    return fail(FMD_ERR_ARG, "fmd_scan_accumulate_device_fmt: format must be one of FMD_IQ_F32, _U8, _S8, _S16 (0..3)");
+  return scan_accumulate(s, d_iq, IqFormat(format), iq_capture_stride, samples, stream);
+}
+
 int fmd_scan_accumulate_device(fmd_scan* s, const float* d_iq, size_t iq_capture_stride, unsigned samples,
                                void* stream)
 {
-  return scan_accumulate(s, d_iq, false, iq_capture_stride, samples, stream);
+  return fmd_scan_accumulate_device_fmt(s, d_iq, FMD_IQ_F32, iq_capture_stride, samples, stream);
 }
 
 int fmd_scan_accumulate_device_u8(fmd_scan* s, const uint8_t* d_iq_u8, size_t iq_capture_stride, unsigned samples,
                                   void* stream)
 {
-  return scan_accumulate(s, d_iq_u8, true, iq_capture_stride, samples, stream);
+  return fmd_scan_accumulate_device_fmt(s, d_iq_u8, FMD_IQ_U8, iq_capture_stride, samples, stream);
 }
 
 int fmd_scan_accumulate_host(fmd_scan* s, const float* iq, size_t iq_capture_stride, unsigned samples)
 {
+  return fmd_scan_accumulate_host_fmt(s, iq, FMD_IQ_F32, iq_capture_stride, samples);
+}
+
+int fmd_scan_accumulate_host_fmt(fmd_scan* s, const void* iq, int format, size_t iq_capture_stride, unsigned samples)
+{
+  if (!iq_format_ok(format))
+    return fail(FMD_ERR_ARG, "fmd_scan_accumulate_host_fmt: format must be one of FMD_IQ_F32, _U8, _S8, _S16 (0..3)");
+  const IqFormat fmt = IqFormat(format);
   if (!s || !iq)
     return fail(FMD_ERR_ARG, "fmd_scan_accumulate_host: null scan or IQ pointer");
   if (s->G > 1 && iq_capture_stride < samples)
@@ -265,7 +287,7 @@ int fmd_scan_accumulate_host(fmd_scan* s, const float* iq, size_t iq_capture_str
     return fail(FMD_ERR_SIZE, "fmd_scan_accumulate_host: fewer samples than one segment (nfft)");
   HIPCHK(hipSetDevice(s->device));
   const size_t stride = s->G > 1 ? iq_capture_stride : 0;
-  const size_t bytes = (size_t(s->G - 1) * stride + samples) * 2 * sizeof(float);
+  const size_t bytes = (size_t(s->G - 1) * stride + samples) * iq_esz(fmt);
   if (bytes > s->d_stage.n)
   {
     HIPCHK(hipStreamSynchronize(nullptr)); // the old buffer may still be read by work queued on this stream
@@ -273,7 +295,7 @@ int fmd_scan_accumulate_host(fmd_scan* s, const float* iq, size_t iq_capture_str
       return fail(FMD_ERR_DEVICE, "fmd_scan: device allocation failed");
   }
   HIPCHK(hipMemcpy(s->d_stage.p, iq, bytes, hipMemcpyHostToDevice));
-  if (int rc = scan_accumulate(s, reinterpret_cast<const float*>(s->d_stage.p), false, stride, samples, nullptr))
+  if (int rc = scan_accumulate(s, s->d_stage.p, fmt, stride, samples, nullptr))
     return rc;
   HIPCHK(hipStreamSynchronize(nullptr));
   return FMD_OK;

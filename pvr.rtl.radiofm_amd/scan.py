@@ -10,8 +10,10 @@ import ctypes as C
 
 import numpy as np
 
-from . import (FMD_ERR_ARG_TEXT, SCAN_CANDIDATE_DTYPE, Batch, FmdError, FmdScanParams, _check, lib,
-               make_params)
+from . import (FMD_ERR_ARG_TEXT, FMD_IQ_F32, FMD_IQ_U8, SCAN_CANDIDATE_DTYPE, Batch, FmdError, FmdScanParams, _check,
+               iq_format_of, lib, make_params)
+
+_INTEGER_IQ = (np.dtype(np.uint8), np.dtype(np.int8), np.dtype(np.int16))
 
 
 class Scan:
@@ -49,14 +51,24 @@ class Scan:
     def reset(self, stream=None):
         _check(lib().fmd_scan_reset(self._h, stream))
 
-    def accumulate_device(self, ptr, stride, samples, stream=None, u8=False):
-        """Capture g at ptr + 2*g*stride floats (bytes with u8=True), `samples` IQ samples each."""
+    def accumulate_device(self, ptr, stride, samples, stream=None, u8=False, fmt=None):
+        """Capture g at ptr + 2*g*stride floats (bytes with u8=True), `samples` IQ samples each; fmt (FMD_IQ_*): the
+        captures' format, stride in IQ samples (fmd_scan_accumulate_device_fmt)."""
+        if fmt is not None:
+            _check(lib().fmd_scan_accumulate_device_fmt(self._h, ptr, int(fmt), int(stride), int(samples), stream))
+            return
         fn = lib().fmd_scan_accumulate_device_u8 if u8 else lib().fmd_scan_accumulate_device
         _check(fn(self._h, ptr, int(stride), int(samples), stream))
 
     def accumulate_host(self, iq):
-        """iq: [G, n] complex64 (or float32 [G, 2n]); [n] for a single capture."""
+        """iq: [G, n] complex64 (or float32 [G, 2n]); [n] for a single capture.  uint8 / int8 / int16 arrays [G, 2n]
+        are integer IQ of that format (fmd_scan_accumulate_host_fmt), converted on the device like the decoder's."""
         iq = np.ascontiguousarray(iq)
+        if iq.dtype in _INTEGER_IQ:
+            iq, fmt, _ = iq_format_of(iq.reshape(self.n_captures, -1))
+            n = iq.shape[1] // 2
+            _check(lib().fmd_scan_accumulate_host_fmt(self._h, iq.ctypes.data, fmt, n, n))
+            return
         if iq.dtype != np.complex64:
             iq = np.ascontiguousarray(iq, dtype=np.float32).view(np.complex64)
         iq = iq.reshape(self.n_captures, -1)
@@ -101,7 +113,7 @@ class Scan:
 def scan_stations(source, n_captures, sample_rate_if, table_size=24, scan_calls=4, confirm_calls=48, center_hz=None,
                   u8=False, **scan_kw):
     """Find the stations of n_captures captures.  source(call) -> [G, n] complex64 captures (u8=True: [G, 2n]
-    RTL-SDR bytes) of one call; calls 0 .. scan_calls-1 go through the spectral scan, the next confirm_calls through
+    RTL-SDR bytes; int8 / int16 arrays [G, 2n]: signed integer IQ, taken by their dtype) of one call; calls 0 .. scan_calls-1 go through the spectral scan, the next confirm_calls through
     one decoder batch with a channel per candidate (the tuner dialog's 1.25 s dwell at 2.4 MS/s and n = 65 536).
     Returns per capture a list of stations by increasing frequency: shift, offset_hz (or freq_hz = center_hz +
     offset when center_hz is given), power_db, snr_db, stereo, pilot_level, tuning_offset, pi (the most frequent
@@ -140,13 +152,16 @@ def scan_stations(source, n_captures, sample_rate_if, table_size=24, scan_calls=
         for call in range(scan_calls, scan_calls + confirm_calls):
             # device calls: the groups stay queued for collect_rds (a host call would drain them itself)
             x = np.ascontiguousarray(source(call))
-            if not u8 and x.dtype == np.complex64:
+            fmt = FMD_IQ_U8 if u8 else FMD_IQ_F32
+            if not u8 and x.dtype in _INTEGER_IQ[1:]:
+                x, fmt, _ = iq_format_of(x)
+            elif not u8 and x.dtype == np.complex64:
                 x = x.view(np.float32)
             d = torch.from_numpy(x.reshape(G, -1)).cuda()
             n = d.shape[1] // 2
             a_stride = b.max_audio_floats(n)
             audio = torch.empty((G * k, a_stride), dtype=torch.float32, device="cuda")
-            b.process_device(d.data_ptr(), n, n, audio.data_ptr(), a_stride, stream=stream.cuda_stream, u8=u8)
+            b.process_device(d.data_ptr(), n, n, audio.data_ptr(), a_stride, stream=stream.cuda_stream, fmt=fmt)
             groups = b.collect_rds_array(run_group_decoder=True, stream=stream.cuda_stream)
             for ch, blk in zip(groups["channel"], groups["blocks"]):
                 blocks[int(ch)][int(blk[0])] += 1
