@@ -97,6 +97,15 @@ public:
     return n > 0 ? static_cast<unsigned int>(n) : 0u;
   }
 
+  /* Not in the reference: ProcessStream with the audio as interleaved signed 16-bit PCM, L, R, L, R, ... --
+   * saturate(round_half_even(x * 32768)) of the float sample ProcessStream writes (FMD_PCM_S16); returns the number
+   * of int16 samples written (2 per frame).  Calls of the two may follow each other freely. */
+  unsigned int ProcessStreamToPcm16(const ComplexType* samples_in, unsigned int samples, int16_t* audio)
+  {
+    const int n = fmd_process_stream_pcm(m_dec, samples_in, FMD_IQ_F32, samples, audio, FMD_PCM_S16);
+    return n > 0 ? static_cast<unsigned int>(n) : 0u;
+  }
+
   bool StereoDetected() const { return Status().stereo_detected != 0; }
   RealType GetTuningOffset() const { return Status().tuning_offset; }
   RealType GetInterfaceLevel() const { return Status().interface_level; }

@@ -73,6 +73,24 @@ extern "C" {
 #define FMD_IQ_S8 2
 #define FMD_IQ_S16 3
 
+/* Audio output formats: the `pcm_format` argument of the _pcm entry points.  L and R interleaved, host byte order.
+ *   FMD_PCM_F32  float L, R     what cFmDecoder::ProcessStream hands its caller; the default everywhere   4 bytes
+ *   FMD_PCM_S16  int16_t L, R   saturate_int16(round_half_even(x * 32768.0f)), NaN gives 0                2
+ * where x is the float sample the FMD_PCM_F32 call writes: x * 2^15 is exact in float (short of overflow, which
+ * saturates), so every sample has one right value -- 1.0 gives 32767, -1.0 gives -32768, 0.5 / 32768 gives 0,
+ * 1.5 / 32768 and 2.5 / 32768 give 2.  No dither and no gain argument: the scale is fixed like the input's.  The
+ * conversion happens in the registers of the audio tail kernel (fmd_f32_to_s16, csrc/fmd_math.h); half the bytes
+ * leave the device.  The same number of samples per channel as the float call; strides and sample counts are in
+ * elements of the format.  Everything else a call produces -- channel state, status record, the audio meter
+ * (its sums are taken over the float samples), RDS groups -- is the bits of the same call with FMD_PCM_F32, and
+ * the format is a property of the call: calls of either format may follow each other freely.
+ * Stereo programme material overshoots full scale now and then (the stereo lock's transient; over-deviated
+ * stations all the time): fmd_batch_read_pcm_clipped counts the samples that saturated.
+ * A format outside 0..1 is refused with FMD_ERR_ARG before anything else is looked at.  The functions without
+ * _pcm remain and are calls of the _pcm ones with FMD_PCM_F32. */
+#define FMD_PCM_F32 0
+#define FMD_PCM_S16 1
+
 /* Constructor arguments of cFmDecoder (FmDecode.h:110-116).  table_size / if_filter_order are
  * the two internal constants BASELINE configs 3 and 5 override; 0 selects the reference
  * values 64 (FmDecode.cpp:249) and 8*downsample (FmDecode.cpp:262). */
@@ -158,6 +176,10 @@ int fmd_process_stream(fmd_decoder* d, const float* iq, unsigned samples, float*
 int fmd_process_stream_u8(fmd_decoder* d, const uint8_t* buf, unsigned samples, float* audio);
 /* The same for any input format (FMD_IQ_*): iq = samples (I, Q) pairs of that format. */
 int fmd_process_stream_fmt(fmd_decoder* d, const void* iq, int format, unsigned samples, float* audio);
+/* ... and any output format (FMD_PCM_*): audio = caller buffer of samples*2 elements of that format; returns the
+ * number of samples written (2 per audio frame) or a negative error. */
+int fmd_process_stream_pcm(fmd_decoder* d, const void* iq, int iq_format, unsigned samples, void* audio,
+                           int pcm_format);
 int fmd_get_status(fmd_decoder* d, fmd_status* st);
 /* The one-channel batch behind a decoder: for the profiling / development calls below (fmd_batch_set_
  * profiling, fmd_batch_get_stage_ms, fmd_batch_debug_*); not for processing (the decoder owns it). */
@@ -214,6 +236,15 @@ int fmd_batch_process_device_fmt(fmd_batch* b, const void* d_iq, int format, siz
                                  unsigned samples, float* d_audio, size_t audio_channel_stride,
                                  unsigned* out_floats, void* stream);
 
+/* Same for any output format (FMD_PCM_*): channel c's interleaved L/R samples start audio_channel_stride elements of
+ * that format behind channel c - 1's, and *out_samples counts elements of it (fmd_batch_max_audio_floats is the
+ * bound for both formats: it is a sample count).  FMD_PCM_S16: d_audio must be 16-byte aligned and
+ * audio_channel_stride a multiple of 8 elements (a lane stores four frames at a time), else FMD_ERR_ARG; nothing is
+ * written behind a row's out_samples elements. */
+int fmd_batch_process_device_pcm(fmd_batch* b, const void* d_iq, int iq_format, size_t iq_channel_stride,
+                                 unsigned samples, void* d_audio, int pcm_format, size_t audio_channel_stride,
+                                 unsigned* out_samples, void* stream);
+
 /* Host-buffer call: copies in, runs fmd_batch_process_device, copies audio out, collects RDS
  * groups and runs the UECP group decoder (callbacks fire here).  Synchronous.  Returns FMD_OK, a
  * negative error, or FMD_WARN_RDS_LOST (once) when groups were dropped because a queue was full:
@@ -227,6 +258,19 @@ int fmd_batch_process_host_u8(fmd_batch* b, const uint8_t* iq_u8, size_t iq_chan
 int fmd_batch_process_host_fmt(fmd_batch* b, const void* iq, int format, size_t iq_channel_stride,
                                unsigned samples, float* audio, size_t audio_channel_stride,
                                unsigned* out_floats);
+/* Any output format (FMD_PCM_*); any stride and alignment of `audio` (rows are copied): FMD_PCM_S16 brings half the
+ * bytes back from the device. */
+int fmd_batch_process_host_pcm(fmd_batch* b, const void* iq, int iq_format, size_t iq_channel_stride,
+                               unsigned samples, void* audio, int pcm_format, size_t audio_channel_stride,
+                               unsigned* out_samples);
+
+/* out[i] = the number of audio samples of channel first_channel + i (L and R counted separately) that FMD_PCM_S16
+ * calls have saturated since the batch was created: samples whose rounded value lay outside [-32768, 32767] and was
+ * clamped (NaN, which gives 0, is not one).  FMD_PCM_F32 calls add nothing.  Like the audio meter it belongs to the
+ * output, not to the decoder: fmd_batch_reset, fmd_batch_reset_channels, retunes and capture switches leave it.
+ * Synchronous: waits for every call of this batch submitted so far (like the host-buffer call, through the null
+ * stream).  A single decoder: through fmd_decoder_batch. */
+int fmd_batch_read_pcm_clipped(fmd_batch* b, unsigned first_channel, unsigned n, uint64_t* out);
 
 /* Copies the queued RDS groups (all channels, call order) to `out`, waits for `stream`.
  * Returns the number of groups (<= cap) or a negative error.  When run_group_decoder != 0
@@ -451,7 +495,8 @@ const char* fmd_stage_name(unsigned idx);
  * (host arrays).  what: 0 atan2f table form (a = y, b = x), 1 atan2f literal fdlibm, 2 sin/cos
  * table form (a = phase; out0 = sin, out1 = cos), 3 sin/cos series form, 4 mid-range division
  * a / b, 5 RTL-SDR byte -> float (a = byte value), 6 the RDS PLL's polynomial arctan2, 7 sin/cos of a
- * phase in [0, 8) with the exact float reduction (the serial stage's two NCOs). */
+ * phase in [0, 8) with the exact float reduction (the serial stage's two NCOs), 8 float -> 16-bit PCM
+ * (fmd_f32_to_s16 of a; out0 = the integer as a float). */
 int fmd_debug_math(int what, unsigned n, const float* a, const float* b, float* out0, float* out1);
 
 /* Dev aid, only with FMD_SERIAL_PROBE=1 in the environment at batch creation: per workgroup of the

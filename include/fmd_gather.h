@@ -13,6 +13,10 @@
  * two per rank), so that each peer uses its own xGMI link to rank 0.  It runs on a stream of the
  * library's own, behind an event on the caller's stream, and overlaps the next steps' compute; the
  * caller orders a stream behind it (fmd_gather_wait) before it reuses the buffers.
+ *
+ * The gather moves bytes: audio produced as 16-bit PCM (FMD_PCM_S16, fmd_batch_process_device_pcm) is sent as the
+ * floats its rows occupy -- audio_floats = channels x audio_stride / 2 with the stride (in int16 elements, a multiple
+ * of 8 anyway) even, d_audio / d_all_audio the int16 buffers cast to float* -- i.e. half the bytes per step.
  */
 #ifndef FMD_GATHER_H
 #define FMD_GATHER_H

@@ -23,6 +23,9 @@ FMD_WARN_RDS_LOST = 1
 # IQ input formats (include/fmd.h FMD_IQ_*): the `format` argument of the _fmt entry points
 FMD_IQ_F32, FMD_IQ_U8, FMD_IQ_S8, FMD_IQ_S16 = 0, 1, 2, 3
 IQ_BYTES = {FMD_IQ_F32: 8, FMD_IQ_U8: 2, FMD_IQ_S8: 2, FMD_IQ_S16: 4}  # per IQ sample
+# audio output formats (include/fmd.h FMD_PCM_*): the `pcm_format` argument of the _pcm entry points
+FMD_PCM_F32, FMD_PCM_S16 = 0, 1
+PCM_BYTES = {FMD_PCM_F32: 4, FMD_PCM_S16: 2}  # per audio sample
 
 TAPS = {"demod": 0, "baseband": 1, "pilot38": 2, "mono_rs": 3, "stereo_rs": 4, "rds_lpf": 5,
         "rds_pll": 6, "rds_mf": 7, "rds_sync": 8}
@@ -140,6 +143,8 @@ EXPORTS = [
     "fmd_scan_accumulate_device_u8", "fmd_scan_accumulate_host", "fmd_scan_finish_device", "fmd_scan_finish_host",
     "fmd_batch_process_device_fmt", "fmd_batch_process_host_fmt", "fmd_process_stream_fmt", "fmd_receiver_write_fmt",
     "fmd_scan_accumulate_device_fmt", "fmd_scan_accumulate_host_fmt",
+    "fmd_batch_process_device_pcm", "fmd_batch_process_host_pcm", "fmd_process_stream_pcm",
+    "fmd_batch_read_pcm_clipped",
 ]
 
 
@@ -261,6 +266,10 @@ def lib():
         L.fmd_receiver_write_fmt.argtypes = [vp, vp, i, u]
         L.fmd_scan_accumulate_device_fmt.argtypes = [vp, vp, i, C.c_size_t, u, vp]
         L.fmd_scan_accumulate_host_fmt.argtypes = [vp, vp, i, C.c_size_t, u]
+        L.fmd_batch_process_device_pcm.argtypes = [vp, vp, i, C.c_size_t, u, vp, i, C.c_size_t, C.POINTER(u), vp]
+        L.fmd_batch_process_host_pcm.argtypes = [vp, vp, i, C.c_size_t, u, vp, i, C.c_size_t, C.POINTER(u)]
+        L.fmd_process_stream_pcm.argtypes = [vp, vp, i, u, vp, i]
+        L.fmd_batch_read_pcm_clipped.argtypes = [vp, u, u, vp]
         _LIB = L
     return _LIB
 
@@ -291,6 +300,24 @@ def iq_format_of(arr):
         raise FmdError(FMD_ERR_ARG_TEXT % ("no IQ format for dtype %s (complex64, float32, uint8, int8, int16)"
                                            % a.dtype))
     return a, fmt, 2
+
+
+def pcm_format_of(pcm):
+    """FMD_PCM_* of a `pcm=` argument: None or np.float32 (the default output), np.int16, or the constant itself.
+    Anything else raises: no other output format exists."""
+    if pcm is None:
+        return FMD_PCM_F32
+    if isinstance(pcm, (int, np.integer)) and not isinstance(pcm, bool):
+        if int(pcm) in PCM_BYTES:
+            return int(pcm)
+    else:
+        try:
+            fmt = {np.dtype(np.float32): FMD_PCM_F32, np.dtype(np.int16): FMD_PCM_S16}.get(np.dtype(pcm))
+        except TypeError:
+            fmt = None
+        if fmt is not None:
+            return fmt
+    raise FmdError(FMD_ERR_ARG_TEXT % ("no audio format for %r (float32, int16, FMD_PCM_F32, FMD_PCM_S16)" % (pcm,)))
 
 
 FIR_SEQUENTIAL = 0
@@ -463,11 +490,13 @@ class Batch:
                                                audio.ctypes.data, a_stride, C.byref(nf)))
         return audio[:, :nf.value]
 
-    def process_host_fmt(self, iq, shared=False):
+    def process_host_fmt(self, iq, shared=False, pcm=None):
         """iq: [C, N] complex64, or [C, 2N] float32 / uint8 / int8 / int16 holding I, Q, I, Q, ... (rows as for
         process_host; one row when shared); the input format is the array's dtype (fmd_batch_process_host_fmt).
-        Signed integers are v * 2^-7 / v * 2^-15: the same bits as process_host on the converted block."""
+        Signed integers are v * 2^-7 / v * 2^-15: the same bits as process_host on the converted block.
+        pcm=np.int16: the audio as int16 (FMD_PCM_S16, fmd_batch_process_host_pcm)."""
         iq, fmt, per = iq_format_of(iq)
+        pcm_fmt = pcm_format_of(pcm)
         if shared:
             n = iq.size // per
             stride = 0
@@ -476,17 +505,27 @@ class Batch:
             n = iq.shape[1] // per
             stride = n
         a_stride = self.max_audio_floats(n)
-        audio = np.zeros((self.n_channels, a_stride), dtype=np.float32)
+        audio = np.zeros((self.n_channels, a_stride), dtype=np.int16 if pcm_fmt == FMD_PCM_S16 else np.float32)
         nf = C.c_uint()
-        _check(lib().fmd_batch_process_host_fmt(self._h, iq.ctypes.data, fmt, stride, n, audio.ctypes.data,
-                                                a_stride, C.byref(nf)))
+        if pcm is None:
+            _check(lib().fmd_batch_process_host_fmt(self._h, iq.ctypes.data, fmt, stride, n, audio.ctypes.data,
+                                                    a_stride, C.byref(nf)))
+        else:
+            _check(lib().fmd_batch_process_host_pcm(self._h, iq.ctypes.data, fmt, stride, n, audio.ctypes.data,
+                                                    pcm_fmt, a_stride, C.byref(nf)))
         return audio[:, :nf.value]
 
     def process_device(self, d_iq_ptr, iq_stride, samples, d_audio_ptr, audio_stride, stream=None,
-                       u8=False, fmt=None):
+                       u8=False, fmt=None, pcm=None):
         """iq_stride in IQ samples; u8=True: d_iq_ptr holds RTL-SDR byte pairs; fmt (FMD_IQ_*): the input format,
-        through fmd_batch_process_device_fmt."""
+        through fmd_batch_process_device_fmt; pcm (np.int16 / FMD_PCM_*): the output format, audio_stride and the
+        returned count in its elements, through fmd_batch_process_device_pcm."""
         nf = C.c_uint()
+        if pcm is not None:
+            in_fmt = int(fmt) if fmt is not None else FMD_IQ_U8 if u8 else FMD_IQ_F32
+            _check(lib().fmd_batch_process_device_pcm(self._h, d_iq_ptr, in_fmt, iq_stride, samples, d_audio_ptr,
+                                                      pcm_format_of(pcm), audio_stride, C.byref(nf), stream))
+            return nf.value
         if fmt is not None:
             _check(lib().fmd_batch_process_device_fmt(self._h, d_iq_ptr, int(fmt), iq_stride, samples, d_audio_ptr,
                                                       audio_stride, C.byref(nf), stream))
@@ -495,6 +534,13 @@ class Batch:
         _check(fn(self._h, d_iq_ptr, iq_stride, samples, d_audio_ptr, audio_stride, C.byref(nf),
                   stream))
         return nf.value
+
+    def pcm_clipped(self):
+        """uint64[C]: audio samples (L and R counted separately) that FMD_PCM_S16 calls have saturated since the batch
+        was created (fmd_batch_read_pcm_clipped); waits for every call submitted so far."""
+        out = np.zeros(self.n_channels, dtype=np.uint64)
+        _check(lib().fmd_batch_read_pcm_clipped(self._h, 0, self.n_channels, out.ctypes.data))
+        return out
 
     def collect_rds_array(self, cap=65536, run_group_decoder=False, stream=None, lag=0):
         """Queued RDS groups as a numpy structured array (channel, call_index, blocks[4])."""
@@ -671,6 +717,16 @@ class FmDecoder:
             iq = iq.astype(np.float32).view(np.complex64)
         audio = np.empty(2 * iq.size, dtype=np.float32)  # RadioReceiver.cpp:519-520 sizing
         n = _check(lib().fmd_process_stream(self._h, iq.ctypes.data, iq.size, audio.ctypes.data))
+        return audio[:n]
+
+    def ProcessStreamToPcm16(self, samples_in):
+        """ProcessStream with the audio as interleaved int16 L, R (FMD_PCM_S16, fmd_process_stream_pcm)."""
+        iq = np.ascontiguousarray(samples_in)
+        if iq.dtype != np.complex64:
+            iq = iq.astype(np.float32).view(np.complex64)
+        audio = np.empty(2 * iq.size, dtype=np.int16)
+        n = _check(lib().fmd_process_stream_pcm(self._h, iq.ctypes.data, FMD_IQ_F32, iq.size, audio.ctypes.data,
+                                                FMD_PCM_S16))
         return audio[:n]
 
     def ProcessStreamU8(self, buf):

@@ -1,0 +1,119 @@
+/*
+ * fmd_audio_tail.inc -- the body of the audio tail kernels (fmd_k_tail.hip.h: k_audio_tail, k_audio_tail_s16), one
+ * text for every output format.  The including kernel names its output policy OUT (OutF32 / OutS16) and defines
+ * FMD_TAIL_DONE_ARGS: the policy's own arguments of done(), with their leading comma, or nothing.
+ */
+  __builtin_amdgcn_s_setprio(3);
+  const unsigned lane = threadIdx.x;
+  // (blockDim.y channel groups per workgroup, a wave each, nothing shared: "light_pack" -- a CU that is awake for
+  // one wave draws as much as one that is busy, so the light part's waves go four to a CU: MEASUREMENTS, round 5)
+  const unsigned c0 = (blockIdx.x * blockDim.y + threadIdx.y) * 64 + lane;
+  if (c0 - lane >= CP)
+    return;
+  const bool active = c0 < C;
+  const unsigned c = active ? c0 : C - 1;
+  float de_re = st.F(F_DE_RE)[c], de_im = st.F(F_DE_IM)[c];
+  float w1a = st.F(F_N_W1A)[c], w2a = st.F(F_N_W2A)[c], w1b = st.F(F_N_W1B)[c], w2b = st.F(F_N_W2B)[c];
+  const int stereo = st.I(I_STEREO_Q0 + (int)stereo_q)[c];
+  const float one_minus_alpha = 1.0f - k.de_alpha;
+  // cRadioReceiver::SamplesMeanRMS over the packet (RadioReceiver.cpp:584-598): float sums over
+  // the interleaved samples L0, R0, L1, R1, ... in that order
+  float vsum = 0.0f, vsumsq = 0.0f;
+
+  auto frame = [&](float2 v) -> float2 { // v.x = stereo, v.y = mono (ProcessTwo's A, B)
+    de_re = one_minus_alpha * de_re + k.de_alpha * v.x;
+    const float s0 = de_re * 2.0f;
+    de_im = one_minus_alpha * de_im + k.de_alpha * v.y;
+    const float m0 = de_im * 2.0f;
+    const float w0a = s0 - k.n_a1 * w1a - k.n_a2 * w2a;
+    const float w0b = m0 - k.n_a1 * w1b - k.n_a2 * w2b;
+    const float s = k.n_b0 * w0a + k.n_b1 * w1a + k.n_b2 * w2a;
+    const float m = k.n_b0 * w0b + k.n_b1 * w1b + k.n_b2 * w2b;
+    w2a = w1a;
+    w1a = w0a;
+    w2b = w1b;
+    w1b = w0b;
+    const float mm = m * 0.5f;
+    const float2 o = stereo ? make_float2((m + s) * 0.5f, (m - s) * 0.5f) : make_float2(mm, mm);
+    vsum += o.x;
+    vsumsq += o.x * o.x;
+    vsum += o.y;
+    vsumsq += o.y * o.y;
+    return o;
+  };
+  typename OUT::frame_t* __restrict__ o = reinterpret_cast<typename OUT::frame_t*>(audio + (size_t)c * audio_stride);
+  typename OUT::State os;
+
+  unsigned i0 = 0;
+  // full tiles: the loads of the next tile are in flight while this one goes through the recurrence
+  // out of registers (past the last full tile: clamped rows nobody uses)
+  float2 vnext[AT_STEPS];
+#pragma unroll
+  for (unsigned u = 0; u < AT_STEPS; u++)
+    vnext[u] = lp[(size_t)min(u, A - 1) * CP + c];
+  for (; i0 + AT_STEPS <= A; i0 += AT_STEPS)
+  {
+    float2 vin[AT_STEPS];
+#pragma unroll
+    for (unsigned u = 0; u < AT_STEPS; u++)
+      vin[u] = vnext[u];
+#pragma unroll
+    for (unsigned u = 0; u < AT_STEPS; u++)
+      vnext[u] = lp[(size_t)min(i0 + AT_STEPS + u, A - 1) * CP + c];
+#pragma unroll
+    for (unsigned u = 0; u < AT_STEPS; u++)
+    {
+      const float2 f = frame(vin[u]);
+      OUT::take(os, u, f);
+      if (active)
+        OUT::store(o, os, i0, u, f);
+    }
+  }
+  if (i0 < A)
+  {
+    const unsigned cnt = A - i0;
+#pragma unroll
+    for (unsigned u = 0; u < AT_STEPS; u++) // the ragged last tile is already in vnext
+      if (u < cnt)
+      {
+        const float2 f = frame(vnext[u]);
+        OUT::take(os, u, f);
+        if (active)
+          OUT::store(o, os, i0, u, f);
+      }
+    OUT::flush(o, os, i0, cnt, active);
+  }
+  if (active)
+  {
+    st.F(F_DE_RE)[c] = de_re;
+    st.F(F_DE_IM)[c] = de_im;
+    st.F(F_N_W1A)[c] = w1a;
+    st.F(F_N_W2A)[c] = w2a;
+    st.F(F_N_W1B)[c] = w1b;
+    st.F(F_N_W2B)[c] = w2b;
+    // mean = vsum / n, rms = sqrt(vsumsq / n) in float (n = floats in the packet), then
+    // m_AudioLevel = 0.95 * m_AudioLevel + 0.05 * audio_rms in double (RadioReceiver.cpp:526-528)
+    const float n = (float)(2u * A);
+    const float rms = sqrtf(vsumsq / n);
+    const float mean = vsum / n;
+    const float level = (float)(0.95 * (double)st.F(F_AUDIO_LEVEL)[c] + 0.05 * (double)rms);
+    st.F(F_AUDIO_MEAN)[c] = mean;
+    st.F(F_AUDIO_RMS)[c] = rms;
+    st.F(F_AUDIO_LEVEL)[c] = level;
+    /* The call is complete for this channel: its status record (see HostStatusWord).  The level
+     * meters are the state arrays as they stand now; the stereo flag is this call's own copy.  With
+     * overlapped calls (concurrency 2) the next call's IF / baseband meters may already be in -- the
+     * reference's status thread reads its decoder mid-call too (RadioReceiver.cpp:544-572 against
+     * :524, no common lock). */
+    unsigned* __restrict__ h = st.ds + c;
+    const size_t CPs = st.CP;
+    h[HS_IF_LEVEL * CPs] = __float_as_uint(st.F(F_IF_LEVEL)[c]);
+    h[HS_BB_MEAN * CPs] = __float_as_uint(st.F(F_BB_MEAN)[c]);
+    h[HS_BB_LEVEL * CPs] = __float_as_uint(st.F(F_BB_LEVEL)[c]);
+    h[HS_P_LEVEL * CPs] = __float_as_uint(st.F(F_P_LEVEL)[c]);
+    h[HS_STEREO * CPs] = (unsigned)stereo;
+    h[HS_AUDIO_MEAN * CPs] = __float_as_uint(mean);
+    h[HS_AUDIO_RMS * CPs] = __float_as_uint(rms);
+    h[HS_AUDIO_LEVEL * CPs] = __float_as_uint(level);
+    OUT::done(os, c FMD_TAIL_DONE_ARGS);
+  }

@@ -265,8 +265,11 @@ struct fmd_batch
   fmd::ChannelState st{};
   std::vector<fmd::HbCoef> hbcoef;
 
-  // host staging for the host-buffer entry point
+  // host staging for the host-buffer entry point (h_audio: sized in bytes of the call's output format)
   DevBuf<float> h_iq, h_audio;
+  // per channel: audio samples that FMD_PCM_S16 calls saturated since the batch was created (k_audio_tail<OutS16>;
+  // fmd_batch_read_pcm_clipped).  It belongs to the output like the audio meter: nothing resets it.
+  DevBuf<unsigned long long> pcm_clip; // [CP]
 
   std::vector<std::unique_ptr<fmd::GroupDecoder>> gdec;
 
@@ -302,7 +305,8 @@ struct fmd_batch
     bool status_after_rds = false;     // the two halves are on different streams: the status record waits for EV_RDS
     hipEvent_t prev_aud = nullptr;     // ... and the bit recovery for the previous call's status record
     uint32_t call_index = 0;
-    float* d_audio = nullptr;
+    void* d_audio = nullptr;           // rows of the call's output format (pcm: FMD_PCM_*), stride in its elements
+    int pcm = 0;
     size_t audio_stride = 0;
     hipEvent_t tl0 = nullptr, tl1 = nullptr; // profiling level 1: the audio tail's own start / stop
   };
@@ -1053,6 +1057,7 @@ int create_one(const fmd_params* params, unsigned n_channels, const int* tuning_
   bad |= b->sctab.alloc(d.sincos_tab.size());
   bad |= b->sctab256.alloc(d.sincos_tab256.size());
   bad |= b->fstate.alloc(size_t(fmd::F_SLOTS) * CP);
+  bad |= b->pcm_clip.alloc(CP);
   bad |= b->istate.alloc(size_t(fmd::I_SLOTS) * CP);
   bad |= b->r_data.alloc(size_t(4) * CP);
   b->queue_cap = std::max(4096u, 8u * C);
@@ -1630,15 +1635,17 @@ static int wait_impl(fmd_batch* b, int lag, void* stream_, bool take_lost);
 /* One call of any batch: a plain one directly; a shell's as one call of every sub-batch, in channel order, on the
  * same streams (fmd_batch::subs). */
 static int process_shell(fmd_batch* b, const void* d_iq, IqFormat fmt, size_t iq_channel_stride, unsigned samples,
-                         float* d_audio, size_t audio_channel_stride, unsigned* out_floats, void* stream);
+                         void* d_audio, PcmFormat pcm, size_t audio_channel_stride, unsigned* out_floats,
+                         void* stream);
 
 /* Pending single-channel edits (retunes, resets) in front of the call; with retuning enabled, the silent twin's call
  * (zeros of the same size, on the same streams) behind it.  A batch with neither takes the plain path alone. */
 static int process_any(fmd_batch* b, const void* d_iq, IqFormat fmt, size_t iq_channel_stride, unsigned samples,
-                       float* d_audio, size_t audio_channel_stride, unsigned* out_floats, void* stream)
+                       void* d_audio, PcmFormat pcm, size_t audio_channel_stride, unsigned* out_floats, void* stream)
 {
   if (!b || (!b->twin && !b->edits_pending))
-    return process_shell(b, d_iq, fmt, iq_channel_stride, samples, d_audio, audio_channel_stride, out_floats, stream);
+    return process_shell(b, d_iq, fmt, iq_channel_stride, samples, d_audio, pcm, audio_channel_stride, out_floats,
+                         stream);
   if (!d_iq || !d_audio)
     return fail(FMD_ERR_ARG, "fmd_batch_process_device: null argument");
   if (samples > FMD_MAX_BLOCK || samples < b->min_samples)
@@ -1655,11 +1662,12 @@ static int process_any(fmd_batch* b, const void* d_iq, IqFormat fmt, size_t iq_c
       return rc;
     }
   b->edits_pending = false;
-  const int rc =
-      process_shell(b, d_iq, fmt, iq_channel_stride, samples, d_audio, audio_channel_stride, out_floats, stream);
+  const int rc = process_shell(b, d_iq, fmt, iq_channel_stride, samples, d_audio, pcm, audio_channel_stride,
+                               out_floats, stream);
   if (rc != FMD_OK || !tw)
     return rc;
-  const int trc = process_device_impl(tw, b->twin_iq.p, IQ_F32, 0, samples, b->twin_audio.p,
+  // (the twin's audio is discarded: it stays float whatever the call's format)
+  const int trc = process_device_impl(tw, b->twin_iq.p, IQ_F32, 0, samples, b->twin_audio.p, PCM_F32,
                                       b->twin_audio.n, nullptr, stream);
   if (trc != FMD_OK)
     mark_failed(b, "the silent twin refused a call the batch took");
@@ -1667,11 +1675,11 @@ static int process_any(fmd_batch* b, const void* d_iq, IqFormat fmt, size_t iq_c
 }
 
 static int process_shell(fmd_batch* b, const void* d_iq, IqFormat fmt, size_t iq_channel_stride, unsigned samples,
-                         float* d_audio, size_t audio_channel_stride, unsigned* out_floats, void* stream)
+                         void* d_audio, PcmFormat pcm, size_t audio_channel_stride, unsigned* out_floats, void* stream)
 {
   if (!b || b->subs.empty())
-    return process_device_impl(b, d_iq, fmt, iq_channel_stride, samples, d_audio, audio_channel_stride, out_floats,
-                               stream);
+    return process_device_impl(b, d_iq, fmt, iq_channel_stride, samples, d_audio, pcm, audio_channel_stride,
+                               out_floats, stream);
   if (!d_iq || !d_audio)
     return fail(FMD_ERR_ARG, "fmd_batch_process_device: null argument");
   if (int rc = check_device_errors(b))
@@ -1686,8 +1694,10 @@ static int process_shell(fmd_batch* b, const void* d_iq, IqFormat fmt, size_t iq
     // (a capture map: every sub-batch takes the first row, its walk names the rows it reads)
     const size_t row0 = b->map_on ? 0 : ch0 / b->cpc;
     const char* iq = static_cast<const char*>(d_iq) + row0 * iq_channel_stride * esz;
-    const int rc = process_device_impl(sb, iq, fmt, iq_channel_stride, samples,
-                                       d_audio + size_t(ch0) * audio_channel_stride, audio_channel_stride, &nf, stream);
+    // (the sub-batch's first row: ch0 * stride elements of the output format)
+    char* audio = static_cast<char*>(d_audio) + size_t(ch0) * audio_channel_stride * pcm_esz(pcm);
+    const int rc = process_device_impl(sb, iq, fmt, iq_channel_stride, samples, audio, pcm, audio_channel_stride, &nf,
+                                       stream);
     if (rc != FMD_OK)
     { // the first sub-batch refuses what every one of them would refuse (same geometry, same positions): nothing
       // has been submitted.  Later: part of the call is on the device -- the batch is unusable until reset.
@@ -1712,14 +1722,33 @@ static int process_shell(fmd_batch* b, const void* d_iq, IqFormat fmt, size_t iq
   return FMD_OK;
 }
 
+int fmd_batch_process_device_pcm(fmd_batch* b, const void* d_iq, int iq_format, size_t iq_channel_stride,
+                                 unsigned samples, void* d_audio, int pcm_format, size_t audio_channel_stride,
+                                 unsigned* out_samples, void* stream)
+{
+  if (!iq_format_ok(iq_format))
+    return fail(FMD_ERR_ARG,
+                "fmd_batch_process_device_pcm: iq_format must be one of FMD_IQ_F32, _U8, _S8, _S16 (0..3)");
+  if (!pcm_format_ok(pcm_format))
+    return fail(FMD_ERR_ARG, "fmd_batch_process_device_pcm: pcm_format must be FMD_PCM_F32 or FMD_PCM_S16 (0..1)");
+  // four 16-bit frames go out as one 16-byte store: every row has to start on a 16-byte boundary (a null argument
+  // gets its own sentence further down)
+  if (pcm_format == FMD_PCM_S16 && b && d_iq && d_audio &&
+      ((reinterpret_cast<uintptr_t>(d_audio) % 16) || (audio_channel_stride % 8)))
+    return fail(FMD_ERR_ARG, "fmd_batch_process_device_pcm: for FMD_PCM_S16 the audio pointer must be 16-byte aligned "
+                             "and audio_channel_stride a multiple of 8 elements");
+  return process_any(b, d_iq, IqFormat(iq_format), iq_channel_stride, samples, d_audio, PcmFormat(pcm_format),
+                     audio_channel_stride, out_samples, stream);
+}
+
 int fmd_batch_process_device_fmt(fmd_batch* b, const void* d_iq, int format, size_t iq_channel_stride,
                                  unsigned samples, float* d_audio, size_t audio_channel_stride,
                                  unsigned* out_floats, void* stream)
 {
   if (!iq_format_ok(format))
     return fail(FMD_ERR_ARG, "fmd_batch_process_device_fmt: format must be one of FMD_IQ_F32, _U8, _S8, _S16 (0..3)");
-  return process_any(b, d_iq, IqFormat(format), iq_channel_stride, samples, d_audio, audio_channel_stride, out_floats,
-                     stream);
+  return fmd_batch_process_device_pcm(b, d_iq, format, iq_channel_stride, samples, d_audio, FMD_PCM_F32,
+                                      audio_channel_stride, out_floats, stream);
 }
 
 int fmd_batch_process_device(fmd_batch* b, const float* d_iq, size_t iq_channel_stride,
@@ -2345,7 +2374,7 @@ int fmd_batch_export_rds_device(fmd_batch* b, int32_t* d_records, unsigned cap, 
 }
 
 static int process_host_impl(fmd_batch* b, const void* iq, IqFormat fmt, size_t iq_channel_stride,
-                             unsigned samples, float* audio, size_t audio_channel_stride,
+                             unsigned samples, void* audio, PcmFormat pcm, size_t audio_channel_stride,
                              unsigned* out_floats)
 {
   if (!b || !iq || !audio)
@@ -2359,9 +2388,13 @@ static int process_host_impl(fmd_batch* b, const void* iq, IqFormat fmt, size_t 
   // input rows: one per capture of the map, per channel, per cpc channels, or one
   const unsigned streams = !iq_channel_stride ? 1u : b->map_on ? b->n_cap : C / b->cpc;
   const size_t iq_floats = (dev_row * streams + 3) / 4;
-  const size_t a_stride = (size_t(fmd_batch_max_audio_floats(b, samples)) + 3) & ~size_t(3);
+  // audio staging: rows of a_stride elements of the output format, every row on a 16-byte boundary
+  const size_t asz = pcm_esz(pcm);
+  const size_t a_round = pcm == PCM_S16 ? 7 : 3;
+  const size_t a_stride = (size_t(fmd_batch_max_audio_floats(b, samples)) + a_round) & ~a_round;
+  const size_t audio_floats = a_stride * C * asz / sizeof(float);
   if ((iq_floats > b->h_iq.n && b->h_iq.alloc(iq_floats)) ||
-      (a_stride * C > b->h_audio.n && b->h_audio.alloc(a_stride * C)))
+      (audio_floats > b->h_audio.n && b->h_audio.alloc(audio_floats)))
     return fail(FMD_ERR_DEVICE, "staging allocation failed");
   using clk = std::chrono::steady_clock;
   auto ms_since = [](clk::time_point t) { return std::chrono::duration<double, std::milli>(clk::now() - t).count(); };
@@ -2374,7 +2407,7 @@ static int process_host_impl(fmd_batch* b, const void* iq, IqFormat fmt, size_t 
   b->host_ms[0] += ms_since(tp);
   tp = clk::now();
   unsigned nf = 0;
-  int rc = process_any(b, b->h_iq.p, fmt, dev_iq_stride, samples, b->h_audio.p, a_stride, &nf, nullptr);
+  int rc = process_any(b, b->h_iq.p, fmt, dev_iq_stride, samples, b->h_audio.p, pcm, a_stride, &nf, nullptr);
   if (rc != FMD_OK)
     return rc;
   if (C > 1 && nf > audio_channel_stride)
@@ -2386,8 +2419,8 @@ static int process_host_impl(fmd_batch* b, const void* iq, IqFormat fmt, size_t 
   rc = wait_impl(b, 0, nullptr, false); // the groups-lost flag is this call's to report, at its end
   if (rc < 0)
     return rc;
-  HIPCHK(hipMemcpy2D(audio, (C > 1 ? audio_channel_stride : size_t(nf)) * sizeof(float), b->h_audio.p,
-                     a_stride * sizeof(float), size_t(nf) * sizeof(float), C, hipMemcpyDeviceToHost));
+  HIPCHK(hipMemcpy2D(audio, (C > 1 ? audio_channel_stride : size_t(nf)) * asz, b->h_audio.p, a_stride * asz,
+                     size_t(nf) * asz, C, hipMemcpyDeviceToHost));
   b->host_ms[2] += ms_since(tp);
   tp = clk::now();
   rc = fmd_batch_collect_rds(b, nullptr, 0, 1, nullptr);
@@ -2400,13 +2433,52 @@ static int process_host_impl(fmd_batch* b, const void* iq, IqFormat fmt, size_t 
   return take_lost_groups(b); // FMD_OK, or FMD_WARN_RDS_LOST once: audio and state are intact
 }
 
+int fmd_batch_process_host_pcm(fmd_batch* b, const void* iq, int iq_format, size_t iq_channel_stride,
+                               unsigned samples, void* audio, int pcm_format, size_t audio_channel_stride,
+                               unsigned* out_samples)
+{
+  if (!iq_format_ok(iq_format))
+    return fail(FMD_ERR_ARG, "fmd_batch_process_host_pcm: iq_format must be one of FMD_IQ_F32, _U8, _S8, _S16 (0..3)");
+  if (!pcm_format_ok(pcm_format))
+    return fail(FMD_ERR_ARG, "fmd_batch_process_host_pcm: pcm_format must be FMD_PCM_F32 or FMD_PCM_S16 (0..1)");
+  return process_host_impl(b, iq, IqFormat(iq_format), iq_channel_stride, samples, audio, PcmFormat(pcm_format),
+                           audio_channel_stride, out_samples);
+}
+
 int fmd_batch_process_host_fmt(fmd_batch* b, const void* iq, int format, size_t iq_channel_stride, unsigned samples,
                                float* audio, size_t audio_channel_stride, unsigned* out_floats)
 {
   if (!iq_format_ok(format))
     return fail(FMD_ERR_ARG, "fmd_batch_process_host_fmt: format must be one of FMD_IQ_F32, _U8, _S8, _S16 (0..3)");
-  return process_host_impl(b, iq, IqFormat(format), iq_channel_stride, samples, audio, audio_channel_stride,
-                           out_floats);
+  return fmd_batch_process_host_pcm(b, iq, format, iq_channel_stride, samples, audio, FMD_PCM_F32,
+                                    audio_channel_stride, out_floats);
+}
+
+int fmd_batch_read_pcm_clipped(fmd_batch* b, unsigned first_channel, unsigned n, uint64_t* out)
+{
+  if (!b || !out)
+    return fail(FMD_ERR_ARG, "fmd_batch_read_pcm_clipped: null argument");
+  if (first_channel > b->C || n > b->C - first_channel)
+    return fail(FMD_ERR_ARG, "fmd_batch_read_pcm_clipped: channels [" + std::to_string(first_channel) + ", " +
+                                 std::to_string(size_t(first_channel) + n) + ") out of range (" +
+                                 std::to_string(b->C) + " channels)");
+  HIPCHK(hipSetDevice(b->device));
+  // every call of this batch submitted so far, on whatever stream its audio tail runs: the null stream behind their
+  // events, then the host behind the null stream (what the host-buffer call does before it copies the audio out)
+  if (int rc = wait_impl(b, 0, nullptr, false); rc < 0)
+    return rc;
+  HIPCHK(hipStreamSynchronize(nullptr));
+  static_assert(sizeof(unsigned long long) == sizeof(uint64_t), "the counter's word");
+  for (unsigned c = first_channel; c < first_channel + n;)
+  { // run by run of channels with one owner (a shell: its sub-batches)
+    unsigned lc = 0;
+    const fmd_batch* ob = owner_of(b, c, &lc);
+    const unsigned run = std::min(first_channel + n - c, ob->C - lc);
+    HIPCHK(hipMemcpy(out + (c - first_channel), ob->pcm_clip.p + lc, size_t(run) * sizeof(uint64_t),
+                     hipMemcpyDeviceToHost));
+    c += run;
+  }
+  return FMD_OK;
 }
 
 int fmd_batch_process_host(fmd_batch* b, const float* iq, size_t iq_channel_stride, unsigned samples,
@@ -2714,15 +2786,25 @@ int fmd_reset(fmd_decoder* d)
   return d ? fmd_batch_reset(d->b) : fail(FMD_ERR_ARG, "null decoder");
 }
 
+int fmd_process_stream_pcm(fmd_decoder* d, const void* iq, int iq_format, unsigned samples, void* audio,
+                           int pcm_format)
+{
+  if (!iq_format_ok(iq_format))
+    return fail(FMD_ERR_ARG, "fmd_process_stream_pcm: iq_format must be one of FMD_IQ_F32, _U8, _S8, _S16 (0..3)");
+  if (!pcm_format_ok(pcm_format))
+    return fail(FMD_ERR_ARG, "fmd_process_stream_pcm: pcm_format must be FMD_PCM_F32 or FMD_PCM_S16 (0..1)");
+  if (!d)
+    return fail(FMD_ERR_ARG, "null decoder");
+  unsigned nf = 0;
+  int rc = fmd_batch_process_host_pcm(d->b, iq, iq_format, 0, samples, audio, pcm_format, 0, &nf);
+  return rc < 0 ? rc : int(nf); // (a groups-lost warning does not touch the audio: fmd_last_error has it)
+}
+
 int fmd_process_stream_fmt(fmd_decoder* d, const void* iq, int format, unsigned samples, float* audio)
 {
   if (!iq_format_ok(format))
     return fail(FMD_ERR_ARG, "fmd_process_stream_fmt: format must be one of FMD_IQ_F32, _U8, _S8, _S16 (0..3)");
-  if (!d)
-    return fail(FMD_ERR_ARG, "null decoder");
-  unsigned nf = 0;
-  int rc = fmd_batch_process_host_fmt(d->b, iq, format, 0, samples, audio, 0, &nf);
-  return rc < 0 ? rc : int(nf); // (a groups-lost warning does not touch the audio: fmd_last_error has it)
+  return fmd_process_stream_pcm(d, iq, format, samples, audio, FMD_PCM_F32);
 }
 
 int fmd_process_stream(fmd_decoder* d, const float* iq, unsigned samples, float* audio)
@@ -2772,9 +2854,13 @@ int fmd_debug_math(int what, unsigned n, const float* a, const float* b, float* 
   }
   if (!bad)
   {
-    hipLaunchKernelGGL(fmd::k_debug_math, dim3(std::min(4096u, (n + 63) / 64)), dim3(64), 0, nullptr, what,
-                       n, da.p, db.p, d0.p, d1.p, tab.p,
-                       FmdSincosTab{d.sct_inv_h, d.sct_h_hi, d.sct_h_lo}, tab256.p);
+    if (what == 8) // fmd_f32_to_s16: a kernel of its own
+      hipLaunchKernelGGL(fmd::k_debug_pcm, dim3(std::min(4096u, (n + 63) / 64)), dim3(64), 0, nullptr, n, da.p, d0.p,
+                         d1.p);
+    else
+      hipLaunchKernelGGL(fmd::k_debug_math, dim3(std::min(4096u, (n + 63) / 64)), dim3(64), 0, nullptr, what,
+                         n, da.p, db.p, d0.p, d1.p, tab.p,
+                         FmdSincosTab{d.sct_inv_h, d.sct_h_hi, d.sct_h_lo}, tab256.p);
     bad |= hipDeviceSynchronize() != hipSuccess;
     bad |= hipMemcpy(out0, d0.p, size_t(n) * 4, hipMemcpyDeviceToHost) != hipSuccess;
     bad |= hipMemcpy(out1, d1.p, size_t(n) * 4, hipMemcpyDeviceToHost) != hipSuccess;

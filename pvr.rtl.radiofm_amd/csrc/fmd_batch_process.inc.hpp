@@ -162,8 +162,14 @@ void launch_light_audio(fmd_batch* b, const fmd_batch::LightJob& j, hipStream_t 
   }
   const fmd::AudioConsts k = audio_consts(d);
   // (profiling level 1: j.tl0 / j.tl1 take the tail's own start and stop)
-  launch(fmd::k_audio_tail, dim3(CP / 64), dim3(64, 1), 0, s, j.tl0, j.tl1, b->alp[j.q].p, j.A, C, CP, k, b->st,
-         j.d_audio, j.audio_stride, unsigned(j.sq), j.call_index);
+  // the call's output format is the tail's store policy (FMD_PCM_*): nothing in front of it sees the format
+  if (j.pcm == FMD_PCM_S16)
+    launch(fmd::k_audio_tail_s16, dim3(CP / 64), dim3(64, 1), 0, s, j.tl0, j.tl1,
+           b->alp[j.q].p, j.A, C, CP, k, b->st, j.d_audio, j.audio_stride, unsigned(j.sq), j.call_index,
+           b->pcm_clip.p);
+  else
+    launch(fmd::k_audio_tail, dim3(CP / 64), dim3(64, 1), 0, s, j.tl0, j.tl1, b->alp[j.q].p, j.A, C, CP,
+           k, b->st, j.d_audio, j.audio_stride, unsigned(j.sq), j.call_index);
   // the record's RDS state is the other half's (same stream: stream order)
   if (j.events && j.status_after_rds && hipStreamWaitEvent(s, b->cev[j.es][fmd_batch::EV_RDS], 0) != hipSuccess)
     mark_failed(b, "hipStreamWaitEvent failed in front of the status record of a call");
@@ -194,6 +200,25 @@ inline bool iq_format_ok(int format)
   return format >= FMD_IQ_F32 && format <= FMD_IQ_S16;
 }
 
+enum PcmFormat
+{
+  PCM_F32 = 0, // interleaved float L, R: what ProcessStream hands its caller (FmDecode.h:135)
+  PCM_S16 = 1  // interleaved int16 L, R in host byte order, fmd_f32_to_s16 of the float sample
+};
+static_assert(PCM_F32 == FMD_PCM_F32 && PCM_S16 == FMD_PCM_S16, "the plan's formats are the C ABI's");
+
+/* bytes per audio sample */
+inline size_t pcm_esz(PcmFormat fmt)
+{
+  return fmt == PCM_S16 ? 2 : 4;
+}
+
+/* the `pcm_format` argument of the _pcm entry points: 0..1, checked before anything else is touched */
+inline bool pcm_format_ok(int format)
+{
+  return format >= FMD_PCM_F32 && format <= FMD_PCM_S16;
+}
+
 /* launch_if_stage<IN> of the call's format */
 inline int launch_if_stage_fmt(IqFormat fmt, fmd_batch* b, const void* d_iq, size_t iq_channel_stride, unsigned N,
                                unsigned pos, unsigned M, int q, hipStream_t sF, const std::function<void(int)>& mark,
@@ -213,7 +238,7 @@ inline int launch_if_stage_fmt(IqFormat fmt, fmd_batch* b, const void* d_iq, siz
 }
 
 int process_device_impl(fmd_batch* b, const void* d_iq, IqFormat fmt, size_t iq_channel_stride,
-                        unsigned samples, float* d_audio, size_t audio_channel_stride,
+                        unsigned samples, void* d_audio, PcmFormat pcm, size_t audio_channel_stride,
                         unsigned* out_floats, void* stream_)
 {
   if (!b || !d_iq || !d_audio)
@@ -800,6 +825,7 @@ int process_device_impl(fmd_batch* b, const void* d_iq, IqFormat fmt, size_t iq_
   job.sq = sq;
   job.call_index = ci;
   job.d_audio = d_audio;
+  job.pcm = pcm;
   job.audio_stride = audio_channel_stride;
   if (serial_mode || b->split_post)
   { // stage order of the reference (what the per-stage profile is keyed to), or two streams

@@ -1,6 +1,7 @@
 /*
  * fmd_k_tail.hip.h -- audio tail (k_audio_tail), status record, RDS record export, stream probes,
  * device-math test kernel, history rolls.
+ * The tail's output policies OutF32 / OutS16 (FMD_PCM_*).
  * Part of fmd_kernels.hip.h (layout, numerics contract and citations: see there and fmd_k_common.hip.h).
  */
 #pragma once
@@ -16,128 +17,97 @@ namespace fmd
 /* ------------------------------------------------------------------------------------------ */
 constexpr int AT_STEPS = 16; // rows in flight per lane (32: slower inside the pipeline, 0.83 against 0.65 ms)
 
+/* What a lane does with the frames of its channel's row: the output format of the call (FMD_PCM_*), a stateless
+ * policy like the IF kernels' InF32 / InU8 / InS8 / InS16.  The kernel holds the row pointer (frame_t* o) and the
+ * policy's few registers (State).  Every lane take()s frame u of a tile; the lanes that have a channel store() what
+ * is due behind frame u of the tile that starts at frame i0 of the row, flush() the ragged last tile of cnt frames
+ * and are done() with the call for channel c.  Recurrence, meter and status record are the kernel's and see float
+ * samples whatever the policy. */
+struct OutF32
+{ // interleaved float L, R: one frame (8 B) per store
+  using frame_t = float2;
+  struct State
+  {
+  };
+  static __device__ __forceinline__ void take(State&, unsigned, float2) {}
+  static __device__ __forceinline__ void store(float2* o, State&, unsigned i0, unsigned u, float2 f) { o[i0 + u] = f; }
+  static __device__ __forceinline__ void flush(float2*, State&, unsigned, unsigned, bool) {}
+  static __device__ __forceinline__ void done(State&, unsigned) {}
+};
+struct OutS16
+{ // interleaved int16 L, R (fmd_f32_to_s16): a frame is one 32-bit word, four of them go out as one 16-byte store.
+  // Rows start on 16-byte boundaries (pointer and stride are checked by the entry point) and a tile is 64 bytes, so
+  // every group of four is aligned; the ragged tile's last 1-3 frames take an 8- and / or a 4-byte store: nothing is
+  // written behind the call's samples.
+  using frame_t = unsigned;
+  struct State
+  {
+    unsigned w[4];      // the frames of the group of four being filled
+    unsigned nclip = 0; // samples this call saturated
+  };
+  static __device__ __forceinline__ void take(State& s, unsigned u, float2 f)
+  {
+    const unsigned l = (unsigned)fmd_f32_to_s16_count(f.x, &s.nclip) & 0xffffu;
+    const unsigned r = (unsigned)fmd_f32_to_s16_count(f.y, &s.nclip);
+    s.w[u & 3u] = l | (r << 16);
+  }
+  static __device__ __forceinline__ void store(unsigned* o, State& s, unsigned i0, unsigned u, float2)
+  {
+    if ((u & 3u) == 3u)
+      *reinterpret_cast<uint4*>(o + i0 + u - 3u) = make_uint4(s.w[0], s.w[1], s.w[2], s.w[3]);
+  }
+  static __device__ __forceinline__ void flush(unsigned* o, State& s, unsigned i0, unsigned cnt, bool active)
+  {
+    if (!active)
+      return;
+    const unsigned at = i0 + (cnt & ~3u);
+    if (cnt & 2u)
+      *reinterpret_cast<uint2*>(o + at) = make_uint2(s.w[0], s.w[1]);
+    if (cnt & 1u)
+      o[at + (cnt & 2u)] = (cnt & 2u) ? s.w[2] : s.w[0];
+  }
+  // clipped: [CP] samples saturated so far (fmd_batch_read_pcm_clipped); calls of a batch run their audio tails in
+  // order, so the lane owns its channel's word
+  static __device__ __forceinline__ void done(State& s, unsigned c, unsigned long long* __restrict__ clipped)
+  {
+    if (s.nclip)
+      clipped[c] += s.nclip;
+  }
+};
+
 /* One lane per channel.  The channel-major output ([C][stride], what ProcessStream's caller gets) is
  * written by every lane into its own channel's row, one frame (8 B) per store: the 16 stores that
  * fill a 128-byte line follow each other within ~2000 cycles and meet in the L2.  (Until round 4 the
  * frames went through an LDS tile for 64-byte segments per store; the tile's 8.7 KB kept the
  * whole-CU resampler off every CU an audio tail was on, and the stores are not what bounds a
  * lane-per-channel recurrence.)  The status record goes to device memory; k_status_publish takes it
- * to the host. */
+ * to the host.  OUT = OutS16: 16-byte stores of four frames, and the samples it saturated are added to the
+ * channel's counter, the one argument more of that form (fmd_batch_read_pcm_clipped).  The two kernels share their
+ * body as text (fmd_audio_tail.inc, like the resampler's walks): the float one has the name, the arguments and the
+ * instructions it had before there was a second format. */
 __global__ __launch_bounds__(256) void k_audio_tail(const float2* __restrict__ lp, unsigned A,
                                                    unsigned C, unsigned CP, AudioConsts k,
                                                    ChannelState st, float* __restrict__ audio,
                                                    size_t audio_stride, unsigned stereo_q,
                                                    unsigned call_index)
 {
-  __builtin_amdgcn_s_setprio(3);
-  const unsigned lane = threadIdx.x;
-  // (blockDim.y channel groups per workgroup, a wave each, nothing shared: "light_pack" -- a CU that is awake for
-  // one wave draws as much as one that is busy, so the light part's waves go four to a CU: MEASUREMENTS, round 5)
-  const unsigned c0 = (blockIdx.x * blockDim.y + threadIdx.y) * 64 + lane;
-  if (c0 - lane >= CP)
-    return;
-  const bool active = c0 < C;
-  const unsigned c = active ? c0 : C - 1;
-  float de_re = st.F(F_DE_RE)[c], de_im = st.F(F_DE_IM)[c];
-  float w1a = st.F(F_N_W1A)[c], w2a = st.F(F_N_W2A)[c], w1b = st.F(F_N_W1B)[c], w2b = st.F(F_N_W2B)[c];
-  const int stereo = st.I(I_STEREO_Q0 + (int)stereo_q)[c];
-  const float one_minus_alpha = 1.0f - k.de_alpha;
-  // cRadioReceiver::SamplesMeanRMS over the packet (RadioReceiver.cpp:584-598): float sums over
-  // the interleaved samples L0, R0, L1, R1, ... in that order
-  float vsum = 0.0f, vsumsq = 0.0f;
+  using OUT = OutF32;
+#define FMD_TAIL_DONE_ARGS
+#include "fmd_audio_tail.inc"
+#undef FMD_TAIL_DONE_ARGS
+}
 
-  auto frame = [&](float2 v) -> float2 { // v.x = stereo, v.y = mono (ProcessTwo's A, B)
-    de_re = one_minus_alpha * de_re + k.de_alpha * v.x;
-    const float s0 = de_re * 2.0f;
-    de_im = one_minus_alpha * de_im + k.de_alpha * v.y;
-    const float m0 = de_im * 2.0f;
-    const float w0a = s0 - k.n_a1 * w1a - k.n_a2 * w2a;
-    const float w0b = m0 - k.n_a1 * w1b - k.n_a2 * w2b;
-    const float s = k.n_b0 * w0a + k.n_b1 * w1a + k.n_b2 * w2a;
-    const float m = k.n_b0 * w0b + k.n_b1 * w1b + k.n_b2 * w2b;
-    w2a = w1a;
-    w1a = w0a;
-    w2b = w1b;
-    w1b = w0b;
-    const float mm = m * 0.5f;
-    const float2 o = stereo ? make_float2((m + s) * 0.5f, (m - s) * 0.5f) : make_float2(mm, mm);
-    vsum += o.x;
-    vsumsq += o.x * o.x;
-    vsum += o.y;
-    vsumsq += o.y * o.y;
-    return o;
-  };
-  float2* __restrict__ o = reinterpret_cast<float2*>(audio + (size_t)c * audio_stride);
-
-  unsigned i0 = 0;
-  // full tiles: the loads of the next tile are in flight while this one goes through the recurrence
-  // out of registers (past the last full tile: clamped rows nobody uses)
-  float2 vnext[AT_STEPS];
-#pragma unroll
-  for (unsigned u = 0; u < AT_STEPS; u++)
-    vnext[u] = lp[(size_t)min(u, A - 1) * CP + c];
-  for (; i0 + AT_STEPS <= A; i0 += AT_STEPS)
-  {
-    float2 vin[AT_STEPS];
-#pragma unroll
-    for (unsigned u = 0; u < AT_STEPS; u++)
-      vin[u] = vnext[u];
-#pragma unroll
-    for (unsigned u = 0; u < AT_STEPS; u++)
-      vnext[u] = lp[(size_t)min(i0 + AT_STEPS + u, A - 1) * CP + c];
-#pragma unroll
-    for (unsigned u = 0; u < AT_STEPS; u++)
-    {
-      const float2 f = frame(vin[u]);
-      if (active)
-        o[i0 + u] = f;
-    }
-  }
-  if (i0 < A)
-  {
-    const unsigned cnt = A - i0;
-#pragma unroll
-    for (unsigned u = 0; u < AT_STEPS; u++) // the ragged last tile is already in vnext
-      if (u < cnt)
-      {
-        const float2 f = frame(vnext[u]);
-        if (active)
-          o[i0 + u] = f;
-      }
-  }
-  if (active)
-  {
-    st.F(F_DE_RE)[c] = de_re;
-    st.F(F_DE_IM)[c] = de_im;
-    st.F(F_N_W1A)[c] = w1a;
-    st.F(F_N_W2A)[c] = w2a;
-    st.F(F_N_W1B)[c] = w1b;
-    st.F(F_N_W2B)[c] = w2b;
-    // mean = vsum / n, rms = sqrt(vsumsq / n) in float (n = floats in the packet), then
-    // m_AudioLevel = 0.95 * m_AudioLevel + 0.05 * audio_rms in double (RadioReceiver.cpp:526-528)
-    const float n = (float)(2u * A);
-    const float rms = sqrtf(vsumsq / n);
-    const float mean = vsum / n;
-    const float level = (float)(0.95 * (double)st.F(F_AUDIO_LEVEL)[c] + 0.05 * (double)rms);
-    st.F(F_AUDIO_MEAN)[c] = mean;
-    st.F(F_AUDIO_RMS)[c] = rms;
-    st.F(F_AUDIO_LEVEL)[c] = level;
-    /* The call is complete for this channel: its status record (see HostStatusWord).  The level
-     * meters are the state arrays as they stand now; the stereo flag is this call's own copy.  With
-     * overlapped calls (concurrency 2) the next call's IF / baseband meters may already be in -- the
-     * reference's status thread reads its decoder mid-call too (RadioReceiver.cpp:544-572 against
-     * :524, no common lock). */
-    unsigned* __restrict__ h = st.ds + c;
-    const size_t CPs = st.CP;
-    h[HS_IF_LEVEL * CPs] = __float_as_uint(st.F(F_IF_LEVEL)[c]);
-    h[HS_BB_MEAN * CPs] = __float_as_uint(st.F(F_BB_MEAN)[c]);
-    h[HS_BB_LEVEL * CPs] = __float_as_uint(st.F(F_BB_LEVEL)[c]);
-    h[HS_P_LEVEL * CPs] = __float_as_uint(st.F(F_P_LEVEL)[c]);
-    h[HS_STEREO * CPs] = (unsigned)stereo;
-    h[HS_AUDIO_MEAN * CPs] = __float_as_uint(mean);
-    h[HS_AUDIO_RMS * CPs] = __float_as_uint(rms);
-    h[HS_AUDIO_LEVEL * CPs] = __float_as_uint(level);
-  }
+__global__ __launch_bounds__(256) void k_audio_tail_s16(const float2* __restrict__ lp, unsigned A,
+                                                       unsigned C, unsigned CP, AudioConsts k,
+                                                       ChannelState st, int16_t* __restrict__ audio,
+                                                       size_t audio_stride, unsigned stereo_q,
+                                                       unsigned call_index,
+                                                       unsigned long long* __restrict__ clipped)
+{
+  using OUT = OutS16;
+#define FMD_TAIL_DONE_ARGS , clipped
+#include "fmd_audio_tail.inc"
+#undef FMD_TAIL_DONE_ARGS
 }
 
 /* The last kernel of a call: every channel's status record from device memory to the host's snapshot
@@ -282,6 +252,17 @@ __global__ __launch_bounds__(64) void k_debug_math(int what, unsigned n, const f
       o0[i] = r0;
       o1[i] = r1;
     }
+  }
+}
+
+/* The device build of fmd_f32_to_s16 on an array (fmd_debug_math, what = 8): the result as a float. */
+__global__ __launch_bounds__(64) void k_debug_pcm(unsigned n, const float* __restrict__ a, float* __restrict__ o0,
+                                                  float* __restrict__ o1)
+{
+  for (unsigned i = blockIdx.x * 64 + threadIdx.x; i < n; i += gridDim.x * 64)
+  {
+    o0[i] = (float)fmd_f32_to_s16(a[i]);
+    o1[i] = 0.0f;
   }
 }
 

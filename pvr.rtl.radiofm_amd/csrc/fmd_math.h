@@ -26,6 +26,7 @@
  *    significant bits) plus b*c_lo with one rounding, c_hi + c_lo = 2/255 to 2^-48; all 256
  *    inputs are checked in the CPU tests.
  *  - fmd_s8_to_f32() / fmd_s16_to_f32(): signed integer IQ, v * 2^-7 and v * 2^-15 (exact).
+ *  - fmd_f32_to_s16(): audio out as 16-bit PCM, saturate(round_half_even(x * 2^15)), NaN -> 0.
  *
  * Usable from host C (CPU sweep of the restatement) and from HIP device code.
  */
@@ -132,6 +133,27 @@ FMD_HD float fmd_s8_to_f32(int v)
 FMD_HD float fmd_s16_to_f32(int v)
 {
   return (float)v * 0x1p-15f;
+}
+
+/* Audio sample -> signed 16-bit PCM (FMD_PCM_S16): saturate(round_half_even(x * 2^15)), NaN gives 0.  x * 2^15 is
+ * exact short of overflow (then +-inf, which saturates), rintf rounds to nearest even in the default rounding mode on
+ * the host and is v_rndne_f32 on the device, and the clamp is done on the rounded FLOAT: the cast sees an integer in
+ * [-32768, 32767], so neither the host's undefined out-of-range cast nor the device's truncating one is reached.  NaN
+ * is tested for first (fmaxf(NaN, -32768.0f) is -32768).  *clipped goes up by one where the rounded value lay
+ * outside the range (NaN is not one). */
+FMD_HD int fmd_f32_to_s16_count(float x, unsigned* clipped)
+{
+  const float y = x * 32768.0f;
+  if (y != y)
+    return 0;
+  const float r = rintf(y);
+  *clipped += (r > 32767.0f) | (r < -32768.0f);
+  return (int)fminf(fmaxf(r, -32768.0f), 32767.0f);
+}
+FMD_HD int fmd_f32_to_s16(float x)
+{
+  unsigned clipped = 0;
+  return fmd_f32_to_s16_count(x, &clipped);
 }
 
 FMD_HD float fmd_atanf(float x)
