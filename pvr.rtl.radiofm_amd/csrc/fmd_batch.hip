@@ -214,8 +214,8 @@ struct fmd_batch
    * chain, two serial stages later), kOscH entries of history in front.  osc_on: every call (large batches
    * from creation; "halfband_chain" = 1 before the first call). */
   static constexpr unsigned kOscH = 64;
-  DevBuf<float2> osc_tab[4];
-  HostBuf<float2> h_osc;     // [NSLOT][kOscH + Mmax + 8]
+  DevBuf<fmd::HbOsc> osc_tab[4]; // (+ HBF_SLACK entries that are read but never used, see k_halfband_chain)
+  HostBuf<fmd::HbOsc> h_osc;     // [NSLOT][kOscH + Mmax + 8]
   Event osc_ev[8];           // [NSLOT] behind the copy out of a staging slot
   bool osc_ev_used[8] = {};
   size_t h_osc_stride = 0;
@@ -264,6 +264,7 @@ struct fmd_batch
   unsigned export_seq = 0;
   fmd::ChannelState st{};
   std::vector<fmd::HbCoef> hbcoef;
+  fmd::HbChainTaps hb_taps{}; // the same taps as k_halfband_chain takes them (three-stage chains)
 
   // host staging for the host-buffer entry point (h_audio: sized in bytes of the call's output format)
   DevBuf<float> h_iq, h_audio;
@@ -727,15 +728,29 @@ fmd_batch::HbfPlan* hbf_plan(fmd_batch* b, unsigned n_in, unsigned S)
   std::vector<fmd::HbStep> steps;
   std::vector<int> first;
   const int per = (n2 + int(S) - 1) / int(S);
+  fmd::HbTails tails{};
+  tails.tail1 = b->hbf_tail1.p;
+  tails.tail2 = b->hbf_tail2.p;
+  tails.first1 = n0 - L1H;
+  tails.first2 = n1 - L2H;
   for (int a = 0; a < n2; a += per)
   {
     first.push_back(int(steps.size()));
+    const size_t f = steps.size();
     const int e = std::min(n2, a + per);
     // what the stretch's outputs need of stages 1 and 0; the call's last stretch also computes the outputs
     // behind that (they are part of the delay lines the next call starts from)
     const bool last = e == n2;
     const int need1 = last ? n1 : 2 * (e - 1) + 1, need0 = last ? n0 : 2 * (need1 - 1) + 1;
     int d2 = a, d1 = std::max(0, 2 * a - L2H), d0 = std::max(0, 2 * d1 - L1H);
+    auto push = [&](int an, int bn, int cn) {
+      unsigned n = unsigned(an) | unsigned(bn) << 5 | unsigned(cn) << 9;
+      if (an > 0 && d0 + an > tails.first1)
+        n |= fmd::HBF_TAIL0;
+      if (bn > 0 && d1 + bn > tails.first2)
+        n |= fmd::HBF_TAIL1;
+      steps.push_back(fmd::HbStep{d0, d1, d2, n});
+    };
     while (d2 < e || d1 < need1 || d0 < need0)
     {
       const int a_hi = std::max(d0, std::min({d0 + 16, need0, 2 * d1 - L1H + RING}));
@@ -743,13 +758,31 @@ fmd_batch::HbfPlan* hbf_plan(fmd_batch* b, unsigned n_in, unsigned S)
       const int c_hi = std::max(d2, std::min({d2 + 4, e, b_hi > 0 ? (b_hi - 1) / 2 + 1 : 0}));
       if (a_hi == d0 && b_hi == d1 && c_hi == d2)
         return nullptr; // cannot happen: a stage can always move
-      steps.push_back(fmd::HbStep{d0, a_hi - d0, d1, b_hi - d1, d2, c_hi - d2, 0, 0});
+      push(a_hi - d0, b_hi - d1, c_hi - d2);
       d0 = a_hi;
       d1 = b_hi;
       d2 = c_hi;
     }
-    while ((steps.size() - size_t(first.back())) % 4) // the kernel takes a stretch's steps four at a time
-      steps.push_back(fmd::HbStep{d0, 0, d1, 0, d2, 0, 0, 0});
+    while ((steps.size() - f) % fmd::HBF_NSET) // the kernel takes a stretch's steps four at a time
+      push(0, 0, 0);
+    // what the kernel finds in a record instead of fetching or carrying it (HbStep::n): the rows to fetch during
+    // the step, the stretch's end, the way to the stretch's copy of `tails` (behind its last step)
+    const size_t g = steps.size();
+    for (size_t i = f; i < g; i++)
+    {
+      const int far = steps[std::min(i + size_t(fmd::HBF_NSET - 1), g - 1)].a_lo - steps[i].a_lo;
+      if (far < 0 || far > 63 || g - i > 1023)
+        return nullptr; // cannot happen: three steps of at most 16 outputs; a call has a few hundred steps
+      steps[i].n |= unsigned(far) << fmd::HBF_FAR_SHIFT;
+      if (steps[i].n & (fmd::HBF_TAIL0 | fmd::HBF_TAIL1))
+        steps[i].n |= unsigned(g - i) << fmd::HBF_TAILS_SHIFT;
+    }
+    steps[g - 1].n |= fmd::HBF_LAST;
+    fmd::HbStep hdr[2];
+    static_assert(sizeof(hdr) == sizeof(tails), "HbTails in the place of two records");
+    std::memcpy(hdr, &tails, sizeof(tails));
+    steps.push_back(hdr[0]);
+    steps.push_back(hdr[1]);
   }
   first.push_back(int(steps.size()));
   std::unique_ptr<fmd_batch::HbfPlan> pl(new fmd_batch::HbfPlan);
@@ -974,12 +1007,13 @@ int create_one(const fmd_params* params, unsigned n_channels, const int* tuning_
   // rows of zeros in front: the resamplers' last batch reaches below the window (k_resample: RS_B rows,
   // k_resample_ring: down to the batch border below, + one batch); 8 rows behind: its top batch
   static_assert(fmd_batch::kBrFront >= 2 * fmd::RS_B, "front rows of br");
-  bad |= b->br[0].alloc(size_t(fmd_batch::kBrFront + d.rs_order + b->Mmax + 8) * CP);
-  bad |= b->br[1].alloc(size_t(fmd_batch::kBrFront + d.rs_order + b->Mmax + 8) * CP);
+  // (HBF_SLACK: rows behind the last one that k_halfband_chain reads and never uses, here and behind mix[])
+  bad |= b->br[0].alloc(size_t(fmd_batch::kBrFront + d.rs_order + b->Mmax + 8 + fmd::HBF_SLACK) * CP);
+  bad |= b->br[1].alloc(size_t(fmd_batch::kBrFront + d.rs_order + b->Mmax + 8 + fmd::HBF_SLACK) * CP);
   if (d.hb.empty())
     return fail(FMD_ERR_ARG, "baseband rate too low for the RDS decimation chain");
-  bad |= b->mix[0].alloc(size_t(d.hb[0].len - 1 + b->Mmax) * CP);
-  bad |= b->mix[1].alloc(size_t(d.hb[0].len - 1 + b->Mmax) * CP);
+  bad |= b->mix[0].alloc(size_t(d.hb[0].len - 1 + b->Mmax + fmd::HBF_SLACK) * CP);
+  bad |= b->mix[1].alloc(size_t(d.hb[0].len - 1 + b->Mmax + fmd::HBF_SLACK) * CP);
   b->hbbuf.resize(d.hb.size() - 1);
   for (size_t s = 1; s < d.hb.size(); s++)
     bad |= b->hbbuf[s - 1].alloc(size_t(d.hb[s].len - 1 + b->hb_nmax[s]) * CP);
@@ -988,7 +1022,7 @@ int create_one(const fmd_params* params, unsigned n_channels, const int* tuning_
     bad |= b->hbf_tail1.alloc(size_t(d.hb[1].len - 1) * CP);
     bad |= b->hbf_tail2.alloc(size_t(d.hb[2].len - 1) * CP);
     for (auto& t : b->osc_tab)
-      bad |= t.alloc(size_t(fmd_batch::kOscH) + b->Mmax + 8);
+      bad |= t.alloc(size_t(fmd_batch::kOscH) + b->Mmax + 8 + fmd::HBF_SLACK);
     b->h_osc_stride = size_t(fmd_batch::kOscH) + b->Mmax + 8;
     bad |= b->h_osc.alloc(fmd_batch::NSLOT * b->h_osc_stride);
     for (auto& e : b->osc_ev)
@@ -1086,6 +1120,19 @@ int create_one(const fmd_params* params, unsigned n_channels, const int* tuning_
     for (int j = 0; 2 * j < h.len && j < 28; j++)
       hc.e[j] = hc.c[2 * j];
     b->hbcoef.push_back(hc);
+  }
+  if (d.hb.size() == 3)
+  { // per stage the even taps and then the centre tap, one stage behind the other (HbChainTaps)
+    float* t = &b->hb_taps.p[0].x;
+    int k = 0;
+    for (const auto& h : d.hb)
+    {
+      const int half = (h.len - 1) / 2;
+      for (int j = 0; j <= half && k < fmd::HBF_TAPS; j++)
+        t[k++] = h.coef[size_t(2 * j)];
+      if (k < fmd::HBF_TAPS)
+        t[k++] = h.coef[size_t(half)];
+    }
   }
   // coherent (fine-grained) host memory: the kernels' system-scope writes are visible to the host
   // without a synchronisation, whatever HIP_HOST_COHERENT says

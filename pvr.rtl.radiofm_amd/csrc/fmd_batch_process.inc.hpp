@@ -425,11 +425,14 @@ int process_device_impl(fmd_batch* b, const void* d_iq, IqFormat fmt, size_t iq_
     // submitted eight calls without ever waiting
     if (b->osc_ev_used[es])
       note(hipEventSynchronize(b->osc_ev[es]));
-    float2* h = b->h_osc.p + size_t(es) * b->h_osc_stride;
-    const float2* hp = b->h_osc.p + size_t((ci + fmd_batch::NSLOT - 1) % fmd_batch::NSLOT) * b->h_osc_stride;
-    std::memcpy(h, hp + b->lastM, fmd_batch::kOscH * sizeof(float2)); // the previous call's last entries
+    fmd::HbOsc* h = b->h_osc.p + size_t(es) * b->h_osc_stride;
+    const fmd::HbOsc* hp = b->h_osc.p + size_t((ci + fmd_batch::NSLOT - 1) % fmd_batch::NSLOT) * b->h_osc_stride;
+    std::memcpy(h, hp + b->lastM, fmd_batch::kOscH * sizeof(fmd::HbOsc)); // the previous call's last entries
     const float oc = d.rds_osc_cos, os = d.rds_osc_sin;
-    float2* o = h + fmd_batch::kOscH;
+    fmd::HbOsc* o = h + fmd_batch::kOscH;
+    // the two products of the chain's complex multiplication that are the same for every channel (HbOsc::z): IEEE
+    // multiplications by zero like the device's (a signed zero each; volatile: never folded)
+    const volatile float zero = 0.0f;
     for (unsigned t = 0; t < M; t++)
     { // the statements of k_demod_serial's MIX form (this file is compiled with -ffp-contract=off too)
       const float x = osc_re * oc - osc_im * os;
@@ -437,9 +440,11 @@ int process_device_impl(fmd_batch* b, const void* d_iq, IqFormat fmt, size_t iq_
       const float gn = float(1.95 - double(osc_re * osc_re + osc_im * osc_im));
       osc_re = gn * x;
       osc_im = gn * y;
-      o[t] = make_float2(x, y);
+      o[t].xy = make_float2(x, y);
+      o[t].z = make_float2(-(zero * y), zero * x);
     }
-    note(hipMemcpyAsync(b->osc_tab[osc_slot].p, h, (fmd_batch::kOscH + M) * sizeof(float2), hipMemcpyHostToDevice, sF));
+    note(hipMemcpyAsync(b->osc_tab[osc_slot].p, h, (fmd_batch::kOscH + M) * sizeof(fmd::HbOsc), hipMemcpyHostToDevice,
+                        sF));
     note(hipEventRecord(b->osc_ev[es], sF));
     b->osc_ev_used[es] = true;
   }
@@ -640,21 +645,20 @@ int process_device_impl(fmd_batch* b, const void* d_iq, IqFormat fmt, size_t iq_
       fmd_batch::HbfPlan* pl = hbf_pl;
       const unsigned groups = CP / 64;
       const unsigned L0H = unsigned(d.hb[0].len - 1);
-      const unsigned n0 = (hb_in[0] + 1) / 2, n1 = (n0 + 1) / 2;
       // stage 0's input rows and, without mixed rows, the oscillator entries that go with them: both
       // indexed by the stage's input row (0 = the first of its L0H history rows)
       const float2* in0 = nomix ? (const float2*)(b->brp(q) + size_t(Hbb - L0H) * CP) : (const float2*)b->mix[q].p;
-      const float2* osc = nomix ? (const float2*)(b->osc_tab[osc_slot].p + (fmd_batch::kOscH - L0H)) : nullptr;
+      const fmd::HbOsc* osc = nomix ? b->osc_tab[osc_slot].p + (fmd_batch::kOscH - L0H) : nullptr;
       auto kern = hbf_kind == 0 ? (nomix ? &fmd::k_halfband_chain<7, 11, 21, true> : &fmd::k_halfband_chain<7, 11, 21, false>)
                                 : (nomix ? &fmd::k_halfband_chain<7, 9, 17, true> : &fmd::k_halfband_chain<7, 9, 17, false>);
       launch(kern, dim3(groups, pl->S), dim3(64, 4), 0, sR, timed(6), timed(7), in0, b->hbbuf[0].p, b->hbbuf[1].p,
-             b->rdsraw[q].p, T_lpf - 1, b->hbf_tail1.p, b->hbf_tail2.p, b->hbcoef[0], b->hbcoef[1], b->hbcoef[2],
-             pl->steps.p, pl->seg_first.p, hb_in[0], n0, n1, C, CP, osc, 0u);
+             b->rdsraw[q].p + size_t(T_lpf - 1) * CP, b->hb_taps, (const fmd::HbStep*)pl->steps.p,
+             (const int*)pl->seg_first.p, C, CP, osc, 0u);
       if (nomix) // the next call's stage-0 history, should it take a launch per stage (it reads mixed rows)
         mix_tail = [&, L0H]() {
           hipLaunchKernelGGL(fmd::k_mix_tail, rgrid(L0H), rt, 0, sR,
                              (const float2*)(b->brp(q) + size_t(Hbb + hb_in[0] - L0H) * CP),
-                             (const float2*)(b->osc_tab[osc_slot].p + fmd_batch::kOscH + hb_in[0] - L0H),
+                             (const fmd::HbOsc*)(b->osc_tab[osc_slot].p + fmd_batch::kOscH + hb_in[0] - L0H),
                              b->mix[q ^ 1].p, L0H, CP);
         };
       else

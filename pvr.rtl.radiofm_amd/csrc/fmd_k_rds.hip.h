@@ -272,10 +272,20 @@ __global__ __launch_bounds__(256) void k_halfband4(const float2* __restrict__ in
 /* from where the chain's roll moves them into those history rows.  Stage 0's rows are fetched    */
 /* a step ahead (15 rows per wave and step in registers).                                         */
 /* ------------------------------------------------------------------------------------------ */
+/* An entry of the RDS oscillator's table as the chain takes it: the value (x, y) and the two products of
+ * CRDSDownConvert::ProcessData's complex multiplication that do not depend on the channel, -(0 y) and 0 x
+ * (DownConvert.cpp:464-465 with an imaginary part of zero) -- made once per call on the host, by the same IEEE
+ * multiplications. */
+struct HbOsc
+{
+  float2 xy; // the oscillator's value
+  float2 z;  // (-(0 y), 0 x)
+};
+
 /* Behind a call that wrote no mixed rows: the H rows of history the NEXT call's first half-band stage
  * finds in front of its input, should that call take a launch per stage (rows M - H .. M - 1 of
  * baseband x oscillator, as the serial stage's MIX form writes them). */
-__global__ void k_mix_tail(const float2* __restrict__ br_last, const float2* __restrict__ osc_last,
+__global__ void k_mix_tail(const float2* __restrict__ br_last, const HbOsc* __restrict__ osc_last,
                            float2* __restrict__ dst, unsigned H, unsigned CP)
 {
   const unsigned c = blockIdx.x * blockDim.x + threadIdx.x;
@@ -284,7 +294,7 @@ __global__ void k_mix_tail(const float2* __restrict__ br_last, const float2* __r
   for (unsigned r = blockIdx.y; r < H; r += gridDim.y)
   {
     const float v = br_last[(size_t)r * CP + c].x;
-    const float2 o = osc_last[r];
+    const float2 o = osc_last[r].xy;
     const float zero = 0.0f;
     dst[(size_t)r * CP + c] = make_float2((v * o.x) - (zero * o.y), (v * o.y) + (zero * o.x));
   }
@@ -292,83 +302,220 @@ __global__ void k_mix_tail(const float2* __restrict__ br_last, const float2* __r
 
 struct HbStep
 {
-  int a_lo, a_n, b_lo, b_n, c_lo, c_n; // outputs of stage 0 / 1 / 2 this step computes (first, count)
+  int a_lo, b_lo, c_lo; // the first output of stage 0 / 1 / 2 this step computes
+  unsigned n;           // how many, and what else the kernel would otherwise carry in registers or fetch (HBF_*)
+};
+/* HbStep::n: outputs of stage 0 (0 .. 16) | stage 1 (0 .. 8) << 5 | stage 2 (0 .. 4) << 9;
+ * HBF_TAIL0 / HBF_TAIL1: among them are outputs of stage 0 / 1 that belong to the next call's history;
+ * HBF_LAST: the stretch's last step; bits 16 .. 21: how far a_lo of the step HBF_NSET - 1 steps ahead (the stretch's
+ * last step at its end) lies in front of this one's -- the rows the kernel fetches during this step; bits 22 .. 31
+ * (steps with HBF_TAIL0 / HBF_TAIL1): how many records further the stretch's HbTails lies. */
+constexpr unsigned HBF_TAIL0 = 1u << 12, HBF_TAIL1 = 1u << 13, HBF_LAST = 1u << 14;
+constexpr int HBF_FAR_SHIFT = 16, HBF_TAILS_SHIFT = 22;
+/* Where the last outputs of stages 0 and 1 go: needed in a few steps at the end of a call only, so the kernel
+ * fetches it there instead of carrying it in registers.  A copy sits behind every stretch's last step, in the place
+ * of two records. */
+struct HbTails
+{
+  float2 *tail1, *tail2;
+  int first1, first2; // n0 - L1H, n1 - L2H: the first outputs of stages 0 / 1 that are history (may be negative)
   int pad0, pad1;
 };
+static_assert(sizeof(HbTails) == 2 * sizeof(HbStep), "the step list's header");
+/* A pointer that came out of memory is a generic one to the compiler, and a store through it a FLAT instruction,
+ * behind which every wait for a load is a wait for all of them: say that it points to global memory. */
+typedef float HbPair __attribute__((ext_vector_type(2)));
+__device__ __forceinline__ void hb_store_global(float2* p, float2 v)
+{
+  HbPair x;
+  x[0] = v.x;
+  x[1] = v.y;
+  *(__attribute__((address_space(1))) HbPair*)p = x;
+}
 constexpr int HBF_RING = 64; // rows per ring (power of two): >= L - 1 + two steps' outputs of the stage before
+constexpr int HBF_NSET = 4;  // a stretch's list is a multiple of this many steps; the kernel reads the list (and
+                             // fetches stage 0's rows) up to as many steps ahead: the host pads the list's end
 
-/* RR consecutive outputs of one stage from the rows `ld` delivers (row = index into the stage's input
- * with its L - 1 history rows in front: output k takes rows 2k .. 2k + L - 1).  Order of the sum as in
- * hb_group: tap 0 twice, the even taps ascending, the centre tap last (DownConvert.cpp:526-543). */
-template <int RR, int HALF, class LD>
-__device__ __forceinline__ void hb_rows(LD ld, const HbCoef& hc, float2 (&acc)[RR])
+/* Rows a group's window may reach past stage 0's last input row 2 H0 + n_in - 1: the group starts at output
+ * n0 + 4 * 3 at most (n0 = (n_in + 1) / 2: a step without outputs for stage 0 at the end of the call) and takes rows
+ * up to 2 k0 + 2 (3 + H0), so 2 n0 + 30 + 2 H0 - (2 H0 + n_in - 1) <= 32. */
+constexpr int HBF_SLACK = 32;
+
+/* The taps of the three stages as hb_rows consumes them: per stage the even taps c[0], c[2], .. c[2 HALF] and then
+ * the centre tap c[HALF] -- (H0 + 2) + (H1 + 2) + (H2 + 2) floats, 45 for the longer chain, two to a scalar
+ * register pair.  A packed multiplication takes either half of such a pair for both of its components (op_sel);
+ * the compiler does not know that and spreads every scalar factor over a pair of its own, 90 registers for 45
+ * taps, which it then parks in vector lanes.  hb_tap_mul says it with the instruction itself: 23 pairs stay in
+ * scalar registers for the whole walk. */
+constexpr int HBF_TAPS = 45;
+struct HbChainTaps
+{
+  float2 p[(HBF_TAPS + 1) / 2]; // tap j = p[j / 2].x (j even) or .y
+};
+
+/* t[j] * x, both components (v_pk_mul_f32 is two IEEE multiplications, as the compiler's own) */
+__device__ __forceinline__ float2 hb_tap_mul(const HbChainTaps& tp, int j, float2 x)
+{
+  float2 r;
+  const float2 pr = tp.p[j / 2];
+  if (j % 2 == 0)
+    asm("v_pk_mul_f32 %0, %1, %2 op_sel_hi:[1,0]" : "=v"(r) : "v"(x), "s"(pr));
+  else
+    asm("v_pk_mul_f32 %0, %1, %2 op_sel:[0,1]" : "=v"(r) : "v"(x), "s"(pr));
+  return r;
+}
+/* (v.x o.x + -(0 o.y), v.x o.y + 0 o.x): the row's first component for both halves of the product, the entry out
+ * of two scalar register pairs */
+__device__ __forceinline__ float2 hb_osc_mul(float2 v, HbOsc o)
+{
+  float2 m, r;
+  asm("v_pk_mul_f32 %0, %1, %2 op_sel_hi:[0,1]" : "=v"(m) : "v"(v), "s"(o.xy));
+  asm("v_pk_add_f32 %0, %1, %2" : "=v"(r) : "v"(m), "s"(o.z));
+  return r;
+}
+__device__ __forceinline__ float2 hb_add(float2 a, float2 b) { return make_float2(a.x + b.x, a.y + b.y); }
+
+/* RR consecutive outputs of one stage from its rows in registers: xe[u] = even row 2u of the group's window (row =
+ * index into the stage's input with its L - 1 history rows in front: output k takes rows 2k .. 2k + L - 1), xc[r] =
+ * the centre row 2r + HALF of output r; the stage's taps start at tap T of tp.  Order of the sum as in hb_group: tap
+ * 0 twice, the even taps ascending, the centre tap last (DownConvert.cpp:526-543). */
+template <int RR, int HALF, int T>
+__device__ __forceinline__ void hb_rows(const float2* xe, const float2* xc, const HbChainTaps& tp, float2 (&acc)[RR])
 {
   static_assert(HALF >= RR, "half-band group");
 #pragma unroll
   for (int u = 0; u < RR + HALF; u++) // even row u: output r takes it with tap e[u - r]
   {
-    const float2 x = ld(2 * u);
+    const float2 x = xe[u];
 #pragma unroll
     for (int r = 0; r < RR; r++)
     {
       const int j = u - r;
       if (j == 0)
       {
-        acc[r] = rf_mul(hc.e[0], x);
-        rf_acc(acc[r], hc.e[0], x);
+        acc[r] = hb_tap_mul(tp, T, x);
+        acc[r] = hb_add(acc[r], hb_tap_mul(tp, T, x));
       }
       else if (j > 0 && j <= HALF)
-        rf_acc(acc[r], hc.e[j], x);
+        acc[r] = hb_add(acc[r], hb_tap_mul(tp, T + j, x));
     }
   }
 #pragma unroll
   for (int r = 0; r < RR; r++)
-    rf_acc(acc[r], hc.c[HALF], ld(2 * r + HALF));
+    acc[r] = hb_add(acc[r], hb_tap_mul(tp, T + HALF + 1, xc[r]));
+}
+
+/* The rows of a group out of a ring whose slot row0 & 63 holds row 0 of the group's window.  One wave-uniform
+ * decision per group and step: a window that does not reach the ring's end is one address and immediate offsets;
+ * one that wraps masks each row's byte offset (an addition and a mask per read, no scalar work).  Both issue the
+ * same reads in the same order. */
+template <int RR, int HALF>
+__device__ __forceinline__ void ring_rows(const float2 (*ring)[64], int row0, unsigned lane, float2 (&xe)[RR + HALF],
+                                          float2 (&xc)[RR])
+{
+  constexpr int SPAN = 2 * (RR + HALF - 1) + 1;
+  const int slot = row0 & (HBF_RING - 1);
+  if (slot + SPAN <= HBF_RING)
+  {
+    const float2* p = &ring[slot][lane];
+#pragma unroll
+    for (int u = 0; u < RR + HALF; u++)
+      xe[u] = p[2 * u * 64];
+#pragma unroll
+    for (int r = 0; r < RR; r++)
+      xc[r] = p[(2 * r + HALF) * 64];
+  }
+  else
+  {
+    const char* base = reinterpret_cast<const char*>(&ring[0][0]);
+    const unsigned a = (unsigned)slot * 512u + lane * 8u;
+    auto at = [&](int row) { return *reinterpret_cast<const float2*>(base + ((a + (unsigned)row * 512u) & 0x7fffu)); };
+#pragma unroll
+    for (int u = 0; u < RR + HALF; u++)
+      xe[u] = at(2 * u);
+#pragma unroll
+    for (int r = 0; r < RR; r++)
+      xc[r] = at(2 * r + HALF);
+  }
+}
+
+/* RR consecutive outputs into their ring slots (first output k0, nr of them valid) */
+template <int RR>
+__device__ __forceinline__ void ring_put(float2 (*ring)[64], int k0, int nr, unsigned lane, const float2 (&acc)[RR])
+{
+  const int slot = k0 & (HBF_RING - 1);
+  if (nr == RR && slot <= HBF_RING - RR)
+  {
+    float2* p = &ring[slot][lane];
+#pragma unroll
+    for (int r = 0; r < RR; r++)
+      p[r * 64] = acc[r];
+  }
+  else
+  {
+#pragma unroll
+    for (int r = 0; r < RR; r++)
+      if (r < nr)
+        ring[(k0 + r) & (HBF_RING - 1)][lane] = acc[r];
+  }
 }
 
 /* OSC: stage 0's input rows are not the mixed rows but (baseband, -) rows, and row r meets the RDS
  * oscillator's value osc[r] on its way into the sum -- (v osc.x - 0 osc.y, v osc.y + 0 osc.x) like
- * CRDSDownConvert::ProcessData writes it (DownConvert.cpp:464-465; the input's imaginary part is zero). */
+ * CRDSDownConvert::ProcessData writes it (DownConvert.cpp:464-465; the input's imaginary part is zero):
+ * a - z is a + (-z), so with the table's two channel-independent products that is one multiplication and one
+ * addition per component.
+ *
+ * Addresses.  Stage 0's fifteen rows of a wave and step are a wave-uniform 64-bit row pointer (one product per
+ * step, the base of a buffer descriptor) plus fifteen 32-bit lane offsets that never change (lane + row * row
+ * bytes: (2 (3 + H0) + 1) rows of CP float2 stay far below 4 GB).  No row is clamped and no load is conditional (a
+ * group at the end of the input has fewer than four outputs, a step may have none for this wave; the compiler can
+ * only wait for "all but the N youngest" loads, and it knows N -- the three younger sets that are still in flight
+ * -- only if every path issues the same number): a group's window may reach up to HBF_SLACK rows past the last
+ * input row, and the host keeps as many rows behind the input buffers and entries behind the oscillator's table.
+ * What is read there only enters outputs that are not written. */
 template <int H0, int H1, int H2, bool OSC = false>
 __global__ __launch_bounds__(256) void k_halfband_chain(
     const float2* __restrict__ mix, const float2* __restrict__ hist1, const float2* __restrict__ hist2,
-    float2* __restrict__ out, unsigned Hout, float2* __restrict__ tail1, float2* __restrict__ tail2,
-    HbCoef hc0, HbCoef hc1, HbCoef hc2, const HbStep* __restrict__ steps, const int* __restrict__ seg_first,
-    unsigned n_in, unsigned n0, unsigned n1, unsigned C, unsigned CP, const float2* __restrict__ osc,
-    unsigned prio)
+    float2* __restrict__ out, HbChainTaps tp, const HbStep* __restrict__ steps, const int* __restrict__ seg_first,
+    unsigned C, unsigned CP, const HbOsc* __restrict__ osc, unsigned prio)
 {
   wave_prio(prio);
   __shared__ float2 ring1[HBF_RING][64]; // stage 0's outputs, row i0 (>= -2 H1: history) at slot i0 & 63
   __shared__ float2 ring2[HBF_RING][64]; // stage 1's outputs
   constexpr int L1H = 2 * H1, L2H = 2 * H2; // history rows of stages 1 and 2
   static_assert(L1H + 34 <= HBF_RING && L2H + 18 <= HBF_RING, "ring size");
+  static_assert((H0 + 2) + (H1 + 2) + (H2 + 2) <= HBF_TAPS, "tap table");
+  static_assert(H0 % 2 == 1 && H1 % 2 == 1 && H2 % 2 == 1, "the centre rows are odd rows");
+  constexpr int T1 = H0 + 2, T2 = T1 + H1 + 2; // the stages' first taps in tp
   const unsigned lane = threadIdx.x;
-  const int w = __builtin_amdgcn_readfirstlane((int)threadIdx.y);
+  const int w = __builtin_amdgcn_readfirstlane((int)threadIdx.y), w4 = 4 * w;
   const unsigned c0 = blockIdx.x * 64 + lane;
-  const bool live = c0 < C;
-  const unsigned c = live ? c0 : C - 1;
+  // lanes past the batch's last channel do everything that channel's lane does, its stores included (the same
+  // values to the same addresses): no lane mask anywhere
+  const unsigned c = c0 < C ? c0 : C - 1;
   const int s_begin = seg_first[blockIdx.y], s_end = seg_first[blockIdx.y + 1];
   if (s_begin >= s_end)
     return;
-  const float2* __restrict__ mp = mix + c;
-  const size_t rowstride = CP;
+  const size_t rowstride = CP; // (the history rows)
   // stage 0's input rows of this wave's group of a step: even rows 0, 2, .. 2 (3 + H0) and the four centres
-  constexpr int NA = 4 + H0 + 4;
-  constexpr int NSET = 4; // register sets: the rows of a step are fetched NSET - 1 steps ahead
-  float2 xs[NSET][NA];
-  /* Always all fifteen loads, rows clamped, never branched (a group at the end of the input has fewer
-   * than four outputs, a step may have none for this wave): the compiler can only wait for "all but the
-   * N youngest" loads, and it knows N -- the three younger sets that are still in flight -- only if every
-   * path issues the same number. */
-  auto fetch_a = [&](float2 (&x)[NA], const HbStep& st) {
-    const int k0 = st.a_lo + 4 * w;
-    const int last = 2 * H0 + (int)n_in - 1;
+  constexpr int NE = 4 + H0, NA = NE + 4;
+  constexpr int NSET = HBF_NSET; // register sets: the rows of a step are fetched NSET - 1 steps ahead
+  using Row = float2;
+  Row xs[NSET][NA];
+  const char* const gb = reinterpret_cast<const char*>(mix);
+  const unsigned row_bytes = CP * (unsigned)sizeof(float2), lane_off = c * (unsigned)sizeof(float2);
+  auto row_of = [](int i) { return i < NE ? 2 * i : 2 * (i - NE) + H0; };
+  auto fetch_a = [&](Row (&x)[NA], int a_lo) {
+    const char* rp = gb + (uint64_t)(unsigned)(2 * (a_lo + w4)) * row_bytes; // (32 x 32 -> 64 bits)
+    const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(const_cast<char*>(rp), 0, -1, 0x00020000);
 #pragma unroll
-    for (int u = 0; u < 4 + H0; u++)
-      x[u] = mp[(size_t)min(2 * k0 + 2 * u, last) * rowstride];
-#pragma unroll
-    for (int r = 0; r < 4; r++)
-      x[4 + H0 + r] = mp[(size_t)min(2 * k0 + 2 * r + H0, last) * rowstride];
+    for (int i = 0; i < NA; i++)
+    {
+      const unsigned off = lane_off + (unsigned)row_of(i) * row_bytes;
+      const auto v = __builtin_amdgcn_raw_buffer_load_b64(rs, off, 0, 0);
+      x[i] = make_float2(__uint_as_float(v[0]), __uint_as_float(v[1]));
+    }
   };
   // the rings' history (the first stretch of a call): rows -L1H .. -1 / -L2H .. -1
   {
@@ -381,83 +528,98 @@ __global__ __launch_bounds__(256) void k_halfband_chain(
         ring2[(i - L2H) & (HBF_RING - 1)][lane] = hist2[(size_t)i * rowstride + c];
 #pragma unroll
     for (int k = 0; k < NSET - 1; k++) // (a stretch's list has a multiple of NSET steps, empty ones at its end)
-      fetch_a(xs[k], steps[s_begin + k]);
+      fetch_a(xs[k], steps[s_begin + k].a_lo);
   }
   __syncthreads();
-  // the step lists travel a step ahead of their use too (a scalar load is a round trip to the L2 for a lone wave)
-  HbStep cur = steps[s_begin], far = steps[min(s_begin + NSET - 1, s_end - 1)];
-  auto step = [&](int s, float2 (&x)[NA], float2 (&xn)[NA]) { // step s out of x; step s + NSET - 1's rows into xn
+  // the step records travel a step ahead of their use too (a scalar load is a round trip to the L2 for a lone wave)
+  const HbStep* __restrict__ sp = steps + s_begin;
+  HbStep cur = sp[0];
+  auto step = [&](int k, Row (&x)[NA], Row (&xn)[NA]) { // step sp[k] out of x; the rows of step sp[k + NSET - 1] into xn
     const HbStep st = cur;
-    const HbStep cur_next = steps[min(s + 1, s_end - 1)], far_next = steps[min(s + NSET, s_end - 1)];
-    fetch_a(xn, far);
+    cur = sp[k + 1]; // (behind a stretch's last step: not a step, and not used)
+    // the wave's place in the three groups of a step out of ONE register: the compiler would keep w, 2 w and 4 w
+    int wq = w4;
+    asm volatile("" : "+s"(wq));
+    fetch_a(xn, st.a_lo + (int)((st.n >> HBF_FAR_SHIFT) & 63u));
     { // stage 0: four outputs per wave out of registers
-      const int k0 = st.a_lo + 4 * w;
-      const int nr = min(4, st.a_lo + st.a_n - k0);
+      const int k0 = st.a_lo + wq;
+      const int nr = min(4, st.a_lo + (int)(st.n & 31u) - k0);
       if (nr > 0)
       {
         float2 acc[4];
-        hb_rows<4, H0>(
-            [&](int row) {
-              const float2 v = (row & 1) ? x[4 + H0 + (row - H0) / 2] : x[row / 2];
-              if constexpr (!OSC)
-                return v;
-              else
-              {
-                const float2 o = osc[min(2 * k0 + row, 2 * H0 + (int)n_in - 1)]; // wave-uniform: a scalar load
-                const float zero = 0.0f;
-                return make_float2((v.x * o.x) - (zero * o.y), (v.x * o.y) + (zero * o.x));
-              }
-            },
-            hc0, acc);
+        if constexpr (!OSC)
+          hb_rows<4, H0, 0>(x, x + NE, tp, acc);
+        else
+        {
+          float2 xm[NA];
+          const HbOsc* __restrict__ op = osc + 2 * k0; // wave-uniform entries: scalar loads at constant offsets
 #pragma unroll
-        for (int r = 0; r < 4; r++)
-          if (r < nr)
+          for (int i = 0; i < NA; i++)
           {
-            const int i0 = k0 + r;
-            ring1[i0 & (HBF_RING - 1)][lane] = acc[r];
-            if (live && i0 >= (int)n0 - L1H)
-              tail1[(size_t)(i0 - ((int)n0 - L1H)) * rowstride + c] = acc[r];
+          {
+            xm[i] = hb_osc_mul(x[i], op[row_of(i)]);
+            if (i % 4 == 3) // four entries (sixteen scalar registers) at a time: the taps need the rest
+              __builtin_amdgcn_sched_barrier(0);
           }
+          }
+          hb_rows<4, H0, 0>(xm, xm + NE, tp, acc);
+        }
+        ring_put<4>(ring1, k0, nr, lane, acc);
+        if (st.n & HBF_TAIL0) // the stage's last L1H outputs: the next call's history
+        {
+          const HbTails t = *reinterpret_cast<const HbTails*>(sp + k + (st.n >> HBF_TAILS_SHIFT));
+#pragma unroll
+          for (int r = 0; r < 4; r++)
+            if (r < nr && k0 + r >= t.first1)
+              hb_store_global(t.tail1 + ((size_t)(k0 + r - t.first1) * CP + c), acc[r]);
+        }
       }
     }
     lds_barrier();
     { // stage 1: two outputs per wave out of ring 1 (row = output index of stage 0 + L1H)
-      const int k0 = st.b_lo + 2 * w;
-      const int nr = min(2, st.b_lo + st.b_n - k0);
+      const int k0 = st.b_lo + (wq >> 1);
+      const int nr = min(2, st.b_lo + (int)((st.n >> 5) & 15u) - k0);
       if (nr > 0)
       {
-        float2 acc[2];
-        hb_rows<2, H1>([&](int row) { return ring1[(2 * k0 + row - L1H) & (HBF_RING - 1)][lane]; }, hc1, acc);
+        float2 xe[2 + H1], xc[2], acc[2];
+        ring_rows<2, H1>(ring1, 2 * k0 - L1H, lane, xe, xc);
+        hb_rows<2, H1, T1>(xe, xc, tp, acc);
+        ring_put<2>(ring2, k0, nr, lane, acc);
+        if (st.n & HBF_TAIL1)
+        {
+          const HbTails t = *reinterpret_cast<const HbTails*>(sp + k + (st.n >> HBF_TAILS_SHIFT));
 #pragma unroll
-        for (int r = 0; r < 2; r++)
-          if (r < nr)
-          {
-            const int i1 = k0 + r;
-            ring2[i1 & (HBF_RING - 1)][lane] = acc[r];
-            if (live && i1 >= (int)n1 - L2H)
-              tail2[(size_t)(i1 - ((int)n1 - L2H)) * rowstride + c] = acc[r];
-          }
+          for (int r = 0; r < 2; r++)
+            if (r < nr && k0 + r >= t.first2)
+              hb_store_global(t.tail2 + ((size_t)(k0 + r - t.first2) * CP + c), acc[r]);
+        }
       }
     }
     lds_barrier();
     { // stage 2: one output per wave out of ring 2
-      const int k0 = st.c_lo + w;
-      if (k0 < st.c_lo + st.c_n)
+      const int k0 = st.c_lo + (wq >> 2);
+      if (k0 < st.c_lo + (int)((st.n >> 9) & 7u))
       {
-        float2 acc[1];
-        hb_rows<1, H2>([&](int row) { return ring2[(2 * k0 + row - L2H) & (HBF_RING - 1)][lane]; }, hc2, acc);
-        if (live)
-          out[(size_t)(Hout + (unsigned)k0) * rowstride + c] = acc[0];
+        float2 xe[1 + H2], xc[1], acc[1];
+        ring_rows<1, H2>(ring2, 2 * k0 - L2H, lane, xe, xc);
+        hb_rows<1, H2, T2>(xe, xc, tp, acc);
+        { // (a store by descriptor like the loads: the row's address is scalar work, the lane's part never changes)
+          char* op = reinterpret_cast<char*>(out) + (uint64_t)(unsigned)k0 * row_bytes;
+          typedef unsigned hb_u2 __attribute__((ext_vector_type(2)));
+          hb_u2 v;
+          v[0] = __float_as_uint(acc[0].x);
+          v[1] = __float_as_uint(acc[0].y);
+          __builtin_amdgcn_raw_buffer_store_b64(v, __builtin_amdgcn_make_buffer_rsrc(op, 0, -1, 0x00020000), lane_off, 0, 0);
+        }
       }
     }
-    cur = cur_next;
-    far = far_next;
+    return (st.n & HBF_LAST) != 0u;
   };
-  for (int s = s_begin; s < s_end; s += NSET)
+  for (bool last = false; !last; sp += NSET)
   {
 #pragma unroll
     for (int k = 0; k < NSET; k++)
-      step(s + k, xs[k], xs[(k + NSET - 1) % NSET]);
+      last = step(k, xs[k], xs[(k + NSET - 1) % NSET]);
   }
 }
 
