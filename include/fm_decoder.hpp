@@ -112,6 +112,21 @@ public:
   RealType GetBasebandLevel() const { return Status().baseband_level; }
   RealType GetPilotLevel() const { return Status().pilot_level; }
 
+  /* Not in the reference: the decoder's whole state as an opaque blob and back (fmd_save_state / fmd_load_state).
+   * SaveState returns the bytes written (0 on an error; blob == nullptr or cap too small: the bytes needed are in
+   * *needed where given); a decoder constructed with the same arguments continues the stream bit for bit after
+   * LoadState (true on success; fmd_last_error() says why not). */
+  size_t SaveState(void* blob, size_t cap, size_t* needed = nullptr)
+  {
+    size_t n = fmd_batch_state_size(fmd_decoder_batch(m_dec), 1);
+    if (needed)
+      *needed = n;
+    if (!blob || cap < n)
+      return 0;
+    return fmd_save_state(m_dec, blob, cap, &n) == FMD_OK ? n : 0;
+  }
+  bool LoadState(const void* blob, size_t size) { return fmd_load_state(m_dec, blob, size) == FMD_OK; }
+
 private:
   fmd_status Status() const
   {

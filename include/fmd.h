@@ -404,6 +404,67 @@ int fmd_batch_retune_channels(fmd_batch* b, const unsigned* channels, const int*
  * as before. */
 int fmd_batch_reset_channels(fmd_batch* b, const unsigned* channels, unsigned n);
 
+/* Saving and restoring a running batch; moving live channels between batches.
+ *
+ * A state blob is an opaque host buffer: a header (magic, layout version, fmd_version()'s string, a fingerprint of
+ * the geometry -- every field of fmd_params and the designed sizes, not the channel count or the device --, the
+ * batch's clock, the channel count, a checksum over everything) and per channel all that makes the next call's
+ * outputs what they are: every carried region of the device state in both buffer parities, the ring origins, the
+ * tuning shift, the status record the getters read, the audio meter, the clipped-sample counter and the host's UECP
+ * group decoder.  A blob is valid for the same build of the library on the same kind of host; anything else is
+ * refused.  NOT carried: RDS groups still queued on the device (collect them from the source before or after: they
+ * stay collectable there), profiling state, development switches, the concurrency mode, callbacks, a pending
+ * groups-lost warning.
+ *
+ * fmd_batch_state_size(b, n): bytes a blob of n channels takes (n = the batch's channel count: a whole batch, with
+ * its silent twin where retuning is enabled); 0 for a null batch.
+ *
+ * fmd_batch_save_state: synchronous; waits for every call submitted so far (also calls in flight under concurrency
+ * mode 2), writes the whole batch -- a shell's sub-batches, the silent twin, the capture map as the next call would
+ * read it, the channels per capture and the call index -- and changes nothing in it.  *written (may be null) gets
+ * the blob's size, also when cap is too small (FMD_ERR_ARG).  Edits no call has applied yet (a retune, reset,
+ * capture switch, import, a new map) give FMD_ERR_STATE.
+ *
+ * fmd_batch_load_state: synchronous; waits for the destination's calls.  Checks checksum, version, geometry,
+ * channel count (FMD_ERR_ARG) and the retune opt-in (FMD_ERR_STATE: the destination must have called
+ * fmd_batch_enable_retune exactly if the source had) before touching anything: on a refusal the destination is
+ * untouched.  Then the whole state and the clock are replaced; groups still queued in the destination and its
+ * pending edits are dropped (no loss flag); a failed batch may be loaded into, which clears the failure.  From the
+ * next call on every output -- audio in either format, getters (right after the load: the source's at the save),
+ * RDS groups with their call index, UECP frames and PS name, audio meter, clipped counts -- is bit for bit what the
+ * source would have produced for the same inputs, whatever the destination's device, concurrency mode or
+ * development switches.
+ *
+ * fmd_batch_export_channels: as save_state (same waiting rule, same format) for the n listed channels, in list
+ * order; any channels of any sub-batch, no duplicates; the source is not disturbed.
+ *
+ * fmd_batch_import_channels: an edit like a retune -- from the next call submitted, slot channels[i] IS the decoder
+ * of the blob's record i (the blob holds exactly n records; its source may have had any channel count).  Calls
+ * already submitted keep the old occupant; groups of earlier calls still go through the slot's old group decoder.
+ * Edits of one slot before one call apply in the order made (import then reset: the reset decoder; reset or retune
+ * then import: the import).  The slot keeps its capture assignment (pair the import with
+ * fmd_batch_switch_captures) and takes the record's shift.  No opt-in is needed; the host does not wait for the
+ * device.  Clock rule: a decoder continues only in a batch whose batch-uniform words (decimator and resampler
+ * positions, tuner index, ring phases, buffer parity: the call index mod 4, the RDS oscillator) equal the blob's in
+ * front of the batch's next call -- two batches created or loaded alike and fed the same sequence of call sizes
+ * always qualify.  A difference, also one of the buffer parity alone, gives FMD_ERR_STATE naming the first
+ * differing word; nothing is queued and the batch carries on.  At most eight imports may wait for one call.
+ *
+ * All: a null argument or a size below a blob's header is FMD_ERR_ARG before the HIP runtime is touched.  Same
+ * threading rule as the process calls.  fmd_save_state / fmd_load_state: the one-channel batch behind a decoder.
+ * fmd_batch_debug_state_skip (test aid): the loads and imports that follow leave one region out -- 0..7 the regions
+ * of fmd_batch_debug_restart_skip, 8 the status record, 9 the group decoder, 10 the audio meter and clip counter;
+ * -1 none (the default).  The restored channel is then not exact. */
+size_t fmd_batch_state_size(const fmd_batch* b, unsigned n_channels);
+int fmd_batch_save_state(fmd_batch* b, void* blob, size_t cap, size_t* written);
+int fmd_batch_load_state(fmd_batch* b, const void* blob, size_t size);
+int fmd_batch_export_channels(fmd_batch* b, const unsigned* channels, unsigned n, void* blob, size_t cap,
+                              size_t* written);
+int fmd_batch_import_channels(fmd_batch* b, const unsigned* channels, unsigned n, const void* blob, size_t size);
+int fmd_save_state(fmd_decoder* d, void* blob, size_t cap, size_t* written);
+int fmd_load_state(fmd_decoder* d, const void* blob, size_t size);
+int fmd_batch_debug_state_skip(fmd_batch* b, int region);
+
 /* Internal execution.  A call is four independent kernel chains (FIR -> serial demodulator ->
  * {RDS branch, audio branch}); mode selects where they run:
  *   0  all on the caller's stream, in order

@@ -145,6 +145,8 @@ EXPORTS = [
     "fmd_scan_accumulate_device_fmt", "fmd_scan_accumulate_host_fmt",
     "fmd_batch_process_device_pcm", "fmd_batch_process_host_pcm", "fmd_process_stream_pcm",
     "fmd_batch_read_pcm_clipped",
+    "fmd_batch_state_size", "fmd_batch_save_state", "fmd_batch_load_state", "fmd_batch_export_channels",
+    "fmd_batch_import_channels", "fmd_save_state", "fmd_load_state", "fmd_batch_debug_state_skip",
 ]
 
 
@@ -270,6 +272,15 @@ def lib():
         L.fmd_batch_process_host_pcm.argtypes = [vp, vp, i, C.c_size_t, u, vp, i, C.c_size_t, C.POINTER(u)]
         L.fmd_process_stream_pcm.argtypes = [vp, vp, i, u, vp, i]
         L.fmd_batch_read_pcm_clipped.argtypes = [vp, u, u, vp]
+        L.fmd_batch_state_size.restype = C.c_size_t
+        L.fmd_batch_state_size.argtypes = [vp, u]
+        L.fmd_batch_save_state.argtypes = [vp, vp, C.c_size_t, C.POINTER(C.c_size_t)]
+        L.fmd_batch_load_state.argtypes = [vp, vp, C.c_size_t]
+        L.fmd_batch_export_channels.argtypes = [vp, vp, u, vp, C.c_size_t, C.POINTER(C.c_size_t)]
+        L.fmd_batch_import_channels.argtypes = [vp, vp, u, vp, C.c_size_t]
+        L.fmd_save_state.argtypes = [vp, vp, C.c_size_t, C.POINTER(C.c_size_t)]
+        L.fmd_load_state.argtypes = [vp, vp, C.c_size_t]
+        L.fmd_batch_debug_state_skip.argtypes = [vp, i]
         _LIB = L
     return _LIB
 
@@ -444,6 +455,41 @@ class Batch:
     def debug_restart_skip(self, region):
         """Test aid: leave one carried region out of the restarts (fmd_batch_debug_restart_skip); -1 = none."""
         _check(lib().fmd_batch_debug_restart_skip(self._h, region))
+
+    def save_state(self):
+        """The whole batch as an opaque blob (fmd_batch_save_state): waits for every call submitted so far and
+        changes nothing.  load_state of it into a batch of the same geometry and channel count continues bit for
+        bit.  RDS groups still queued are not carried: collect them first."""
+        buf = np.empty(lib().fmd_batch_state_size(self._h, self.n_channels), dtype=np.uint8)
+        n = C.c_size_t()
+        _check(lib().fmd_batch_save_state(self._h, buf.ctypes.data, buf.size, C.byref(n)))
+        return buf[:n.value].tobytes()
+
+    def load_state(self, blob):
+        """Replace the whole state and the clock by a save_state blob (fmd_batch_load_state)."""
+        buf = np.frombuffer(blob, dtype=np.uint8)
+        _check(lib().fmd_batch_load_state(self._h, buf.ctypes.data if buf.size else None, buf.size))
+
+    def export_channels(self, channels):
+        """The listed channels' decoders as a blob, in list order (fmd_batch_export_channels)."""
+        ch = np.ascontiguousarray(channels, dtype=np.uint32).reshape(-1)
+        buf = np.empty(lib().fmd_batch_state_size(self._h, max(1, ch.size)), dtype=np.uint8)
+        n = C.c_size_t()
+        _check(lib().fmd_batch_export_channels(self._h, ch.ctypes.data, ch.size, buf.ctypes.data, buf.size,
+                                               C.byref(n)))
+        return buf[:n.value].tobytes()
+
+    def import_channels(self, channels, blob):
+        """From the next call on, slot channels[i] is the decoder of the blob's record i
+        (fmd_batch_import_channels); the batch's clock must equal the blob's."""
+        ch = np.ascontiguousarray(channels, dtype=np.uint32).reshape(-1)
+        buf = np.frombuffer(blob, dtype=np.uint8)
+        _check(lib().fmd_batch_import_channels(self._h, ch.ctypes.data, ch.size,
+                                               buf.ctypes.data if buf.size else None, buf.size))
+
+    def debug_state_skip(self, region):
+        """Test aid: loads and imports that follow leave one region out (fmd_batch_debug_state_skip); -1 = none."""
+        _check(lib().fmd_batch_debug_state_skip(self._h, int(region)))
 
     def min_samples(self):
         """Smallest call size this batch's geometry accepts (fmd_batch_min_samples)."""
@@ -705,6 +751,19 @@ class FmDecoder:
 
     def Reset(self):
         _check(lib().fmd_reset(self._h))
+
+    def SaveState(self):
+        """The decoder's state as an opaque blob (fmd_save_state); LoadState of it into a decoder created with the
+        same arguments continues the stream bit for bit."""
+        view = self.batch_view()
+        buf = np.empty(lib().fmd_batch_state_size(view._h, 1), dtype=np.uint8)
+        n = C.c_size_t()
+        _check(lib().fmd_save_state(self._h, buf.ctypes.data, buf.size, C.byref(n)))
+        return buf[:n.value].tobytes()
+
+    def LoadState(self, blob):
+        buf = np.frombuffer(blob, dtype=np.uint8)
+        _check(lib().fmd_load_state(self._h, buf.ctypes.data if buf.size else None, buf.size))
 
     def batch_view(self):
         """The decoder's one-channel batch as a Batch object that does not own it: for the profiling and

@@ -368,6 +368,7 @@ struct fmd_batch
     unsigned ch;
     int shift;
     bool reset; // fmd_batch_reset_channels (shift unused); else a retune to `shift`
+    int imp = -1; // >= 0: an import (fmd_batch_import_channels), entry of `imports`; the slot takes `shift`
   };
   std::vector<Edit> edits;             // pending, in the order they were made (local channel numbers)
   bool edits_pending = false;          // caller-facing batch: edits wait in `edits` here or in a sub-batch
@@ -406,6 +407,40 @@ struct fmd_batch
   HostBuf<uint2> h_walk;               // [NSLOT][C]
   Event walk_ev[NSLOT];                // behind the copy out of a staging slot
   bool walk_ev_used[NSLOT] = {};
+
+  /* Saving, loading and moving channel state (fmd_batch_save_state and its kin).  A batch
+   * with buffers of its own holds the table of its carried regions (state_tab, built on first use: the restart's
+   * regions, the status record and the clip counter), the bytes a channel takes in a payload, and the imports its
+   * next call applies: each staged in a page-locked slot (list entries, tuner rows, packed payload) that one copy
+   * takes to the device slot of the same number in front of k_channel_import.  The caller-facing batch holds the
+   * group decoders that come with imported channels until a group of their first call arrives. */
+  fmd::StateTable state_tab{};
+  int state_group[fmd::kStateMaxRegions] = {}; // the skip index each table entry belongs to (0..10)
+  size_t state_bytes = 0;              // per channel, device payload
+  int state_skip = -1;                 // fmd_batch_debug_state_skip (mutation test): a region loads / imports leave out
+  struct PendingImport
+  {
+    int slot = 0;
+    unsigned n_cols = 0, n_rows = 0;   // channels of the blob, distinct tuner rows
+    size_t rows_at = 0, payload_at = 0, bytes = 0; // layout of the staging slot
+    bool origins_live = false;
+    std::vector<fmd::StateEdit> list;  // this batch's channels of the import, sorted by channel
+  };
+  std::vector<PendingImport> imports;
+  HostBuf<char> h_imp[NSLOT];
+  DevBuf<char> d_imp[NSLOT];
+  Event imp_ev[NSLOT];                 // behind the copy out of a staging slot
+  bool imp_ev_used[NSLOT] = {};
+  unsigned imp_seq = 0;
+  struct GdecImport
+  {
+    uint32_t k = 0;                    // first call of the imported decoder
+    std::unique_ptr<fmd::GroupDecoder> g; // null: the record had none yet
+  };
+  std::map<unsigned, std::vector<GdecImport>> gdec_imports; // caller-facing batch, per channel, call order
+  // baseband samples the batch-wide oscillator sequence still lacks as history (a load from a batch that kept none:
+  // until then the serial stage writes mixed rows)
+  unsigned osc_warm = 0;
 
   // Everything else frees itself; the sub-batches and the twin run on this batch's streams: they go first.
   ~fmd_batch()
@@ -1457,6 +1492,8 @@ hipError_t order_after_calls(fmd_batch* x, hipStream_t s)
  * clears (so a reset in front of it drops out), a reset behind a retune clears the restarted state again.  So the
  * restarts (k_channel_restart) go first, then the resets (k_channel_reset).  The twin's next call goes behind a
  * restart too (it reads the twin as the previous call left it). */
+int submit_imports(fmd_batch* x, hipStream_t sF, const std::map<unsigned, int>& import_of); // fmd_batch_state.inc.hpp
+
 int submit_edits(fmd_batch* x, fmd_batch* tw, hipStream_t stream)
 {
   if (x->edits.empty())
@@ -1471,6 +1508,7 @@ int submit_edits(fmd_batch* x, fmd_batch* tw, hipStream_t stream)
   {
     bool retune = false, reset = false;
     int shift = 0;
+    int imp = -1; // the import the channel's state comes from (replaces all of it, like a retune)
   };
   std::map<unsigned, Fate> fate;
   for (const auto& e : x->edits)
@@ -1478,10 +1516,16 @@ int submit_edits(fmd_batch* x, fmd_batch* tw, hipStream_t stream)
     Fate& f = fate[e.ch];
     if (e.reset)
       f.reset = true;
+    else if (e.imp >= 0)
+      f = Fate{false, false, 0, e.imp};
     else
-      f = Fate{true, false, int((long long)(e.shift) % (long long)T)};
+      f = Fate{true, false, int((long long)(e.shift) % (long long)T), -1};
   }
   x->edits.clear();
+  std::map<unsigned, int> import_of;
+  for (const auto& [ch, f] : fate)
+    if (f.imp >= 0)
+      import_of[ch] = f.imp;
   const int slot = int(x->restart_seq++ % fmd_batch::NSLOT);
   if (x->edit_ev_used[slot]) // the copy of NSLOT edits ago (long done unless the caller never waits)
     HIPCHK(hipEventSynchronize(x->edit_ev[slot]));
@@ -1512,7 +1556,8 @@ int submit_edits(fmd_batch* x, fmd_batch* tw, hipStream_t stream)
   HIPCHK(order_after_calls(x, sF));
   if (n_rs)
     HIPCHK(order_after_calls(tw, sF));
-  HIPCHK(hipMemcpyAsync(de, he, (n_rs + n_z) * sizeof(int2), hipMemcpyHostToDevice, sF));
+  if (n_rs + n_z)
+    HIPCHK(hipMemcpyAsync(de, he, (n_rs + n_z) * sizeof(int2), hipMemcpyHostToDevice, sF));
   float2* dr = nullptr;
   if (n_rs)
   {
@@ -1533,6 +1578,9 @@ int submit_edits(fmd_batch* x, fmd_batch* tw, hipStream_t stream)
                        (const float2*)dr, (float2*)x->lut.p, T);
     HIPCHK(hipGetLastError());
   }
+  if (!x->imports.empty()) // behind the restarts, in front of the resets (a channel takes one of the two)
+    if (int rc = submit_imports(x, sF, import_of))
+      return rc;
   if (n_z)
   {
     fmd::ResetTable tab{};
@@ -1588,6 +1636,19 @@ int shift_at(fmd_batch* b, unsigned c, uint32_t ci)
  * a retune or reset of the channel (groups of earlier calls, collected late, still go through the old state). */
 void gdec_follow_edits(fmd_batch* b, unsigned c, uint32_t ci)
 {
+  // the decoders of imported channels (fmd_batch_import_channels) whose first call has come, in call order
+  if (auto it = b->gdec_imports.find(c); it != b->gdec_imports.end())
+  {
+    auto& v = it->second;
+    while (!v.empty() && v.front().k <= ci)
+    {
+      b->gdec[c] = std::move(v.front().g);
+      b->gdec_epoch[c] = std::max(b->gdec_epoch[c], v.front().k);
+      v.erase(v.begin());
+    }
+    if (v.empty())
+      b->gdec_imports.erase(it);
+  }
   uint32_t k_last = 0;
   {
     std::lock_guard<std::mutex> lk(b->log_mu);
@@ -1601,6 +1662,18 @@ void gdec_follow_edits(fmd_batch* b, unsigned c, uint32_t ci)
       b->gdec[c]->reset();
     b->gdec_epoch[c] = k_last;
   }
+}
+
+/* a retune or reset made behind an import of the same call: the imported group decoder never gets a group */
+void drop_gdec_import(fmd_batch* b, unsigned c, uint32_t k)
+{
+  auto it = b->gdec_imports.find(c);
+  if (it == b->gdec_imports.end())
+    return;
+  while (!it->second.empty() && it->second.back().k >= k)
+    it->second.pop_back();
+  if (it->second.empty())
+    b->gdec_imports.erase(it);
 }
 
 /* input rows channel numbers may name: the map's, or the cpc rule's */
@@ -2052,6 +2125,7 @@ int fmd_batch_retune_channels(fmd_batch* b, const unsigned* channels, const int*
     unsigned lc = 0;
     fmd_batch* ob = owner_of(b, channels[i], &lc);
     ob->edits.push_back(fmd_batch::Edit{lc, shifts[i], false});
+    drop_gdec_import(b, channels[i], k);
     auto& log = b->shift_log[channels[i]];
     if (!log.empty() && log.back().first == k)
       log.back().second = shifts[i];
@@ -2088,6 +2162,7 @@ int fmd_batch_reset_channels(fmd_batch* b, const unsigned* channels, unsigned n)
     unsigned lc = 0;
     fmd_batch* ob = owner_of(b, channels[i], &lc);
     ob->edits.push_back(fmd_batch::Edit{lc, 0, true});
+    drop_gdec_import(b, channels[i], k);
     // the log marks the call for the group decoder; the shift stays what it is
     auto& log = b->shift_log[channels[i]];
     if (log.empty() || log.back().first != k)
@@ -2565,7 +2640,7 @@ int fmd_batch_get_status(fmd_batch* b, unsigned channel, fmd_status* stt)
   // wrote (create, reset) is of the newest call
   const uint32_t snap = (w[fmd::HS_SEQ_END] & 0x80000000u) ? __atomic_load_n(&b->call_index, __ATOMIC_RELAXED)
                                                             : w[fmd::HS_SEQ_END];
-  const int shift = b->twin ? shift_at(b, channel, snap) : b->shifts[channel];
+  const int shift = shift_at(b, channel, snap); // (the log is empty until the first retune, reset or import)
   const float tuned = float(-shift) * b->des.fs_if / float(int(b->des.table_size));
   stt->tuning_offset = tuned + f(fmd::HS_BB_MEAN) * b->des.freq_dev;
   stt->interface_level = f(fmd::HS_IF_LEVEL);
@@ -2991,8 +3066,11 @@ int fmd_batch_debug_serial_probe(fmd_batch* b, long long* out, unsigned cap_work
   return int(wgs);
 }
 
-/* ---- cRadioReceiver's stream side (csrc/fmd_receiver.hpp) ------------------------------------ */
 } // extern "C"
+
+#include "fmd_batch_state.inc.hpp" // fmd_batch_save_state / _load_state / _export_channels / _import_channels
+
+/* ---- cRadioReceiver's stream side (csrc/fmd_receiver.hpp) ------------------------------------ */
 
 fmd_batch* fmd::Receiver::fmd_decoder_batch(fmd_decoder* d)
 {

@@ -416,7 +416,7 @@ int process_device_impl(fmd_batch* b, const void* d_iq, IqFormat fmt, size_t iq_
   // ... and then the serial stage writes no mixed rows: the chain multiplies the baseband with the
   // oscillator's sequence itself (computed here, once per batch and call, and copied over on the IF stream:
   // long before anything needs it)
-  const bool nomix = hbf_pl != nullptr && b->osc_on && b->dbg_nomix != 0;
+  const bool nomix = hbf_pl != nullptr && b->osc_on && b->dbg_nomix != 0 && b->osc_warm == 0;
   const unsigned osc_slot = ci & 3u;
   float osc_re = b->osc_re, osc_im = b->osc_im; // committed with the positions, at the end
   if (b->osc_on)
@@ -945,6 +945,7 @@ int process_device_impl(fmd_batch* b, const void* d_iq, IqFormat fmt, size_t iq_
   b->rs_pos = new_rs_pos;                           // DownConvert.cpp:230-232
   b->osc_re = osc_re;                               // DownConvert.cpp:440-441 (batch-wide, see osc_on)
   b->osc_im = osc_im;
+  b->osc_warm -= std::min(b->osc_warm, M);
   b->rds_lpf_g = (b->rds_lpf_g + R) % T_lpf;
   b->mf_g = (b->mf_g + R) % T_mf;
   b->alpf_g = (b->alpf_g + A) % T_alp;

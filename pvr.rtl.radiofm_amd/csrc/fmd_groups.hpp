@@ -131,6 +131,39 @@ public:
     }
   }
 
+  /* Everything the decoder carries from group to group, field by field (fmd_batch_save_state and its kin write
+   * and read the decoder through this; the callbacks, their user pointer and the channel number are those of
+   * the batch that constructs the decoder it reads into). */
+  template <class F>
+  void each_field(F&& f)
+  {
+    f(&seq_, sizeof(seq_));
+    f(&fill_, sizeof(fill_));
+    f(frame_, sizeof(frame_));
+    f(oda_, sizeof(oda_));
+    f(&pty_, sizeof(pty_));
+    f(&ta_tp_, sizeof(ta_tp_));
+    f(ptyn_, sizeof(ptyn_));
+    f(&ptyn_ab_, sizeof(ptyn_ab_));
+    f(&ptyn_set_, sizeof(ptyn_set_));
+    f(&di_, sizeof(di_));
+    f(&di_prev_, sizeof(di_prev_));
+    f(&di_count_, sizeof(di_count_));
+    f(&ms_, sizeof(ms_));
+    f(&ms_prev_, sizeof(ms_prev_));
+    f(ps_name_, sizeof(ps_name_));
+    f(ps_text_, sizeof(ps_text_));
+    f(&ps_set_, sizeof(ps_set_));
+    f(&pin_, sizeof(pin_));
+    f(&pi_, sizeof(pi_));
+    f(rt_, sizeof(rt_));
+    f(&rt_first_, sizeof(rt_first_));
+    f(&rt_ab_, sizeof(rt_ab_));
+    f(&rt_segreg_, sizeof(rt_segreg_));
+    f(&rt_count_, sizeof(rt_count_));
+    f(&rtp_ready_, sizeof(rtp_ready_));
+  }
+
 private:
   fmd_callbacks cb_{};
   void* user_;
