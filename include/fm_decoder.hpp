@@ -127,6 +127,17 @@ public:
   }
   bool LoadState(const void* blob, size_t size) { return fmd_load_state(m_dec, blob, size) == FMD_OK; }
 
+  /* Not in the reference: ProcessStream with the demodulated multiplex beside the audio -- the FM PLL's output at
+   * the baseband rate (m_BufferBaseband, FmDecode.cpp:433; a deviation of f Hz reads f / 30 000), *mpx_samples floats
+   * into `mpx`, a caller buffer of `samples` floats (FMD_MPX_F32).  The audio is ProcessStream's. */
+  unsigned int ProcessStreamWithMpx(const ComplexType* samples_in, unsigned int samples, float* audio, float* mpx,
+                                    unsigned int* mpx_samples)
+  {
+    const int n = fmd_process_stream_mpx(m_dec, samples_in, FMD_IQ_F32, samples, audio, FMD_PCM_F32, mpx, FMD_MPX_F32,
+                                         mpx_samples);
+    return n > 0 ? static_cast<unsigned int>(n) : 0u;
+  }
+
 private:
   fmd_status Status() const
   {

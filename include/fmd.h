@@ -91,6 +91,29 @@ extern "C" {
 #define FMD_PCM_F32 0
 #define FMD_PCM_S16 1
 
+/* The demodulated multiplex (MPX) beside the audio: the `mpx_format` argument of the _mpx entry points.  The
+ * multiplex is the FM PLL's output at the baseband rate (m_BufferBaseband, FmDecode.cpp:433) -- what an external
+ * RDS / RDS2 / DARC / SCA decoder, a modulation analyser or a stereo decoder of the caller's own consumes, and the one
+ * signal worth archiving when a station is to be decoded again later.  Mono, one row per channel, host byte order:
+ *   FMD_MPX_F32  float     the sample as is                                                       4 bytes
+ *   FMD_MPX_S16  int16_t   saturate_int16(round_half_even(x * 8192.0f)), NaN gives 0              2
+ * Content: sample t of a call's row is the float FMD_TAP_BASEBAND returns at t, bit for bit; a call delivers
+ * M = *out_mpx_samples of them, the call's baseband length, the same for every channel, known when the call returns
+ * and at most fmd_batch_max_mpx_samples(b, samples).
+ * Scale: a carrier deviation of f Hz reads x = f / 30 000 (FmDecode.cpp:254, :409-412): +-75 kHz is +-2.5.  The DC
+ * term (the tuning offset) is already removed there; nothing else is applied -- no de-emphasis, no filter, no
+ * resampling.  FMD_MPX_S16: full scale is +-4.0 = +-120 kHz, +-75 kHz is +-20 480; x * 2^13 is exact in float short
+ * of overflow, which saturates, so every sample has one right value.  There is no clip counter: a saturated sample
+ * reads 32767 or -32768, and whoever receives the row can count those.
+ * Rate: fmd_batch_mpx_rate(b) = sample_rate_if / downsample samples per second (218 181.8 at 2.4 MS/s and 11).
+ * The format is a property of the call: calls without multiplex, with FMD_MPX_F32 and with FMD_MPX_S16 may follow
+ * each other freely, and a call that asks for the multiplex leaves channel state, audio, status record, audio meter
+ * and RDS groups with the bits of the same call without it.  A channel that was reset, retuned or moved to another
+ * capture in front of the call delivers the multiplex of the decoder it now is.
+ * A format outside 0..1 is refused with FMD_ERR_ARG before anything else is looked at. */
+#define FMD_MPX_F32 0
+#define FMD_MPX_S16 1
+
 /* Constructor arguments of cFmDecoder (FmDecode.h:110-116).  table_size / if_filter_order are
  * the two internal constants BASELINE configs 3 and 5 override; 0 selects the reference
  * values 64 (FmDecode.cpp:249) and 8*downsample (FmDecode.cpp:262). */
@@ -180,6 +203,10 @@ int fmd_process_stream_fmt(fmd_decoder* d, const void* iq, int format, unsigned 
  * number of samples written (2 per audio frame) or a negative error. */
 int fmd_process_stream_pcm(fmd_decoder* d, const void* iq, int iq_format, unsigned samples, void* audio,
                            int pcm_format);
+/* ... and the multiplex beside it (FMD_MPX_*): mpx = caller buffer of `samples` elements of mpx_format (any
+ * alignment), *mpx_samples = how many were written.  mpx == NULL: fmd_process_stream_pcm. */
+int fmd_process_stream_mpx(fmd_decoder* d, const void* iq, int iq_format, unsigned samples, void* audio,
+                           int pcm_format, void* mpx, int mpx_format, unsigned* mpx_samples);
 int fmd_get_status(fmd_decoder* d, fmd_status* st);
 /* The one-channel batch behind a decoder: for the profiling / development calls below (fmd_batch_set_
  * profiling, fmd_batch_get_stage_ms, fmd_batch_debug_*); not for processing (the decoder owns it). */
@@ -208,6 +235,10 @@ int fmd_batch_streams_sharing_queue(const fmd_batch* b);
 /* smallest `samples` a process call of this batch accepts (see FMD_MIN_BLOCK) */
 unsigned fmd_batch_min_samples(const fmd_batch* b);
 unsigned fmd_batch_max_audio_floats(const fmd_batch* b, unsigned samples);
+/* multiplex samples per channel a call of `samples` delivers at most (see FMD_MPX_*): the bound for sizing rows */
+unsigned fmd_batch_max_mpx_samples(const fmd_batch* b, unsigned samples);
+/* multiplex samples per second: sample_rate_if / downsample */
+double fmd_batch_mpx_rate(const fmd_batch* b);
 
 /* Device-resident call, asynchronous on `stream` (hipStream_t, NULL = default stream).
  *  d_iq            complex<float> IQ in HBM; channel c starts at d_iq + 2*c*iq_channel_stride
@@ -245,6 +276,20 @@ int fmd_batch_process_device_pcm(fmd_batch* b, const void* d_iq, int iq_format, 
                                  unsigned samples, void* d_audio, int pcm_format, size_t audio_channel_stride,
                                  unsigned* out_samples, void* stream);
 
+/* The _pcm call with every channel's demodulated multiplex beside the audio (FMD_MPX_*): channel c's row starts
+ * mpx_channel_stride elements of mpx_format behind channel c - 1's and takes *out_mpx_samples = M samples.
+ * d_mpx == NULL makes it exactly the _pcm call (*out_mpx_samples = 0).  d_mpx must be 16-byte aligned and
+ * mpx_channel_stride a multiple of 4 elements (FMD_MPX_F32) or 8 (FMD_MPX_S16) and >= M
+ * (fmd_batch_max_mpx_samples(b, samples) always is), else FMD_ERR_ARG and the batch is exactly as it was; nothing is
+ * written behind a row's M elements.  The rows are written by a transposing kernel behind the call's serial stage,
+ * beside the resampler.  Like d_audio's rows they are complete when the call is -- in the order of `stream` with
+ * concurrency 0 and 1, behind the fmd_batch_wait[_lagged] that covers the call with concurrency 2: a caller with
+ * calls in flight gives each of them rows of its own and does not read them before that wait. */
+int fmd_batch_process_device_mpx(fmd_batch* b, const void* d_iq, int iq_format, size_t iq_channel_stride,
+                                 unsigned samples, void* d_audio, int pcm_format, size_t audio_channel_stride,
+                                 unsigned* out_samples, void* d_mpx, int mpx_format, size_t mpx_channel_stride,
+                                 unsigned* out_mpx_samples, void* stream);
+
 /* Host-buffer call: copies in, runs fmd_batch_process_device, copies audio out, collects RDS
  * groups and runs the UECP group decoder (callbacks fire here).  Synchronous.  Returns FMD_OK, a
  * negative error, or FMD_WARN_RDS_LOST (once) when groups were dropped because a queue was full:
@@ -263,6 +308,13 @@ int fmd_batch_process_host_fmt(fmd_batch* b, const void* iq, int format, size_t 
 int fmd_batch_process_host_pcm(fmd_batch* b, const void* iq, int iq_format, size_t iq_channel_stride,
                                unsigned samples, void* audio, int pcm_format, size_t audio_channel_stride,
                                unsigned* out_samples);
+
+/* ... and the multiplex (FMD_MPX_*) into host rows of any stride >= M and any alignment (rows are copied through a
+ * device staging buffer that is sized on first use); mpx == NULL: fmd_batch_process_host_pcm. */
+int fmd_batch_process_host_mpx(fmd_batch* b, const void* iq, int iq_format, size_t iq_channel_stride,
+                               unsigned samples, void* audio, int pcm_format, size_t audio_channel_stride,
+                               unsigned* out_samples, void* mpx, int mpx_format, size_t mpx_channel_stride,
+                               unsigned* out_mpx_samples);
 
 /* out[i] = the number of audio samples of channel first_channel + i (L and R counted separately) that FMD_PCM_S16
  * calls have saturated since the batch was created: samples whose rounded value lay outside [-32768, 32767] and was
@@ -473,7 +525,7 @@ int fmd_batch_debug_state_skip(fmd_batch* b, int region);
  *   2  on internal streams and the caller's stream is NOT ordered after the call: the FIR of
  *      call k+1 overlaps the serial stages of call k.  The caller must use different audio buffers
  *      for calls in flight, keep d_iq and d_audio valid, and call fmd_batch_wait[_lagged] (or
- *      collect_rds) before consuming outputs. */
+ *      collect_rds) before consuming outputs (d_mpx's rows of the _mpx call included). */
 int fmd_batch_set_concurrency(fmd_batch* b, int mode);
 /* Orders `stream` after every call submitted so far (outputs complete, inputs released). */
 int fmd_batch_wait(fmd_batch* b, void* stream);
@@ -557,7 +609,7 @@ const char* fmd_stage_name(unsigned idx);
  * table form (a = phase; out0 = sin, out1 = cos), 3 sin/cos series form, 4 mid-range division
  * a / b, 5 RTL-SDR byte -> float (a = byte value), 6 the RDS PLL's polynomial arctan2, 7 sin/cos of a
  * phase in [0, 8) with the exact float reduction (the serial stage's two NCOs), 8 float -> 16-bit PCM
- * (fmd_f32_to_s16 of a; out0 = the integer as a float). */
+ * (fmd_f32_to_s16 of a; out0 = the integer as a float), 9 float -> 16-bit multiplex (fmd_f32_to_mpx16 of a, likewise). */
 int fmd_debug_math(int what, unsigned n, const float* a, const float* b, float* out0, float* out1);
 
 /* Dev aid, only with FMD_SERIAL_PROBE=1 in the environment at batch creation: per workgroup of the
@@ -576,6 +628,11 @@ int fmd_batch_debug_stream_conflicts(fmd_batch* b, void* stream);
  * the device.  What a short run's fill and drain are made of (bench.py prints it with
  * FMD_BENCH_TIMELINE=1). */
 int fmd_batch_debug_timeline(fmd_batch* b, float* out, unsigned cap_calls);
+/* Dev aid (tools/mpx_bench.py): the first query switches the timing on and returns 0 -- from then on the multiplex
+ * writer of the batch's _mpx calls is launched with events of its own at its start and stop; later queries:
+ * out[i] = its ms in one of the last 8 such calls.  Returns the number written.  Synchronises the device.  (A batch
+ * above 8192 channels: its first sub-batch.) */
+int fmd_batch_debug_mpx_ms(fmd_batch* b, float* out, unsigned cap);
 /* Test aid: bound (in polls) of the serial stage's LDS hand-off waits for the calls that follow;
  * 0 makes every wait time out at once, which exercises the device-side error path. */
 int fmd_batch_debug_set_spin_limit(fmd_batch* b, unsigned limit);

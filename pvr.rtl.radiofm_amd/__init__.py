@@ -26,6 +26,9 @@ IQ_BYTES = {FMD_IQ_F32: 8, FMD_IQ_U8: 2, FMD_IQ_S8: 2, FMD_IQ_S16: 4}  # per IQ 
 # audio output formats (include/fmd.h FMD_PCM_*): the `pcm_format` argument of the _pcm entry points
 FMD_PCM_F32, FMD_PCM_S16 = 0, 1
 PCM_BYTES = {FMD_PCM_F32: 4, FMD_PCM_S16: 2}  # per audio sample
+# multiplex output formats (include/fmd.h FMD_MPX_*): the `mpx_format` argument of the _mpx entry points
+FMD_MPX_F32, FMD_MPX_S16 = 0, 1
+MPX_BYTES = {FMD_MPX_F32: 4, FMD_MPX_S16: 2}  # per multiplex sample
 
 TAPS = {"demod": 0, "baseband": 1, "pilot38": 2, "mono_rs": 3, "stereo_rs": 4, "rds_lpf": 5,
         "rds_pll": 6, "rds_mf": 7, "rds_sync": 8}
@@ -145,6 +148,8 @@ EXPORTS = [
     "fmd_scan_accumulate_device_fmt", "fmd_scan_accumulate_host_fmt",
     "fmd_batch_process_device_pcm", "fmd_batch_process_host_pcm", "fmd_process_stream_pcm",
     "fmd_batch_read_pcm_clipped",
+    "fmd_batch_process_device_mpx", "fmd_batch_process_host_mpx", "fmd_process_stream_mpx",
+    "fmd_batch_max_mpx_samples", "fmd_batch_mpx_rate", "fmd_batch_debug_mpx_ms",
     "fmd_batch_state_size", "fmd_batch_save_state", "fmd_batch_load_state", "fmd_batch_export_channels",
     "fmd_batch_import_channels", "fmd_save_state", "fmd_load_state", "fmd_batch_debug_state_skip",
 ]
@@ -272,6 +277,16 @@ def lib():
         L.fmd_batch_process_host_pcm.argtypes = [vp, vp, i, C.c_size_t, u, vp, i, C.c_size_t, C.POINTER(u)]
         L.fmd_process_stream_pcm.argtypes = [vp, vp, i, u, vp, i]
         L.fmd_batch_read_pcm_clipped.argtypes = [vp, u, u, vp]
+        L.fmd_batch_process_device_mpx.argtypes = [vp, vp, i, C.c_size_t, u, vp, i, C.c_size_t, C.POINTER(u),
+                                                   vp, i, C.c_size_t, C.POINTER(u), vp]
+        L.fmd_batch_process_host_mpx.argtypes = [vp, vp, i, C.c_size_t, u, vp, i, C.c_size_t, C.POINTER(u),
+                                                 vp, i, C.c_size_t, C.POINTER(u)]
+        L.fmd_process_stream_mpx.argtypes = [vp, vp, i, u, vp, i, vp, i, C.POINTER(u)]
+        L.fmd_batch_max_mpx_samples.restype = u
+        L.fmd_batch_max_mpx_samples.argtypes = [vp, u]
+        L.fmd_batch_mpx_rate.restype = C.c_double
+        L.fmd_batch_mpx_rate.argtypes = [vp]
+        L.fmd_batch_debug_mpx_ms.argtypes = [vp, vp, u]
         L.fmd_batch_state_size.restype = C.c_size_t
         L.fmd_batch_state_size.argtypes = [vp, u]
         L.fmd_batch_save_state.argtypes = [vp, vp, C.c_size_t, C.POINTER(C.c_size_t)]
@@ -329,6 +344,23 @@ def pcm_format_of(pcm):
         if fmt is not None:
             return fmt
     raise FmdError(FMD_ERR_ARG_TEXT % ("no audio format for %r (float32, int16, FMD_PCM_F32, FMD_PCM_S16)" % (pcm,)))
+
+
+def mpx_format_of(mpx):
+    """FMD_MPX_* of an `mpx=` argument: np.float32, np.int16, or the constant itself.  Anything else raises: no
+    other multiplex format exists (None is no format: the caller did not ask for the multiplex)."""
+    if isinstance(mpx, (int, np.integer)) and not isinstance(mpx, bool):
+        if int(mpx) in MPX_BYTES:
+            return int(mpx)
+    elif mpx is not None:
+        try:
+            fmt = {np.dtype(np.float32): FMD_MPX_F32, np.dtype(np.int16): FMD_MPX_S16}.get(np.dtype(mpx))
+        except TypeError:
+            fmt = None
+        if fmt is not None:
+            return fmt
+    raise FmdError(FMD_ERR_ARG_TEXT % ("no multiplex format for %r (float32, int16, FMD_MPX_F32, FMD_MPX_S16)"
+                                       % (mpx,)))
 
 
 FIR_SEQUENTIAL = 0
@@ -498,6 +530,14 @@ class Batch:
     def max_audio_floats(self, samples):
         return lib().fmd_batch_max_audio_floats(self._h, samples)
 
+    def max_mpx_samples(self, samples):
+        """Multiplex samples per channel a call of `samples` delivers at most (fmd_batch_max_mpx_samples)."""
+        return lib().fmd_batch_max_mpx_samples(self._h, samples)
+
+    def mpx_rate(self):
+        """Multiplex samples per second: sample_rate_if / downsample (fmd_batch_mpx_rate)."""
+        return lib().fmd_batch_mpx_rate(self._h)
+
     def process_host(self, iq, shared=False):
         """iq: [C, N] complex64 ([captures, N] with several channels per capture or a capture map; [N] when
         shared).  Returns [C, n_floats] float32 audio."""
@@ -536,13 +576,16 @@ class Batch:
                                                audio.ctypes.data, a_stride, C.byref(nf)))
         return audio[:, :nf.value]
 
-    def process_host_fmt(self, iq, shared=False, pcm=None):
+    def process_host_fmt(self, iq, shared=False, pcm=None, mpx=None):
         """iq: [C, N] complex64, or [C, 2N] float32 / uint8 / int8 / int16 holding I, Q, I, Q, ... (rows as for
         process_host; one row when shared); the input format is the array's dtype (fmd_batch_process_host_fmt).
         Signed integers are v * 2^-7 / v * 2^-15: the same bits as process_host on the converted block.
-        pcm=np.int16: the audio as int16 (FMD_PCM_S16, fmd_batch_process_host_pcm)."""
+        pcm=np.int16: the audio as int16 (FMD_PCM_S16, fmd_batch_process_host_pcm).
+        mpx=np.float32 / np.int16: returns (audio, multiplex), the multiplex as [C, M] rows of that format
+        (FMD_MPX_*, fmd_batch_process_host_mpx: a deviation of f Hz reads f / 30 000, times 8192 as int16)."""
         iq, fmt, per = iq_format_of(iq)
         pcm_fmt = pcm_format_of(pcm)
+        mpx_fmt = None if mpx is None else mpx_format_of(mpx)
         if shared:
             n = iq.size // per
             stride = 0
@@ -553,6 +596,14 @@ class Batch:
         a_stride = self.max_audio_floats(n)
         audio = np.zeros((self.n_channels, a_stride), dtype=np.int16 if pcm_fmt == FMD_PCM_S16 else np.float32)
         nf = C.c_uint()
+        if mpx_fmt is not None:
+            m_stride = self.max_mpx_samples(n)
+            rows = np.zeros((self.n_channels, m_stride), dtype=np.int16 if mpx_fmt == FMD_MPX_S16 else np.float32)
+            nm = C.c_uint()
+            _check(lib().fmd_batch_process_host_mpx(self._h, iq.ctypes.data, fmt, stride, n, audio.ctypes.data,
+                                                    pcm_fmt, a_stride, C.byref(nf), rows.ctypes.data, mpx_fmt,
+                                                    m_stride, C.byref(nm)))
+            return audio[:, :nf.value], rows[:, :nm.value]
         if pcm is None:
             _check(lib().fmd_batch_process_host_fmt(self._h, iq.ctypes.data, fmt, stride, n, audio.ctypes.data,
                                                     a_stride, C.byref(nf)))
@@ -562,11 +613,21 @@ class Batch:
         return audio[:, :nf.value]
 
     def process_device(self, d_iq_ptr, iq_stride, samples, d_audio_ptr, audio_stride, stream=None,
-                       u8=False, fmt=None, pcm=None):
+                       u8=False, fmt=None, pcm=None, d_mpx_ptr=None, mpx_stride=0, mpx=None):
         """iq_stride in IQ samples; u8=True: d_iq_ptr holds RTL-SDR byte pairs; fmt (FMD_IQ_*): the input format,
         through fmd_batch_process_device_fmt; pcm (np.int16 / FMD_PCM_*): the output format, audio_stride and the
-        returned count in its elements, through fmd_batch_process_device_pcm."""
+        returned count in its elements, through fmd_batch_process_device_pcm.
+        d_mpx_ptr / mpx_stride / mpx (np.float32, np.int16 / FMD_MPX_*): the call's multiplex rows, through
+        fmd_batch_process_device_mpx; returns (audio samples, multiplex samples) per channel."""
         nf = C.c_uint()
+        if d_mpx_ptr is not None or mpx is not None:
+            in_fmt = int(fmt) if fmt is not None else FMD_IQ_U8 if u8 else FMD_IQ_F32
+            nm = C.c_uint()
+            _check(lib().fmd_batch_process_device_mpx(self._h, d_iq_ptr, in_fmt, iq_stride, samples, d_audio_ptr,
+                                                      pcm_format_of(pcm), audio_stride, C.byref(nf), d_mpx_ptr,
+                                                      mpx_format_of(FMD_MPX_F32 if mpx is None else mpx), mpx_stride,
+                                                      C.byref(nm), stream))
+            return nf.value, nm.value
         if pcm is not None:
             in_fmt = int(fmt) if fmt is not None else FMD_IQ_U8 if u8 else FMD_IQ_F32
             _check(lib().fmd_batch_process_device_pcm(self._h, d_iq_ptr, in_fmt, iq_stride, samples, d_audio_ptr,
@@ -650,6 +711,13 @@ class Batch:
     def debug_set(self, key, value):
         """Development switch of this batch by name (fmd_batch_debug_set)."""
         _check(lib().fmd_batch_debug_set(self._h, key.encode(), int(value)))
+
+    def debug_mpx_ms(self):
+        """ms of the multiplex writer in the last (up to 8) _mpx calls; the first query switches the timing on and
+        returns nothing (fmd_batch_debug_mpx_ms)."""
+        buf = np.zeros(8, dtype=np.float32)
+        n = _check(lib().fmd_batch_debug_mpx_ms(self._h, buf.ctypes.data, buf.size))
+        return buf[:n].copy()
 
     def debug_host_ms(self):
         """(calls, {copy_in, submit, wait_copy_out, rds_callbacks}) mean ms of the host-buffer calls since
@@ -787,6 +855,20 @@ class FmDecoder:
         n = _check(lib().fmd_process_stream_pcm(self._h, iq.ctypes.data, FMD_IQ_F32, iq.size, audio.ctypes.data,
                                                 FMD_PCM_S16))
         return audio[:n]
+
+    def ProcessStreamWithMpx(self, samples_in, mpx=np.float32):
+        """(ProcessStream's audio, the demodulated multiplex of the block as float32 or int16): FMD_MPX_*,
+        fmd_process_stream_mpx."""
+        iq = np.ascontiguousarray(samples_in)
+        if iq.dtype != np.complex64:
+            iq = iq.astype(np.float32).view(np.complex64)
+        mpx_fmt = mpx_format_of(mpx)
+        audio = np.empty(2 * iq.size, dtype=np.float32)
+        rows = np.empty(iq.size, dtype=np.int16 if mpx_fmt == FMD_MPX_S16 else np.float32)
+        nm = C.c_uint()
+        n = _check(lib().fmd_process_stream_mpx(self._h, iq.ctypes.data, FMD_IQ_F32, iq.size, audio.ctypes.data,
+                                                FMD_PCM_F32, rows.ctypes.data, mpx_fmt, C.byref(nm)))
+        return audio[:n], rows[:nm.value]
 
     def ProcessStreamU8(self, buf):
         """ReadAsyncCB + ProcessStream (RTL_SDR_Source.cpp:196-213): buf = I,Q byte pairs."""

@@ -268,6 +268,12 @@ struct fmd_batch
 
   // host staging for the host-buffer entry point (h_audio: sized in bytes of the call's output format)
   DevBuf<float> h_iq, h_audio;
+  DevBuf<float> h_mpx; // ... and of its multiplex rows (fmd_batch_process_host_mpx: sized on first use)
+  // fmd_batch_debug_mpx_ms (its first query switches this on): the multiplex writer's own start and stop of the last
+  // NSLOT calls that asked for the multiplex (events of their own, no slot of the stage list or the timeline)
+  int dbg_mpx_timing = 0;
+  Event mpx_ev[8][2]; // [NSLOT]
+  bool mpx_ev_used[8] = {};
   // per channel: audio samples that FMD_PCM_S16 calls saturated since the batch was created (k_audio_tail<OutS16>;
   // fmd_batch_read_pcm_clipped).  It belongs to the output like the audio meter: nothing resets it.
   DevBuf<unsigned long long> pcm_clip; // [CP]
@@ -1356,6 +1362,17 @@ unsigned fmd_batch_min_samples(const fmd_batch* b)
   return b ? b->min_samples : 0;
 }
 
+unsigned fmd_batch_max_mpx_samples(const fmd_batch* b, unsigned samples)
+{
+  // the decimator's outputs of a block, with its phase at 0 (DownConvert.cpp:112,123)
+  return b ? (samples + b->des.D - 1) / b->des.D : 0;
+}
+
+double fmd_batch_mpx_rate(const fmd_batch* b)
+{
+  return b ? b->params.sample_rate_if / double(b->des.D) : 0.0;
+}
+
 unsigned fmd_batch_max_audio_floats(const fmd_batch* b, unsigned samples)
 {
   if (!b)
@@ -1756,16 +1773,17 @@ static int wait_impl(fmd_batch* b, int lag, void* stream_, bool take_lost);
  * same streams (fmd_batch::subs). */
 static int process_shell(fmd_batch* b, const void* d_iq, IqFormat fmt, size_t iq_channel_stride, unsigned samples,
                          void* d_audio, PcmFormat pcm, size_t audio_channel_stride, unsigned* out_floats,
-                         void* stream);
+                         void* stream, const MpxJob& mpx = MpxJob());
 
 /* Pending single-channel edits (retunes, resets) in front of the call; with retuning enabled, the silent twin's call
  * (zeros of the same size, on the same streams) behind it.  A batch with neither takes the plain path alone. */
 static int process_any(fmd_batch* b, const void* d_iq, IqFormat fmt, size_t iq_channel_stride, unsigned samples,
-                       void* d_audio, PcmFormat pcm, size_t audio_channel_stride, unsigned* out_floats, void* stream)
+                       void* d_audio, PcmFormat pcm, size_t audio_channel_stride, unsigned* out_floats, void* stream,
+                       const MpxJob& mpx = MpxJob())
 {
   if (!b || (!b->twin && !b->edits_pending))
     return process_shell(b, d_iq, fmt, iq_channel_stride, samples, d_audio, pcm, audio_channel_stride, out_floats,
-                         stream);
+                         stream, mpx);
   if (!d_iq || !d_audio)
     return fail(FMD_ERR_ARG, "fmd_batch_process_device: null argument");
   if (samples > FMD_MAX_BLOCK || samples < b->min_samples)
@@ -1783,10 +1801,10 @@ static int process_any(fmd_batch* b, const void* d_iq, IqFormat fmt, size_t iq_c
     }
   b->edits_pending = false;
   const int rc = process_shell(b, d_iq, fmt, iq_channel_stride, samples, d_audio, pcm, audio_channel_stride,
-                               out_floats, stream);
+                               out_floats, stream, mpx);
   if (rc != FMD_OK || !tw)
     return rc;
-  // (the twin's audio is discarded: it stays float whatever the call's format)
+  // (the twin's audio is discarded: it stays float whatever the call's format; its multiplex is not written at all)
   const int trc = process_device_impl(tw, b->twin_iq.p, IQ_F32, 0, samples, b->twin_audio.p, PCM_F32,
                                       b->twin_audio.n, nullptr, stream);
   if (trc != FMD_OK)
@@ -1795,11 +1813,12 @@ static int process_any(fmd_batch* b, const void* d_iq, IqFormat fmt, size_t iq_c
 }
 
 static int process_shell(fmd_batch* b, const void* d_iq, IqFormat fmt, size_t iq_channel_stride, unsigned samples,
-                         void* d_audio, PcmFormat pcm, size_t audio_channel_stride, unsigned* out_floats, void* stream)
+                         void* d_audio, PcmFormat pcm, size_t audio_channel_stride, unsigned* out_floats, void* stream,
+                         const MpxJob& mpx)
 {
   if (!b || b->subs.empty())
     return process_device_impl(b, d_iq, fmt, iq_channel_stride, samples, d_audio, pcm, audio_channel_stride,
-                               out_floats, stream);
+                               out_floats, stream, mpx);
   if (!d_iq || !d_audio)
     return fail(FMD_ERR_ARG, "fmd_batch_process_device: null argument");
   if (int rc = check_device_errors(b))
@@ -1816,8 +1835,11 @@ static int process_shell(fmd_batch* b, const void* d_iq, IqFormat fmt, size_t iq
     const char* iq = static_cast<const char*>(d_iq) + row0 * iq_channel_stride * esz;
     // (the sub-batch's first row: ch0 * stride elements of the output format)
     char* audio = static_cast<char*>(d_audio) + size_t(ch0) * audio_channel_stride * pcm_esz(pcm);
+    MpxJob sub_mpx = mpx; // (the sub-batch's first multiplex row, like its first audio row)
+    if (mpx.d)
+      sub_mpx.d = static_cast<char*>(mpx.d) + size_t(ch0) * mpx.stride * mpx_esz(mpx.fmt);
     const int rc = process_device_impl(sb, iq, fmt, iq_channel_stride, samples, audio, pcm, audio_channel_stride, &nf,
-                                       stream);
+                                       stream, sub_mpx);
     if (rc != FMD_OK)
     { // the first sub-batch refuses what every one of them would refuse (same geometry, same positions): nothing
       // has been submitted.  Later: part of the call is on the device -- the batch is unusable until reset.
@@ -1859,6 +1881,48 @@ int fmd_batch_process_device_pcm(fmd_batch* b, const void* d_iq, int iq_format, 
                              "and audio_channel_stride a multiple of 8 elements");
   return process_any(b, d_iq, IqFormat(iq_format), iq_channel_stride, samples, d_audio, PcmFormat(pcm_format),
                      audio_channel_stride, out_samples, stream);
+}
+
+int fmd_batch_process_device_mpx(fmd_batch* b, const void* d_iq, int iq_format, size_t iq_channel_stride,
+                                 unsigned samples, void* d_audio, int pcm_format, size_t audio_channel_stride,
+                                 unsigned* out_samples, void* d_mpx, int mpx_format, size_t mpx_channel_stride,
+                                 unsigned* out_mpx_samples, void* stream)
+{
+  if (!mpx_format_ok(mpx_format))
+    return fail(FMD_ERR_ARG, "fmd_batch_process_device_mpx: mpx_format must be FMD_MPX_F32 or FMD_MPX_S16 (0..1)");
+  if (!iq_format_ok(iq_format))
+    return fail(FMD_ERR_ARG,
+                "fmd_batch_process_device_mpx: iq_format must be one of FMD_IQ_F32, _U8, _S8, _S16 (0..3)");
+  if (!pcm_format_ok(pcm_format))
+    return fail(FMD_ERR_ARG, "fmd_batch_process_device_mpx: pcm_format must be FMD_PCM_F32 or FMD_PCM_S16 (0..1)");
+  if (!d_mpx)
+  { // no multiplex: the _pcm call, nothing else
+    if (out_mpx_samples)
+      *out_mpx_samples = 0;
+    return fmd_batch_process_device_pcm(b, d_iq, iq_format, iq_channel_stride, samples, d_audio, pcm_format,
+                                        audio_channel_stride, out_samples, stream);
+  }
+  if (!b)
+    return fail(FMD_ERR_ARG, "fmd_batch_process_device_mpx: null argument");
+  if (pcm_format == FMD_PCM_S16 && d_iq && d_audio &&
+      ((reinterpret_cast<uintptr_t>(d_audio) % 16) || (audio_channel_stride % 8)))
+    return fail(FMD_ERR_ARG, "fmd_batch_process_device_mpx: for FMD_PCM_S16 the audio pointer must be 16-byte aligned "
+                             "and audio_channel_stride a multiple of 8 elements");
+  // a lane stores 16 bytes of a row at a time: every row has to start on a 16-byte boundary, and hold the call's
+  // samples -- looked at here, in front of the pending channel edits: a refused call leaves the batch as it was
+  if ((reinterpret_cast<uintptr_t>(d_mpx) % 16) || (mpx_channel_stride % (mpx_format == FMD_MPX_S16 ? 8 : 4)))
+    return fail(FMD_ERR_ARG, "fmd_batch_process_device_mpx: the multiplex pointer must be 16-byte aligned and "
+                             "mpx_channel_stride a multiple of 4 (FMD_MPX_F32) / 8 (FMD_MPX_S16) elements");
+  if (mpx_channel_stride < next_baseband_length(b, samples))
+    return fail(FMD_ERR_ARG, "fmd_batch_process_device_mpx: mpx_channel_stride smaller than the call's baseband "
+                             "length (fmd_batch_max_mpx_samples is the bound)");
+  MpxJob mpx;
+  mpx.d = d_mpx;
+  mpx.fmt = MpxFormat(mpx_format);
+  mpx.stride = mpx_channel_stride;
+  mpx.out = out_mpx_samples;
+  return process_any(b, d_iq, IqFormat(iq_format), iq_channel_stride, samples, d_audio, PcmFormat(pcm_format),
+                     audio_channel_stride, out_samples, stream, mpx);
 }
 
 int fmd_batch_process_device_fmt(fmd_batch* b, const void* d_iq, int format, size_t iq_channel_stride,
@@ -2497,12 +2561,33 @@ int fmd_batch_export_rds_device(fmd_batch* b, int32_t* d_records, unsigned cap, 
 
 static int process_host_impl(fmd_batch* b, const void* iq, IqFormat fmt, size_t iq_channel_stride,
                              unsigned samples, void* audio, PcmFormat pcm, size_t audio_channel_stride,
-                             unsigned* out_floats)
+                             unsigned* out_floats, void* mpx = nullptr, MpxFormat mpx_fmt = MPX_F32,
+                             size_t mpx_channel_stride = 0, unsigned* out_mpx = nullptr)
 {
   if (!b || !iq || !audio)
     return fail(FMD_ERR_ARG, "fmd_batch_process_host: null argument");
   HIPCHK(hipSetDevice(b->device));
   const unsigned C = b->C;
+  // multiplex staging: rows of m_stride elements, every row on a 16-byte boundary; the caller's rows have to hold
+  // the call's samples (known before the call: nothing is submitted for a refused one)
+  MpxJob mj;
+  const size_t msz = mpx_esz(mpx_fmt);
+  const size_t m_round = mpx_fmt == MPX_S16 ? 7 : 3;
+  const size_t m_stride = (size_t(fmd_batch_max_mpx_samples(b, samples)) + m_round) & ~m_round;
+  unsigned nm = 0;
+  if (mpx)
+  {
+    if (C > 1 && mpx_channel_stride < next_baseband_length(b, samples))
+      return fail(FMD_ERR_ARG, "fmd_batch_process_host_mpx: mpx_channel_stride smaller than the call's baseband "
+                               "length (fmd_batch_max_mpx_samples is the bound)");
+    const size_t mpx_floats = m_stride * C * msz / sizeof(float);
+    if (mpx_floats > b->h_mpx.n && b->h_mpx.alloc(mpx_floats))
+      return fail(FMD_ERR_DEVICE, "staging allocation failed");
+    mj.d = b->h_mpx.p;
+    mj.fmt = mpx_fmt;
+    mj.stride = m_stride;
+    mj.out = &nm;
+  }
   const size_t esz = iq_esz(fmt); // bytes per IQ sample
   // device copy: one row per channel, rows padded to a whole pair of samples
   const size_t dev_row = (size_t(samples) + 1) / 2 * 2 * esz;
@@ -2529,7 +2614,7 @@ static int process_host_impl(fmd_batch* b, const void* iq, IqFormat fmt, size_t 
   b->host_ms[0] += ms_since(tp);
   tp = clk::now();
   unsigned nf = 0;
-  int rc = process_any(b, b->h_iq.p, fmt, dev_iq_stride, samples, b->h_audio.p, pcm, a_stride, &nf, nullptr);
+  int rc = process_any(b, b->h_iq.p, fmt, dev_iq_stride, samples, b->h_audio.p, pcm, a_stride, &nf, nullptr, mj);
   if (rc != FMD_OK)
     return rc;
   if (C > 1 && nf > audio_channel_stride)
@@ -2543,6 +2628,11 @@ static int process_host_impl(fmd_batch* b, const void* iq, IqFormat fmt, size_t 
     return rc;
   HIPCHK(hipMemcpy2D(audio, (C > 1 ? audio_channel_stride : size_t(nf)) * asz, b->h_audio.p, a_stride * asz,
                      size_t(nf) * asz, C, hipMemcpyDeviceToHost));
+  if (mpx && nm)
+    HIPCHK(hipMemcpy2D(mpx, (C > 1 ? mpx_channel_stride : size_t(nm)) * msz, b->h_mpx.p, m_stride * msz,
+                       size_t(nm) * msz, C, hipMemcpyDeviceToHost));
+  if (out_mpx)
+    *out_mpx = nm;
   b->host_ms[2] += ms_since(tp);
   tp = clk::now();
   rc = fmd_batch_collect_rds(b, nullptr, 0, 1, nullptr);
@@ -2565,6 +2655,22 @@ int fmd_batch_process_host_pcm(fmd_batch* b, const void* iq, int iq_format, size
     return fail(FMD_ERR_ARG, "fmd_batch_process_host_pcm: pcm_format must be FMD_PCM_F32 or FMD_PCM_S16 (0..1)");
   return process_host_impl(b, iq, IqFormat(iq_format), iq_channel_stride, samples, audio, PcmFormat(pcm_format),
                            audio_channel_stride, out_samples);
+}
+
+int fmd_batch_process_host_mpx(fmd_batch* b, const void* iq, int iq_format, size_t iq_channel_stride,
+                               unsigned samples, void* audio, int pcm_format, size_t audio_channel_stride,
+                               unsigned* out_samples, void* mpx, int mpx_format, size_t mpx_channel_stride,
+                               unsigned* out_mpx_samples)
+{
+  if (!mpx_format_ok(mpx_format))
+    return fail(FMD_ERR_ARG, "fmd_batch_process_host_mpx: mpx_format must be FMD_MPX_F32 or FMD_MPX_S16 (0..1)");
+  if (!iq_format_ok(iq_format))
+    return fail(FMD_ERR_ARG, "fmd_batch_process_host_mpx: iq_format must be one of FMD_IQ_F32, _U8, _S8, _S16 (0..3)");
+  if (!pcm_format_ok(pcm_format))
+    return fail(FMD_ERR_ARG, "fmd_batch_process_host_mpx: pcm_format must be FMD_PCM_F32 or FMD_PCM_S16 (0..1)");
+  return process_host_impl(b, iq, IqFormat(iq_format), iq_channel_stride, samples, audio, PcmFormat(pcm_format),
+                           audio_channel_stride, out_samples, mpx, MpxFormat(mpx_format), mpx_channel_stride,
+                           out_mpx_samples);
 }
 
 int fmd_batch_process_host_fmt(fmd_batch* b, const void* iq, int format, size_t iq_channel_stride, unsigned samples,
@@ -2922,6 +3028,23 @@ int fmd_process_stream_pcm(fmd_decoder* d, const void* iq, int iq_format, unsign
   return rc < 0 ? rc : int(nf); // (a groups-lost warning does not touch the audio: fmd_last_error has it)
 }
 
+int fmd_process_stream_mpx(fmd_decoder* d, const void* iq, int iq_format, unsigned samples, void* audio,
+                           int pcm_format, void* mpx, int mpx_format, unsigned* mpx_samples)
+{
+  if (!mpx_format_ok(mpx_format))
+    return fail(FMD_ERR_ARG, "fmd_process_stream_mpx: mpx_format must be FMD_MPX_F32 or FMD_MPX_S16 (0..1)");
+  if (!iq_format_ok(iq_format))
+    return fail(FMD_ERR_ARG, "fmd_process_stream_mpx: iq_format must be one of FMD_IQ_F32, _U8, _S8, _S16 (0..3)");
+  if (!pcm_format_ok(pcm_format))
+    return fail(FMD_ERR_ARG, "fmd_process_stream_mpx: pcm_format must be FMD_PCM_F32 or FMD_PCM_S16 (0..1)");
+  if (!d)
+    return fail(FMD_ERR_ARG, "null decoder");
+  unsigned nf = 0;
+  int rc = fmd_batch_process_host_mpx(d->b, iq, iq_format, 0, samples, audio, pcm_format, 0, &nf, mpx, mpx_format, 0,
+                                      mpx_samples);
+  return rc < 0 ? rc : int(nf);
+}
+
 int fmd_process_stream_fmt(fmd_decoder* d, const void* iq, int format, unsigned samples, float* audio)
 {
   if (!iq_format_ok(format))
@@ -2979,6 +3102,9 @@ int fmd_debug_math(int what, unsigned n, const float* a, const float* b, float* 
     if (what == 8) // fmd_f32_to_s16: a kernel of its own
       hipLaunchKernelGGL(fmd::k_debug_pcm, dim3(std::min(4096u, (n + 63) / 64)), dim3(64), 0, nullptr, n, da.p, d0.p,
                          d1.p);
+    else if (what == 9) // fmd_f32_to_mpx16
+      hipLaunchKernelGGL(fmd::k_debug_mpx, dim3(std::min(4096u, (n + 63) / 64)), dim3(64), 0, nullptr, n, da.p, d0.p,
+                         d1.p);
     else
       hipLaunchKernelGGL(fmd::k_debug_math, dim3(std::min(4096u, (n + 63) / 64)), dim3(64), 0, nullptr, what,
                          n, da.p, db.p, d0.p, d1.p, tab.p,
@@ -2988,6 +3114,33 @@ int fmd_debug_math(int what, unsigned n, const float* a, const float* b, float* 
     bad |= hipMemcpy(out1, d1.p, size_t(n) * 4, hipMemcpyDeviceToHost) != hipSuccess;
   }
   return bad ? fail(FMD_ERR_DEVICE, "fmd_debug_math: device error") : FMD_OK;
+}
+
+int fmd_batch_debug_mpx_ms(fmd_batch* b, float* out, unsigned cap)
+{
+  if (!b || !out)
+    return fail(FMD_ERR_ARG, "fmd_batch_debug_mpx_ms: null argument");
+  if (is_shell(b)) // (the first sub-batch's calls)
+    return fmd_batch_debug_mpx_ms(b->subs[0].get(), out, cap);
+  HIPCHK(hipSetDevice(b->device));
+  HIPCHK(hipDeviceSynchronize());
+  if (!b->dbg_mpx_timing)
+  { // the first query: the calls from here on are timed
+    for (int i = 0; i < fmd_batch::NSLOT; i++)
+      for (int j = 0; j < 2; j++)
+        HIPCHK(b->mpx_ev[i][j].create(hipEventDefault));
+    b->dbg_mpx_timing = 1;
+    return 0;
+  }
+  unsigned n = 0;
+  for (int i = 0; i < fmd_batch::NSLOT && n < cap; i++)
+  {
+    float ms = 0.0f;
+    if (b->mpx_ev_used[i] && hipEventElapsedTime(&ms, b->mpx_ev[i][0], b->mpx_ev[i][1]) == hipSuccess)
+      out[n++] = ms;
+  }
+  (void)hipGetLastError();
+  return int(n);
 }
 
 int fmd_batch_debug_timeline(fmd_batch* b, float* out, unsigned cap_calls)

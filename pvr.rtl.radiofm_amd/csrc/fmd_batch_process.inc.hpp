@@ -219,6 +219,44 @@ inline bool pcm_format_ok(int format)
   return format >= FMD_PCM_F32 && format <= FMD_PCM_S16;
 }
 
+enum MpxFormat
+{
+  MPX_F32 = 0, // the FM PLL's output as is (m_BufferBaseband, FmDecode.cpp:433)
+  MPX_S16 = 1  // int16 in host byte order, fmd_f32_to_mpx16 of the float sample
+};
+static_assert(MPX_F32 == FMD_MPX_F32 && MPX_S16 == FMD_MPX_S16, "the plan's formats are the C ABI's");
+
+/* bytes per multiplex sample */
+inline size_t mpx_esz(MpxFormat fmt)
+{
+  return fmt == MPX_S16 ? 2 : 4;
+}
+
+/* the `mpx_format` argument of the _mpx entry points: 0..1, checked before anything else is touched */
+inline bool mpx_format_ok(int format)
+{
+  return format >= FMD_MPX_F32 && format <= FMD_MPX_S16;
+}
+
+/* Where a call delivers its multiplex (the _mpx entry points); d == null: nowhere, the call launches what a call
+ * without the argument launches. */
+struct MpxJob
+{
+  void* d = nullptr;      // rows of the format, channel c at d + c * stride elements; 16-byte aligned
+  MpxFormat fmt = MPX_F32;
+  size_t stride = 0;      // elements; a multiple of 4 (F32) / 8 (S16), >= the call's baseband length
+  unsigned* out = nullptr; // (host, optional) samples per row: the call's baseband length
+};
+
+/* The baseband length M of the batch's next call of `samples` (DownConvert.cpp:112,123), 0 where the call would be
+ * refused for its size: what an _mpx entry point holds the row stride against before anything is submitted. */
+inline unsigned next_baseband_length(const fmd_batch* b, unsigned samples)
+{
+  const fmd_batch* x = b->subs.empty() ? b : b->subs[0].get();
+  const unsigned D = x->des.D;
+  return x->if_pos < samples ? (samples - x->if_pos + D - 1) / D : 0;
+}
+
 /* launch_if_stage<IN> of the call's format */
 inline int launch_if_stage_fmt(IqFormat fmt, fmd_batch* b, const void* d_iq, size_t iq_channel_stride, unsigned N,
                                unsigned pos, unsigned M, int q, hipStream_t sF, const std::function<void(int)>& mark,
@@ -239,7 +277,7 @@ inline int launch_if_stage_fmt(IqFormat fmt, fmd_batch* b, const void* d_iq, siz
 
 int process_device_impl(fmd_batch* b, const void* d_iq, IqFormat fmt, size_t iq_channel_stride,
                         unsigned samples, void* d_audio, PcmFormat pcm, size_t audio_channel_stride,
-                        unsigned* out_floats, void* stream_)
+                        unsigned* out_floats, void* stream_, const MpxJob& mpx = MpxJob())
 {
   if (!b || !d_iq || !d_audio)
     return fail(FMD_ERR_ARG, "fmd_batch_process_device: null argument");
@@ -326,6 +364,8 @@ int process_device_impl(fmd_batch* b, const void* d_iq, IqFormat fmt, size_t iq_
     return fail(FMD_ERR_SIZE, "block too short: no audio frame falls into it");
   if (size_t(2) * A > audio_channel_stride && C > 1)
     return fail(FMD_ERR_ARG, "audio_channel_stride smaller than the audio produced");
+  if (mpx.d && mpx.stride < M)
+    return fail(FMD_ERR_ARG, "mpx_channel_stride smaller than the call's baseband length");
 
   const unsigned T_lpf = unsigned(d.rds_lpf_taps.size());
   const unsigned T_mf = unsigned(d.rds_mf_taps.size());
@@ -797,6 +837,25 @@ int process_device_impl(fmd_batch* b, const void* d_iq, IqFormat fmt, size_t iq_
                          dim3(64, 4), 0, sA, b->brp(q), Hbb, d.rs_order, b->ktab.p, b->rs_row,
                          b->rs_margin, b->pidx.p, A, b->rs[q].p, T_alp - 1, C, CP);
     }
+    /* The multiplex rows of the call (the _mpx entry points): br[q]'s data rows, transposed, next to the resampler
+     * that reads the same rows.  In front of EV_HEAVY on every path: the next writer of these rows, the serial stage
+     * of the next-but-one call, runs behind that call's IF FIR, which waits for this EV_HEAVY; EV_ROLL behind it is
+     * what fmd_batch_wait and the caller's stream wait for. */
+    if (mpx.d)
+    {
+      const dim3 g(CP / 64, (M + fmd::MPX_T - 1) / fmd::MPX_T);
+      const float* rows = reinterpret_cast<const float*>(b->brp(q) + size_t(Hbb) * CP);
+      // (fmd_batch_debug_mpx_ms: the kernel's own start and stop, events of the call's slot)
+      const hipEvent_t t0 = b->dbg_mpx_timing ? b->mpx_ev[es][0].e : nullptr;
+      const hipEvent_t t1 = b->dbg_mpx_timing ? b->mpx_ev[es][1].e : nullptr;
+      b->mpx_ev_used[es] = t0 != nullptr;
+      if (mpx.fmt == MPX_S16)
+        launch(fmd::k_mpx_out<fmd::MpxS16>, g, dim3(256), 0, sA, t0, t1, rows, M, C, CP,
+               static_cast<int16_t*>(mpx.d), mpx.stride);
+      else
+        launch(fmd::k_mpx_out<fmd::MpxF32>, g, dim3(256), 0, sA, t0, t1, rows, M, C, CP,
+               static_cast<float*>(mpx.d), mpx.stride);
+    }
     roll_later(b->brp(q), b->brp(q ^ 1), Hbb, M); // with the low-pass's own roll, at the chain's end
     mark(6);
     if (lpf_light) // the low-pass is the light part's (launch_light_audio); the baseband rows' roll: below
@@ -955,6 +1014,8 @@ int process_device_impl(fmd_batch* b, const void* d_iq, IqFormat fmt, size_t iq_
   b->lastR = R;
   if (out_floats)
     *out_floats = 2 * A;
+  if (mpx.out)
+    *mpx.out = mpx.d ? M : 0;
   return FMD_OK;
 }
 

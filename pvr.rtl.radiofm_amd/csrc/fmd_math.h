@@ -27,6 +27,7 @@
  *    inputs are checked in the CPU tests.
  *  - fmd_s8_to_f32() / fmd_s16_to_f32(): signed integer IQ, v * 2^-7 and v * 2^-15 (exact).
  *  - fmd_f32_to_s16(): audio out as 16-bit PCM, saturate(round_half_even(x * 2^15)), NaN -> 0.
+ *  - fmd_f32_to_mpx16(): multiplex out as 16-bit integers, the same with x * 2^13.
  *
  * Usable from host C (CPU sweep of the restatement) and from HIP device code.
  */
@@ -154,6 +155,19 @@ FMD_HD int fmd_f32_to_s16(float x)
 {
   unsigned clipped = 0;
   return fmd_f32_to_s16_count(x, &clipped);
+}
+
+/* Multiplex sample -> signed 16-bit (FMD_MPX_S16): saturate(round_half_even(x * 2^13)), NaN gives 0.  The audio
+ * conversion's steps with the multiplex's scale (full scale +-4.0 = +-120 kHz of deviation): x * 2^13 is exact short of
+ * overflow, the clamp is done on the rounded float.  (fmd_f32_to_s16(x * 0.25f) gives the same integer for every
+ * float -- the extra product is inexact only below 2^-124, where both give 0 --; written out, the function is the
+ * specification.) */
+FMD_HD int fmd_f32_to_mpx16(float x)
+{
+  const float y = x * 8192.0f;
+  if (y != y)
+    return 0;
+  return (int)fminf(fmaxf(rintf(y), -32768.0f), 32767.0f);
 }
 
 FMD_HD float fmd_atanf(float x)
