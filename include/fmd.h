@@ -316,6 +316,41 @@ int fmd_batch_process_host_mpx(fmd_batch* b, const void* iq, int iq_format, size
                                unsigned* out_samples, void* mpx, int mpx_format, size_t mpx_channel_stride,
                                unsigned* out_mpx_samples);
 
+/* Which channels deliver rows.  By default a call writes one audio row and -- where it is
+ * asked for the multiplex -- one multiplex row per channel.  From the next call submitted on,
+ * fmd_batch_select_audio(b, channels, n) makes row i of d_audio channel channels[i]'s: the call writes exactly n
+ * rows, in the order of the list, and nothing else into d_audio.  fmd_batch_select_mpx does the same for d_mpx.
+ * channels == NULL restores one row per channel (then n is ignored); a list with n == 0 delivers no rows of that
+ * output: d_audio may then be NULL in the device calls and `audio` in the host calls, and a call with an empty
+ * multiplex selection is the call with d_mpx == NULL (*out_mpx_samples = 0).  The two selections are independent of
+ * each other and of the formats, which stay arguments of the call; *out_samples and *out_mpx_samples are what they
+ * were.  The pointer and stride rules hold per row as before (FMD_PCM_S16: 16-byte aligned, stride a multiple of 8;
+ * multiplex: 16-byte aligned, stride a multiple of 4 / 8 and >= M); a NULL d_audio with rows to write is
+ * FMD_ERR_ARG.  The host calls (fmd_batch_process_host_*) copy back the selected rows only: `audio` / `mpx` hold n
+ * rows.
+ *
+ * Nothing else moves: channel state, status records, the audio meter, RDS groups and the group decoders of every
+ * channel, selected or not, keep the bits of the same call without a selection -- an unselected channel's audio tail
+ * runs, only its stores and the 16-bit conversion are left out.  fmd_batch_read_pcm_clipped therefore counts
+ * delivered samples only (as FMD_PCM_F32 calls add nothing).
+ *
+ * A selection is applied in front of the next call like fmd_batch_switch_captures: nothing waits, the device is not
+ * drained, and calls already submitted (also those in flight under concurrency 2) keep the selection they were
+ * submitted with.  It belongs to the slot: resets, retunes, capture switches and imports leave it, the row delivers
+ * the decoder the slot now is; it is no part of a state blob and fmd_batch_load_state does not touch it.  Lists hold
+ * global channel numbers, also above 8192 channels.
+ *
+ * FMD_ERR_ARG, the batch as it was: a null batch (no device call is made), a channel out of range or listed twice, a
+ * list with n above the channel count, a failed batch.  FMD_ERR_STATE: the batch behind an fmd_decoder
+ * (fmd_decoder_batch), whose output the decoder owns.
+ *
+ * fmd_batch_get_audio_selection / _mpx_selection: the channels of the rows the next call writes into out[0 .. cap),
+ * returns their number (the channel count and 0, 1, 2, ... without a selection). */
+int fmd_batch_select_audio(fmd_batch* b, const unsigned* channels, unsigned n);
+int fmd_batch_select_mpx(fmd_batch* b, const unsigned* channels, unsigned n);
+int fmd_batch_get_audio_selection(fmd_batch* b, unsigned* out, unsigned cap);
+int fmd_batch_get_mpx_selection(fmd_batch* b, unsigned* out, unsigned cap);
+
 /* out[i] = the number of audio samples of channel first_channel + i (L and R counted separately) that FMD_PCM_S16
  * calls have saturated since the batch was created: samples whose rounded value lay outside [-32768, 32767] and was
  * clamped (NaN, which gives 0, is not one).  FMD_PCM_F32 calls add nothing.  Like the audio meter it belongs to the
@@ -466,7 +501,7 @@ int fmd_batch_reset_channels(fmd_batch* b, const unsigned* channels, unsigned n)
  * group decoder.  A blob is valid for the same build of the library on the same kind of host; anything else is
  * refused.  NOT carried: RDS groups still queued on the device (collect them from the source before or after: they
  * stay collectable there), profiling state, development switches, the concurrency mode, callbacks, a pending
- * groups-lost warning.
+ * groups-lost warning, the output selections (fmd_batch_select_audio / _mpx: they belong to the slot).
  *
  * fmd_batch_state_size(b, n): bytes a blob of n channels takes (n = the batch's channel count: a whole batch, with
  * its silent twin where retuning is enabled); 0 for a null batch.

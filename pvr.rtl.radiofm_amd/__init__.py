@@ -152,6 +152,7 @@ EXPORTS = [
     "fmd_batch_max_mpx_samples", "fmd_batch_mpx_rate", "fmd_batch_debug_mpx_ms",
     "fmd_batch_state_size", "fmd_batch_save_state", "fmd_batch_load_state", "fmd_batch_export_channels",
     "fmd_batch_import_channels", "fmd_save_state", "fmd_load_state", "fmd_batch_debug_state_skip",
+    "fmd_batch_select_audio", "fmd_batch_select_mpx", "fmd_batch_get_audio_selection", "fmd_batch_get_mpx_selection",
 ]
 
 
@@ -296,6 +297,10 @@ def lib():
         L.fmd_save_state.argtypes = [vp, vp, C.c_size_t, C.POINTER(C.c_size_t)]
         L.fmd_load_state.argtypes = [vp, vp, C.c_size_t]
         L.fmd_batch_debug_state_skip.argtypes = [vp, i]
+        L.fmd_batch_select_audio.argtypes = [vp, vp, u]
+        L.fmd_batch_select_mpx.argtypes = [vp, vp, u]
+        L.fmd_batch_get_audio_selection.argtypes = [vp, vp, u]
+        L.fmd_batch_get_mpx_selection.argtypes = [vp, vp, u]
         _LIB = L
     return _LIB
 
@@ -523,6 +528,52 @@ class Batch:
         """Test aid: loads and imports that follow leave one region out (fmd_batch_debug_state_skip); -1 = none."""
         _check(lib().fmd_batch_debug_state_skip(self._h, int(region)))
 
+    def _selection_list(self, channels, what):
+        """The list of a select_* call as uint32, refused here like the library refuses it (before any device call)."""
+        ch = np.asarray(channels, dtype=np.int64).reshape(-1)
+        if ch.size > self.n_channels:
+            raise FmdError(FMD_ERR_ARG_TEXT % ("%s: more rows than the batch has channels" % what))
+        if ch.size and (ch.min() < 0 or ch.max() >= self.n_channels):
+            raise FmdError(FMD_ERR_ARG_TEXT % ("%s: a channel is out of range" % what))
+        if np.unique(ch).size != ch.size:
+            raise FmdError(FMD_ERR_ARG_TEXT % ("%s: a channel is listed twice" % what))
+        return np.ascontiguousarray(ch, dtype=np.uint32)
+
+    def select_audio(self, channels):
+        """From the next call on, audio row i is channel channels[i] and the call writes len(channels) rows
+        (fmd_batch_select_audio); None: one row per channel again; an empty list: no audio rows."""
+        if channels is None:
+            _check(lib().fmd_batch_select_audio(self._h, None, 0))
+            return
+        ch = self._selection_list(channels, "select_audio")
+        keep = ch if ch.size else np.zeros(1, dtype=np.uint32)  # (an empty list is still a list: a non-null pointer)
+        _check(lib().fmd_batch_select_audio(self._h, keep.ctypes.data, ch.size))
+
+    def select_mpx(self, channels):
+        """The same for the multiplex rows (fmd_batch_select_mpx)."""
+        if channels is None:
+            _check(lib().fmd_batch_select_mpx(self._h, None, 0))
+            return
+        ch = self._selection_list(channels, "select_mpx")
+        keep = ch if ch.size else np.zeros(1, dtype=np.uint32)
+        _check(lib().fmd_batch_select_mpx(self._h, keep.ctypes.data, ch.size))
+
+    def audio_selection(self):
+        """uint32[n]: the channels of the audio rows the next call writes (fmd_batch_get_audio_selection)."""
+        out = np.zeros(self.n_channels, dtype=np.uint32)
+        n = _check(lib().fmd_batch_get_audio_selection(self._h, out.ctypes.data, out.size))
+        return out[:n].copy()
+
+    def mpx_selection(self):
+        """uint32[n]: the channels of the multiplex rows the next call writes (fmd_batch_get_mpx_selection)."""
+        out = np.zeros(self.n_channels, dtype=np.uint32)
+        n = _check(lib().fmd_batch_get_mpx_selection(self._h, out.ctypes.data, out.size))
+        return out[:n].copy()
+
+    def _rows(self, mpx=False):
+        fn = lib().fmd_batch_get_mpx_selection if mpx else lib().fmd_batch_get_audio_selection
+        return _check(fn(self._h, None, 0))
+
     def min_samples(self):
         """Smallest call size this batch's geometry accepts (fmd_batch_min_samples)."""
         return lib().fmd_batch_min_samples(self._h)
@@ -552,7 +603,7 @@ class Batch:
             n = iq.shape[1]
             stride = n
         a_stride = self.max_audio_floats(n)
-        audio = np.zeros((self.n_channels, a_stride), dtype=np.float32)
+        audio = np.zeros((self._rows(), a_stride), dtype=np.float32)
         nf = C.c_uint()
         _check(lib().fmd_batch_process_host(self._h, iq.ctypes.data, stride, n, audio.ctypes.data,
                                             a_stride, C.byref(nf)))
@@ -570,7 +621,7 @@ class Batch:
             n = iq_u8.shape[1] // 2
             stride = n
         a_stride = self.max_audio_floats(n)
-        audio = np.zeros((self.n_channels, a_stride), dtype=np.float32)
+        audio = np.zeros((self._rows(), a_stride), dtype=np.float32)
         nf = C.c_uint()
         _check(lib().fmd_batch_process_host_u8(self._h, iq_u8.ctypes.data, stride, n,
                                                audio.ctypes.data, a_stride, C.byref(nf)))
@@ -580,6 +631,7 @@ class Batch:
         """iq: [C, N] complex64, or [C, 2N] float32 / uint8 / int8 / int16 holding I, Q, I, Q, ... (rows as for
         process_host; one row when shared); the input format is the array's dtype (fmd_batch_process_host_fmt).
         Signed integers are v * 2^-7 / v * 2^-15: the same bits as process_host on the converted block.
+        With a selection (select_audio / select_mpx) the arrays hold its rows, in its order.
         pcm=np.int16: the audio as int16 (FMD_PCM_S16, fmd_batch_process_host_pcm).
         mpx=np.float32 / np.int16: returns (audio, multiplex), the multiplex as [C, M] rows of that format
         (FMD_MPX_*, fmd_batch_process_host_mpx: a deviation of f Hz reads f / 30 000, times 8192 as int16)."""
@@ -594,11 +646,11 @@ class Batch:
             n = iq.shape[1] // per
             stride = n
         a_stride = self.max_audio_floats(n)
-        audio = np.zeros((self.n_channels, a_stride), dtype=np.int16 if pcm_fmt == FMD_PCM_S16 else np.float32)
+        audio = np.zeros((self._rows(), a_stride), dtype=np.int16 if pcm_fmt == FMD_PCM_S16 else np.float32)
         nf = C.c_uint()
         if mpx_fmt is not None:
             m_stride = self.max_mpx_samples(n)
-            rows = np.zeros((self.n_channels, m_stride), dtype=np.int16 if mpx_fmt == FMD_MPX_S16 else np.float32)
+            rows = np.zeros((self._rows(mpx=True), m_stride), dtype=np.int16 if mpx_fmt == FMD_MPX_S16 else np.float32)
             nm = C.c_uint()
             _check(lib().fmd_batch_process_host_mpx(self._h, iq.ctypes.data, fmt, stride, n, audio.ctypes.data,
                                                     pcm_fmt, a_stride, C.byref(nf), rows.ctypes.data, mpx_fmt,

@@ -2,6 +2,10 @@
  * fmd_audio_tail.inc -- the body of the audio tail kernels (fmd_k_tail.hip.h: k_audio_tail, k_audio_tail_s16), one
  * text for every output format.  The including kernel names its output policy OUT (OutF32 / OutS16) and defines
  * FMD_TAIL_DONE_ARGS: the policy's own arguments of done(), with their leading comma, or nothing.
+ * The selected forms (k_audio_tail_sel, k_audio_tail_s16_sel) also define FMD_TAIL_ROWS, the [CP] int32 table of the
+ * call's selection: the output row of every channel, -1 for a channel that delivers none.  Such a lane runs the
+ * recurrence, the meter and the status record like every other lane and leaves out what belongs to the output:
+ * take(), store(), flush() and done() (the conversion and the clip count with them).
  */
   __builtin_amdgcn_s_setprio(3);
   const unsigned lane = threadIdx.x;
@@ -12,6 +16,16 @@
     return;
   const bool active = c0 < C;
   const unsigned c = active ? c0 : C - 1;
+#ifdef FMD_TAIL_ROWS
+  const int sel_row = FMD_TAIL_ROWS[c];
+  const bool deliver = active && sel_row >= 0;
+  const unsigned row = deliver ? (unsigned)sel_row : 0u;
+  constexpr bool all_take = false;
+#else
+  const bool deliver = active; // one row per channel: every lane that has a channel delivers it, row = channel
+  const unsigned row = c;
+  constexpr bool all_take = true;
+#endif
   float de_re = st.F(F_DE_RE)[c], de_im = st.F(F_DE_IM)[c];
   float w1a = st.F(F_N_W1A)[c], w2a = st.F(F_N_W2A)[c], w1b = st.F(F_N_W1B)[c], w2b = st.F(F_N_W2B)[c];
   const int stereo = st.I(I_STEREO_Q0 + (int)stereo_q)[c];
@@ -41,7 +55,7 @@
     vsumsq += o.y * o.y;
     return o;
   };
-  typename OUT::frame_t* __restrict__ o = reinterpret_cast<typename OUT::frame_t*>(audio + (size_t)c * audio_stride);
+  typename OUT::frame_t* __restrict__ o = reinterpret_cast<typename OUT::frame_t*>(audio + (size_t)row * audio_stride);
   typename OUT::State os;
 
   unsigned i0 = 0;
@@ -64,8 +78,9 @@
     for (unsigned u = 0; u < AT_STEPS; u++)
     {
       const float2 f = frame(vin[u]);
-      OUT::take(os, u, f);
-      if (active)
+      if (all_take || deliver)
+        OUT::take(os, u, f);
+      if (deliver)
         OUT::store(o, os, i0, u, f);
     }
   }
@@ -77,11 +92,12 @@
       if (u < cnt)
       {
         const float2 f = frame(vnext[u]);
-        OUT::take(os, u, f);
-        if (active)
+        if (all_take || deliver)
+          OUT::take(os, u, f);
+        if (deliver)
           OUT::store(o, os, i0, u, f);
       }
-    OUT::flush(o, os, i0, cnt, active);
+    OUT::flush(o, os, i0, cnt, deliver);
   }
   if (active)
   {
@@ -115,5 +131,6 @@
     h[HS_AUDIO_MEAN * CPs] = __float_as_uint(mean);
     h[HS_AUDIO_RMS * CPs] = __float_as_uint(rms);
     h[HS_AUDIO_LEVEL * CPs] = __float_as_uint(level);
-    OUT::done(os, c FMD_TAIL_DONE_ARGS);
+    if (all_take || deliver)
+      OUT::done(os, c FMD_TAIL_DONE_ARGS);
   }

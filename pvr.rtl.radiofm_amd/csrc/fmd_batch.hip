@@ -278,6 +278,35 @@ struct fmd_batch
   // fmd_batch_read_pcm_clipped).  It belongs to the output like the audio meter: nothing resets it.
   DevBuf<unsigned long long> pcm_clip; // [CP]
 
+  /* Which channels deliver audio / multiplex rows (fmd_batch_select_audio / _mpx).  The
+   * caller-facing batch holds the list as the caller gave it (global channels, row i = list[i]); a batch with buffers
+   * of its own holds its part as (local channel, global row) entries sorted by channel, and the row tables its
+   * kernels read.  A table is a per-call resource: the audio tail and the multiplex writer run on different streams,
+   * and calls in flight keep the selection they were submitted with.  So every change makes a new VERSION -- device
+   * table, page-locked staging and an event of its own --, uploaded on the reading kernel's stream right in front of
+   * the first kernel that reads it; `read` is recorded behind every reader, and a version is written again only once
+   * it is no longer the current one and `read` has completed: behind its last reader.  No call waits for another. */
+  struct SelTable
+  {
+    DevBuf<int> d;      // audio: [CP] output row of every channel, -1 none; multiplex: [C] int2 (channel, row)
+    HostBuf<int> h;     // what the upload reads: the version's own, rewritten only with the version
+    Event read;         // behind the last kernel that reads d (and so behind the upload)
+    hipStream_t stream = nullptr; // where `read` was last recorded
+    bool used = false;
+  };
+  struct Selection
+  {
+    bool on = false;              // false: one row per channel, the kernels and launches of a batch without this
+    unsigned n_total = 0;         // rows of the whole selection (the caller-facing batch's list)
+    std::vector<unsigned> list;   // caller-facing batch: the channels in row order
+    std::vector<int2> ent;        // batch with buffers: its part, sorted by channel
+    bool dirty = false;           // ent changed since the current version was built
+    std::vector<std::unique_ptr<SelTable>> pool;
+    int cur = -1;
+  };
+  Selection sel_audio, sel_mpx;
+  bool decoder_owned = false;     // the one-channel batch behind an fmd_decoder: it takes no selection
+
   std::vector<std::unique_ptr<fmd::GroupDecoder>> gdec;
 
   // profiling: 0 off, 1 = events around the IF FIR kernel only, 2 = around every stage.
@@ -316,6 +345,7 @@ struct fmd_batch
     int pcm = 0;
     size_t audio_stride = 0;
     hipEvent_t tl0 = nullptr, tl1 = nullptr; // profiling level 1: the audio tail's own start / stop
+    Selection* asel = nullptr;         // the call's audio selection, or null: one row per channel
   };
   /* More channels than the whole-CU pipeline is built for (kSubBatchChannels = 64 CUs' worth of serial stage): the
    * batch the caller holds is a SHELL over ceil(C / 8192) sub-batches of equal size, each a complete batch of its own
@@ -474,6 +504,12 @@ constexpr unsigned kSubBatchChannels = 8192;
 inline bool is_shell(const fmd_batch* b)
 {
   return !b->subs.empty();
+}
+
+/* whether the batch's next call writes any audio row (a selection of no rows: the audio pointer may be null) */
+inline bool audio_rows_due(const fmd_batch* b)
+{
+  return !(b->sel_audio.on && b->sel_audio.n_total == 0);
 }
 
 /* the sub-batch that owns a channel, and the channel's index there (a plain batch: itself) */
@@ -1784,7 +1820,7 @@ static int process_any(fmd_batch* b, const void* d_iq, IqFormat fmt, size_t iq_c
   if (!b || (!b->twin && !b->edits_pending))
     return process_shell(b, d_iq, fmt, iq_channel_stride, samples, d_audio, pcm, audio_channel_stride, out_floats,
                          stream, mpx);
-  if (!d_iq || !d_audio)
+  if (!d_iq || (!d_audio && audio_rows_due(b)))
     return fail(FMD_ERR_ARG, "fmd_batch_process_device: null argument");
   if (samples > FMD_MAX_BLOCK || samples < b->min_samples)
     return fail(FMD_ERR_SIZE, "samples must be within [fmd_batch_min_samples(), the largest block] = [" +
@@ -1819,7 +1855,7 @@ static int process_shell(fmd_batch* b, const void* d_iq, IqFormat fmt, size_t iq
   if (!b || b->subs.empty())
     return process_device_impl(b, d_iq, fmt, iq_channel_stride, samples, d_audio, pcm, audio_channel_stride,
                                out_floats, stream, mpx);
-  if (!d_iq || !d_audio)
+  if (!d_iq || (!d_audio && audio_rows_due(b)))
     return fail(FMD_ERR_ARG, "fmd_batch_process_device: null argument");
   if (int rc = check_device_errors(b))
     return rc;
@@ -1833,10 +1869,12 @@ static int process_shell(fmd_batch* b, const void* d_iq, IqFormat fmt, size_t iq
     // (a capture map: every sub-batch takes the first row, its walk names the rows it reads)
     const size_t row0 = b->map_on ? 0 : ch0 / b->cpc;
     const char* iq = static_cast<const char*>(d_iq) + row0 * iq_channel_stride * esz;
-    // (the sub-batch's first row: ch0 * stride elements of the output format)
-    char* audio = static_cast<char*>(d_audio) + size_t(ch0) * audio_channel_stride * pcm_esz(pcm);
+    // (the sub-batch's first row: ch0 * stride elements of the output format; with a selection every sub-batch
+    // writes into the one compact output, its table holds global row numbers)
+    char* audio = static_cast<char*>(d_audio) +
+                  (b->sel_audio.on ? size_t(0) : size_t(ch0) * audio_channel_stride * pcm_esz(pcm));
     MpxJob sub_mpx = mpx; // (the sub-batch's first multiplex row, like its first audio row)
-    if (mpx.d)
+    if (mpx.d && !b->sel_mpx.on)
       sub_mpx.d = static_cast<char*>(mpx.d) + size_t(ch0) * mpx.stride * mpx_esz(mpx.fmt);
     const int rc = process_device_impl(sb, iq, fmt, iq_channel_stride, samples, audio, pcm, audio_channel_stride, &nf,
                                        stream, sub_mpx);
@@ -1895,8 +1933,8 @@ int fmd_batch_process_device_mpx(fmd_batch* b, const void* d_iq, int iq_format, 
                 "fmd_batch_process_device_mpx: iq_format must be one of FMD_IQ_F32, _U8, _S8, _S16 (0..3)");
   if (!pcm_format_ok(pcm_format))
     return fail(FMD_ERR_ARG, "fmd_batch_process_device_mpx: pcm_format must be FMD_PCM_F32 or FMD_PCM_S16 (0..1)");
-  if (!d_mpx)
-  { // no multiplex: the _pcm call, nothing else
+  if (!d_mpx || (b && b->sel_mpx.on && b->sel_mpx.n_total == 0))
+  { // no multiplex (or a selection of no rows): the _pcm call, nothing else
     if (out_mpx_samples)
       *out_mpx_samples = 0;
     return fmd_batch_process_device_pcm(b, d_iq, iq_format, iq_channel_stride, samples, d_audio, pcm_format,
@@ -2347,6 +2385,87 @@ int fmd_batch_switch_captures(fmd_batch* b, const unsigned* channels, const unsi
   return FMD_OK;
 }
 
+/* fmd_batch_select_audio / _mpx: checked as a whole, then every batch with buffers takes its part -- (local channel,
+ * global row), sorted by channel: the audio table is indexed by channel anyway, and the multiplex writer's gathers
+ * coalesce over neighbouring channels -- and builds a new table version in front of its next call (sel_table). */
+static int select_rows(fmd_batch* b, bool mpx, const unsigned* channels, unsigned n, const char* who)
+{
+  if (!b)
+    return fail(FMD_ERR_ARG, std::string(who) + ": null batch");
+  if (b->decoder_owned)
+    return fail(FMD_ERR_STATE, std::string(who) + ": the batch behind an fmd_decoder takes no selection (the decoder "
+                                                  "owns its output)");
+  if (b->failed)
+    return fail(FMD_ERR_ARG, std::string(who) + ": the batch has failed (fmd_batch_reset clears it)");
+  if (channels)
+  {
+    if (n > b->C)
+      return fail(FMD_ERR_ARG, std::string(who) + ": more rows than the batch has channels");
+    std::vector<unsigned> seen(channels, channels + n);
+    std::sort(seen.begin(), seen.end());
+    if (n && seen.back() >= b->C)
+      return fail(FMD_ERR_ARG, std::string(who) + ": channel " + std::to_string(seen.back()) + " out of range");
+    if (std::adjacent_find(seen.begin(), seen.end()) != seen.end())
+      return fail(FMD_ERR_ARG, std::string(who) + ": a channel is listed twice");
+  }
+  else
+    n = 0;
+  fmd_batch::Selection& top = mpx ? b->sel_mpx : b->sel_audio;
+  const std::vector<fmd_batch*> xs = buffer_batches(b);
+  for (size_t k = 0; k < xs.size(); k++)
+  {
+    fmd_batch* x = xs[k];
+    const unsigned ch0 = is_shell(b) ? b->sub_ch0[k] : 0u;
+    fmd_batch::Selection& sel = mpx ? x->sel_mpx : x->sel_audio;
+    sel.ent.clear();
+    for (unsigned i = 0; i < n; i++)
+      if (channels[i] >= ch0 && channels[i] - ch0 < x->C)
+        sel.ent.push_back(make_int2(int(channels[i] - ch0), int(i)));
+    std::sort(sel.ent.begin(), sel.ent.end(), [](const int2& a, const int2& c) { return a.x < c.x; });
+    sel.on = channels != nullptr;
+    sel.n_total = n;
+    sel.dirty = true;
+  }
+  top.on = channels != nullptr;
+  top.n_total = n;
+  if (channels)
+    top.list.assign(channels, channels + n);
+  else
+    top.list.clear();
+  return FMD_OK;
+}
+
+static int get_selection(fmd_batch* b, bool mpx, unsigned* out, unsigned cap, const char* who)
+{
+  if (!b || (cap && !out))
+    return fail(FMD_ERR_ARG, std::string(who) + ": null argument");
+  const fmd_batch::Selection& sel = mpx ? b->sel_mpx : b->sel_audio;
+  const unsigned n = sel.on ? sel.n_total : b->C;
+  for (unsigned i = 0; i < std::min(cap, n); i++)
+    out[i] = sel.on ? sel.list[i] : i;
+  return int(n);
+}
+
+int fmd_batch_select_audio(fmd_batch* b, const unsigned* channels, unsigned n)
+{
+  return select_rows(b, false, channels, n, "fmd_batch_select_audio");
+}
+
+int fmd_batch_select_mpx(fmd_batch* b, const unsigned* channels, unsigned n)
+{
+  return select_rows(b, true, channels, n, "fmd_batch_select_mpx");
+}
+
+int fmd_batch_get_audio_selection(fmd_batch* b, unsigned* out, unsigned cap)
+{
+  return get_selection(b, false, out, cap, "fmd_batch_get_audio_selection");
+}
+
+int fmd_batch_get_mpx_selection(fmd_batch* b, unsigned* out, unsigned cap)
+{
+  return get_selection(b, true, out, cap, "fmd_batch_get_mpx_selection");
+}
+
 int fmd_batch_retune_channels_to(fmd_batch* b, const unsigned* channels, const int* shifts, const unsigned* captures,
                                  unsigned n)
 {
@@ -2564,10 +2683,16 @@ static int process_host_impl(fmd_batch* b, const void* iq, IqFormat fmt, size_t 
                              unsigned* out_floats, void* mpx = nullptr, MpxFormat mpx_fmt = MPX_F32,
                              size_t mpx_channel_stride = 0, unsigned* out_mpx = nullptr)
 {
-  if (!b || !iq || !audio)
+  if (!b || !iq || (!audio && audio_rows_due(b)))
     return fail(FMD_ERR_ARG, "fmd_batch_process_host: null argument");
   HIPCHK(hipSetDevice(b->device));
   const unsigned C = b->C;
+  // rows of the two outputs: one per channel, or the selections' (fmd_batch_select_audio / _mpx) -- staged, copied
+  // back and laid out in the caller's arrays as that many rows
+  const unsigned a_rows = b->sel_audio.on ? b->sel_audio.n_total : C;
+  const unsigned m_rows = b->sel_mpx.on ? b->sel_mpx.n_total : C;
+  if (m_rows == 0) // a selection of no rows: the call without the multiplex
+    mpx = nullptr;
   // multiplex staging: rows of m_stride elements, every row on a 16-byte boundary; the caller's rows have to hold
   // the call's samples (known before the call: nothing is submitted for a refused one)
   MpxJob mj;
@@ -2577,10 +2702,10 @@ static int process_host_impl(fmd_batch* b, const void* iq, IqFormat fmt, size_t 
   unsigned nm = 0;
   if (mpx)
   {
-    if (C > 1 && mpx_channel_stride < next_baseband_length(b, samples))
+    if (m_rows > 1 && mpx_channel_stride < next_baseband_length(b, samples))
       return fail(FMD_ERR_ARG, "fmd_batch_process_host_mpx: mpx_channel_stride smaller than the call's baseband "
                                "length (fmd_batch_max_mpx_samples is the bound)");
-    const size_t mpx_floats = m_stride * C * msz / sizeof(float);
+    const size_t mpx_floats = m_stride * m_rows * msz / sizeof(float);
     if (mpx_floats > b->h_mpx.n && b->h_mpx.alloc(mpx_floats))
       return fail(FMD_ERR_DEVICE, "staging allocation failed");
     mj.d = b->h_mpx.p;
@@ -2599,7 +2724,7 @@ static int process_host_impl(fmd_batch* b, const void* iq, IqFormat fmt, size_t 
   const size_t asz = pcm_esz(pcm);
   const size_t a_round = pcm == PCM_S16 ? 7 : 3;
   const size_t a_stride = (size_t(fmd_batch_max_audio_floats(b, samples)) + a_round) & ~a_round;
-  const size_t audio_floats = a_stride * C * asz / sizeof(float);
+  const size_t audio_floats = a_stride * a_rows * asz / sizeof(float);
   if ((iq_floats > b->h_iq.n && b->h_iq.alloc(iq_floats)) ||
       (audio_floats > b->h_audio.n && b->h_audio.alloc(audio_floats)))
     return fail(FMD_ERR_DEVICE, "staging allocation failed");
@@ -2617,7 +2742,7 @@ static int process_host_impl(fmd_batch* b, const void* iq, IqFormat fmt, size_t 
   int rc = process_any(b, b->h_iq.p, fmt, dev_iq_stride, samples, b->h_audio.p, pcm, a_stride, &nf, nullptr, mj);
   if (rc != FMD_OK)
     return rc;
-  if (C > 1 && nf > audio_channel_stride)
+  if (a_rows > 1 && nf > audio_channel_stride)
     return fail(FMD_ERR_ARG, "audio_channel_stride smaller than the audio produced");
   b->host_ms[1] += ms_since(tp);
   tp = clk::now();
@@ -2626,11 +2751,12 @@ static int process_host_impl(fmd_batch* b, const void* iq, IqFormat fmt, size_t 
   rc = wait_impl(b, 0, nullptr, false); // the groups-lost flag is this call's to report, at its end
   if (rc < 0)
     return rc;
-  HIPCHK(hipMemcpy2D(audio, (C > 1 ? audio_channel_stride : size_t(nf)) * asz, b->h_audio.p, a_stride * asz,
-                     size_t(nf) * asz, C, hipMemcpyDeviceToHost));
+  if (a_rows)
+    HIPCHK(hipMemcpy2D(audio, (a_rows > 1 ? audio_channel_stride : size_t(nf)) * asz, b->h_audio.p, a_stride * asz,
+                       size_t(nf) * asz, a_rows, hipMemcpyDeviceToHost));
   if (mpx && nm)
-    HIPCHK(hipMemcpy2D(mpx, (C > 1 ? mpx_channel_stride : size_t(nm)) * msz, b->h_mpx.p, m_stride * msz,
-                       size_t(nm) * msz, C, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy2D(mpx, (m_rows > 1 ? mpx_channel_stride : size_t(nm)) * msz, b->h_mpx.p, m_stride * msz,
+                       size_t(nm) * msz, m_rows, hipMemcpyDeviceToHost));
   if (out_mpx)
     *out_mpx = nm;
   b->host_ms[2] += ms_since(tp);
@@ -2997,6 +3123,7 @@ int fmd_create(const fmd_params* params, const fmd_callbacks* cb, void* user, fm
   int rc = fmd_batch_create(params, 1, nullptr, dev, cb, user, &b);
   if (rc != FMD_OK)
     return rc;
+  b->decoder_owned = true;
   *out = new fmd_decoder{b};
   return FMD_OK;
 }

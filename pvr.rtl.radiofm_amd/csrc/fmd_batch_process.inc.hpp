@@ -145,6 +145,77 @@ void launch_light_rds(fmd_batch* b, const fmd_batch::LightJob& j, hipStream_t s)
     mark_failed(b, "hipEventRecord failed behind the RDS part of a call");
 }
 
+/* The row table of selection `sel` for a kernel about to be launched on stream st.  A
+ * selection that changed since its current version was built takes a version nobody reads any more -- not the current
+ * one, and the event behind its last reader has completed -- or a new one (only while the pool grows: as many
+ * versions as calls are in flight, plus one), fills the version's own staging and uploads it on st, in front of the
+ * reader.  A reader on another stream than the last one first waits for that one: the upload is in its order.
+ * sel_read_done() behind the launch records the version's event.  Null: the batch has been marked failed. */
+const int* sel_table(fmd_batch* b, fmd_batch::Selection& sel, bool mpx, hipStream_t st)
+{
+  if (sel.dirty || sel.cur < 0)
+  {
+    int v = -1;
+    for (size_t i = 0; i < sel.pool.size() && v < 0; i++)
+      if (int(i) != sel.cur && (!sel.pool[i]->used || hipEventQuery(sel.pool[i]->read) == hipSuccess))
+        v = int(i);
+    (void)hipGetLastError(); // (hipErrorNotReady is an answer, not an error)
+    if (v < 0)
+    {
+      auto t = std::make_unique<fmd_batch::SelTable>();
+      const size_t ints = mpx ? size_t(2) * b->C : size_t(b->CP);
+      if (t->d.alloc(ints) || t->h.alloc(ints) || t->read.create() != hipSuccess)
+      {
+        mark_failed(b, "allocation of a selection's row table failed");
+        return nullptr;
+      }
+      sel.pool.push_back(std::move(t));
+      v = int(sel.pool.size()) - 1;
+    }
+    fmd_batch::SelTable& t = *sel.pool[v];
+    size_t ints = 0;
+    if (mpx)
+    {
+      for (const int2& e : sel.ent)
+      {
+        t.h.p[ints++] = e.x;
+        t.h.p[ints++] = e.y;
+      }
+    }
+    else
+    {
+      ints = b->CP;
+      std::fill(t.h.p, t.h.p + ints, -1);
+      for (const int2& e : sel.ent)
+        t.h.p[e.x] = e.y;
+    }
+    if (ints && hipMemcpyAsync(t.d.p, t.h.p, ints * sizeof(int), hipMemcpyHostToDevice, st) != hipSuccess)
+    {
+      mark_failed(b, "the upload of a selection's row table failed");
+      return nullptr;
+    }
+    t.stream = st;
+    t.used = true;
+    sel.cur = v;
+    sel.dirty = false;
+  }
+  fmd_batch::SelTable& t = *sel.pool[sel.cur];
+  if (t.stream != st && hipStreamWaitEvent(st, t.read, 0) != hipSuccess)
+  {
+    mark_failed(b, "hipStreamWaitEvent failed in front of a selection's row table");
+    return nullptr;
+  }
+  return t.d.p;
+}
+
+void sel_read_done(fmd_batch* b, fmd_batch::Selection& sel, hipStream_t st)
+{
+  fmd_batch::SelTable& t = *sel.pool[sel.cur];
+  if (hipEventRecord(t.read, st) != hipSuccess)
+    mark_failed(b, "hipEventRecord failed behind a selection's row table");
+  t.stream = st;
+}
+
 /* Audio half on stream s, behind event `audio_after` of the call where it has one: (layout 2: the 29-tap low-pass,)
  * de-emphasis, notch, L/R matrix, audio meter; then -- behind the RDS half -- the status record; records EV_AUD. */
 void launch_light_audio(fmd_batch* b, const fmd_batch::LightJob& j, hipStream_t s)
@@ -163,13 +234,26 @@ void launch_light_audio(fmd_batch* b, const fmd_batch::LightJob& j, hipStream_t 
   const fmd::AudioConsts k = audio_consts(d);
   // (profiling level 1: j.tl0 / j.tl1 take the tail's own start and stop)
   // the call's output format is the tail's store policy (FMD_PCM_*): nothing in front of it sees the format
-  if (j.pcm == FMD_PCM_S16)
+  // a selection (fmd_batch_select_audio): the selected forms and the call's row table; without, the kernels, the
+  // arguments and the launches of a batch that never had one
+  const int* rows = j.asel ? sel_table(b, *j.asel, false, s) : nullptr;
+  if (j.asel && !rows)
+    ; // (the batch has failed: its state is void, the tail is left out)
+  else if (j.asel && j.pcm == FMD_PCM_S16)
+    launch(fmd::k_audio_tail_s16_sel, dim3(CP / 64), dim3(64, 1), 0, s, j.tl0, j.tl1, b->alp[j.q].p, j.A, C, CP, k,
+           b->st, j.d_audio, j.audio_stride, unsigned(j.sq), j.call_index, b->pcm_clip.p, rows);
+  else if (j.asel)
+    launch(fmd::k_audio_tail_sel, dim3(CP / 64), dim3(64, 1), 0, s, j.tl0, j.tl1, b->alp[j.q].p, j.A, C, CP, k, b->st,
+           j.d_audio, j.audio_stride, unsigned(j.sq), j.call_index, rows);
+  else if (j.pcm == FMD_PCM_S16)
     launch(fmd::k_audio_tail_s16, dim3(CP / 64), dim3(64, 1), 0, s, j.tl0, j.tl1,
            b->alp[j.q].p, j.A, C, CP, k, b->st, j.d_audio, j.audio_stride, unsigned(j.sq), j.call_index,
            b->pcm_clip.p);
   else
     launch(fmd::k_audio_tail, dim3(CP / 64), dim3(64, 1), 0, s, j.tl0, j.tl1, b->alp[j.q].p, j.A, C, CP,
            k, b->st, j.d_audio, j.audio_stride, unsigned(j.sq), j.call_index);
+  if (rows)
+    sel_read_done(b, *j.asel, s);
   // the record's RDS state is the other half's (same stream: stream order)
   if (j.events && j.status_after_rds && hipStreamWaitEvent(s, b->cev[j.es][fmd_batch::EV_RDS], 0) != hipSuccess)
     mark_failed(b, "hipStreamWaitEvent failed in front of the status record of a call");
@@ -279,7 +363,7 @@ int process_device_impl(fmd_batch* b, const void* d_iq, IqFormat fmt, size_t iq_
                         unsigned samples, void* d_audio, PcmFormat pcm, size_t audio_channel_stride,
                         unsigned* out_floats, void* stream_, const MpxJob& mpx = MpxJob())
 {
-  if (!b || !d_iq || !d_audio)
+  if (!b || !d_iq || (!d_audio && audio_rows_due(b)))
     return fail(FMD_ERR_ARG, "fmd_batch_process_device: null argument");
   if (samples > FMD_MAX_BLOCK || samples < b->min_samples)
     return fail(FMD_ERR_SIZE, "samples must be within [fmd_batch_min_samples(), the largest block] = [" +
@@ -362,7 +446,8 @@ int process_device_impl(fmd_batch* b, const void* d_iq, IqFormat fmt, size_t iq_
     return fail(FMD_ERR_STATE, "internal: plan exceeds buffer geometry");
   if (A == 0)
     return fail(FMD_ERR_SIZE, "block too short: no audio frame falls into it");
-  if (size_t(2) * A > audio_channel_stride && C > 1)
+  // (the stride lies between rows: one row per channel, or the rows of the selection)
+  if (size_t(2) * A > audio_channel_stride && (b->sel_audio.on ? b->sel_audio.n_total : C) > 1)
     return fail(FMD_ERR_ARG, "audio_channel_stride smaller than the audio produced");
   if (mpx.d && mpx.stride < M)
     return fail(FMD_ERR_ARG, "mpx_channel_stride smaller than the call's baseband length");
@@ -841,7 +926,27 @@ int process_device_impl(fmd_batch* b, const void* d_iq, IqFormat fmt, size_t iq_
      * that reads the same rows.  In front of EV_HEAVY on every path: the next writer of these rows, the serial stage
      * of the next-but-one call, runs behind that call's IF FIR, which waits for this EV_HEAVY; EV_ROLL behind it is
      * what fmd_batch_wait and the caller's stream wait for. */
-    if (mpx.d)
+    if (mpx.d && b->sel_mpx.on)
+    { // the selected writer (fmd_batch_select_mpx): tiles of 64 entries of this batch's part of the list
+      const unsigned n = unsigned(b->sel_mpx.ent.size());
+      const int* tab = n ? sel_table(b, b->sel_mpx, true, sA) : nullptr;
+      if (tab)
+      {
+        const dim3 g((n + 63) / 64, (M + fmd::MPX_T - 1) / fmd::MPX_T);
+        const float* rows = reinterpret_cast<const float*>(b->brp(q) + size_t(Hbb) * CP);
+        const hipEvent_t t0 = b->dbg_mpx_timing ? b->mpx_ev[es][0].e : nullptr;
+        const hipEvent_t t1 = b->dbg_mpx_timing ? b->mpx_ev[es][1].e : nullptr;
+        b->mpx_ev_used[es] = t0 != nullptr;
+        if (mpx.fmt == MPX_S16)
+          launch(fmd::k_mpx_out_sel<fmd::MpxS16>, g, dim3(256), 0, sA, t0, t1, rows, M, n, CP,
+                 reinterpret_cast<const int2*>(tab), static_cast<int16_t*>(mpx.d), mpx.stride);
+        else
+          launch(fmd::k_mpx_out_sel<fmd::MpxF32>, g, dim3(256), 0, sA, t0, t1, rows, M, n, CP,
+                 reinterpret_cast<const int2*>(tab), static_cast<float*>(mpx.d), mpx.stride);
+        sel_read_done(b, b->sel_mpx, sA);
+      }
+    }
+    else if (mpx.d)
     {
       const dim3 g(CP / 64, (M + fmd::MPX_T - 1) / fmd::MPX_T);
       const float* rows = reinterpret_cast<const float*>(b->brp(q) + size_t(Hbb) * CP);
@@ -890,6 +995,7 @@ int process_device_impl(fmd_batch* b, const void* d_iq, IqFormat fmt, size_t iq_
   job.d_audio = d_audio;
   job.pcm = pcm;
   job.audio_stride = audio_channel_stride;
+  job.asel = b->sel_audio.on ? &b->sel_audio : nullptr;
   if (serial_mode || b->split_post)
   { // stage order of the reference (what the per-stage profile is keyed to), or two streams
     rds_heavy();

@@ -26,7 +26,8 @@ struct MpxS16
 
 constexpr unsigned MPX_T = 64; // time steps of a tile: 256 contiguous bytes of a float row, 128 of an int16 row
 
-/* One workgroup (4 waves) per tile of 64 channels x MPX_T time steps of `in`, the `.x` halves of the float2 rows
+/* k_mpx_out (its body is fmd_mpx_tile.inc, one text with the selected writer below):
+ * One workgroup (4 waves) per tile of 64 channels x MPX_T time steps of `in`, the `.x` halves of the float2 rows
  * [t][CP] the serial stage wrote (in = first data row, as floats); out: row c at out + c * stride elements.
  *
  * Reads: wave w takes the tile's rows 16 jj + 4 w + e (jj, e = 0..3), a lane one channel: per row the 64 lanes
@@ -53,90 +54,35 @@ template <class Fmt>
 __global__ __launch_bounds__(256) void k_mpx_out(const float* __restrict__ in, unsigned M, unsigned C, unsigned CP,
                                                  typename Fmt::elem_t* __restrict__ out, size_t stride)
 {
-  __shared__ __attribute__((aligned(16))) float tile[64 * MPX_T];
-  const unsigned l = threadIdx.x & 63u, w = threadIdx.x >> 6;
-  const unsigned ch0 = blockIdx.x * 64u, t0 = blockIdx.y * MPX_T;
-  {
-    const unsigned c = (l & 48u) + 2u * (l & 7u) + ((l >> 3) & 1u);
-    const float* src = in + 2u * size_t(ch0 + c);
-    float4 v[4];
-#pragma unroll
-    for (unsigned jj = 0; jj < 4; jj++)
-    {
-      const unsigned t = t0 + 4u * (w + 4u * jj);
-      float x[4];
-#pragma unroll
-      for (unsigned e = 0; e < 4; e++)
-        x[e] = (t + e < M) ? src[2u * size_t(t + e) * CP] : 0.0f;
-      v[jj] = make_float4(x[0], x[1], x[2], x[3]);
-    }
-#pragma unroll
-    for (unsigned jj = 0; jj < 4; jj++)
-      *reinterpret_cast<float4*>(&tile[c * MPX_T + 4u * ((w + 4u * jj + (c >> 1)) & 15u)]) = v[jj];
-  }
-  __syncthreads();
-  constexpr unsigned PER = Fmt::PER;       // samples a lane stores at a time
-  constexpr unsigned LPR = MPX_T / PER;    // lanes per channel row of the tile: 16 / 8
-  constexpr unsigned CPI = 64u / LPR;      // channels per wave and read: 4 / 8
-  constexpr unsigned NI = 16u / CPI;       // groups of PER samples per lane: 4 / 2
-  const unsigned g = l % LPR;              // the lane's group of PER samples in its channels' rows
-  const unsigned t = t0 + PER * g;
-  float x[NI][PER];
-#pragma unroll
-  for (unsigned i = 0; i < NI; i++)
-  {
-    const unsigned c = 16u * w + CPI * i + l / LPR;
-#pragma unroll
-    for (unsigned s = 0; s < PER / 4u; s++)
-    {
-      const float4 f =
-          *reinterpret_cast<const float4*>(&tile[c * MPX_T + 4u * (((PER / 4u) * g + s + (c >> 1)) & 15u)]);
-      x[i][4 * s] = f.x;
-      x[i][4 * s + 1] = f.y;
-      x[i][4 * s + 2] = f.z;
-      x[i][4 * s + 3] = f.w;
-    }
-  }
-  const bool whole = t0 + MPX_T <= M; // (the workgroup's: every tile but the call's last one)
-#pragma unroll
-  for (unsigned i = 0; i < NI; i++)
-  {
-    const unsigned c = 16u * w + CPI * i + l / LPR;
-    if (ch0 + c >= C)
-      continue;
-    typename Fmt::elem_t* o = out + size_t(ch0 + c) * stride + t;
-    if constexpr (PER == 4)
-    {
-      if (whole)
-        *reinterpret_cast<float4*>(o) = make_float4(x[i][0], x[i][1], x[i][2], x[i][3]);
-      else
-      { // (volatile: the compiler otherwise folds these stores into the 16-byte one and splits that in 12 + 4)
-        volatile float* ov = o;
-#pragma unroll
-        for (unsigned e = 0; e < 4; e++)
-          if (t + e < M)
-            ov[e] = x[i][e];
-      }
-    }
-    else
-    {
-      unsigned h[8];
-#pragma unroll
-      for (unsigned e = 0; e < 8; e++)
-        h[e] = (unsigned)fmd_f32_to_mpx16(x[i][e]) & 0xffffu;
-      if (whole)
-        *reinterpret_cast<uint4*>(o) =
-            make_uint4(h[0] | (h[1] << 16), h[2] | (h[3] << 16), h[4] | (h[5] << 16), h[6] | (h[7] << 16));
-      else
-      {
-        volatile int16_t* ov = o;
-#pragma unroll
-        for (unsigned e = 0; e < 8; e++)
-          if (t + e < M)
-            ov[e] = (int16_t)h[e];
-      }
-    }
-  }
+#define FMD_MPX_SRC(c) (row0 + (c))
+#define FMD_MPX_SKIPPED(c) (row0 + (c) >= C)
+#define FMD_MPX_DST(c) (row0 + (c))
+#include "fmd_mpx_tile.inc"
+#undef FMD_MPX_SRC
+#undef FMD_MPX_SKIPPED
+#undef FMD_MPX_DST
+}
+
+/* The selected writer (fmd_batch_select_mpx): tiles of 64 list entries x MPX_T time steps, grid ((n + 63) / 64, tiles
+ * of time).  ent[e] = (channel the entry reads, output row it writes), e < n, sorted by channel by the host: the LDS
+ * image, its conflict-free reads and writes and the 16-byte stores are k_mpx_out's (the layout argument above is about
+ * tile rows, whatever channels they hold); the loads are per-lane gathers of the 8-byte float2 of the entry's channel
+ * out of the [t][CP] rows -- neighbouring channels of the sorted list share a 64- or 128-byte request, a lone
+ * channel takes one 32-byte sector per time step for its 4 bytes.  Output rows >= n and samples at or behind M are
+ * never written. */
+template <class Fmt>
+__global__ __launch_bounds__(256) void k_mpx_out_sel(const float* __restrict__ in, unsigned M, unsigned n, unsigned CP,
+                                                     const int2* __restrict__ ent,
+                                                     typename Fmt::elem_t* __restrict__ out, size_t stride)
+{
+  // (entries at or behind n: the last one's channel is read again, none is stored)
+#define FMD_MPX_SRC(c) ((unsigned)ent[min(row0 + (c), n - 1u)].x)
+#define FMD_MPX_SKIPPED(c) (row0 + (c) >= n)
+#define FMD_MPX_DST(c) ((unsigned)ent[row0 + (c)].y)
+#include "fmd_mpx_tile.inc"
+#undef FMD_MPX_SRC
+#undef FMD_MPX_SKIPPED
+#undef FMD_MPX_DST
 }
 
 /* The device build of fmd_f32_to_mpx16 on an array (fmd_debug_math, what = 9): the result as a float. */

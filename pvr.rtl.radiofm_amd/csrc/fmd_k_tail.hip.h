@@ -110,6 +110,38 @@ __global__ __launch_bounds__(256) void k_audio_tail_s16(const float2* __restrict
 #undef FMD_TAIL_DONE_ARGS
 }
 
+/* The selected forms (fmd_batch_select_audio): row rows[c] of `audio` is channel c's, a channel whose entry is -1
+ * delivers nothing -- its lane runs the recurrence, the meter and the status record and skips the stores, the
+ * conversion and the clip count.  The same body text; chosen only for calls with a selection. */
+__global__ __launch_bounds__(256) void k_audio_tail_sel(const float2* __restrict__ lp, unsigned A, unsigned C,
+                                                       unsigned CP, AudioConsts k, ChannelState st,
+                                                       float* __restrict__ audio, size_t audio_stride,
+                                                       unsigned stereo_q, unsigned call_index,
+                                                       const int* __restrict__ rows)
+{
+  using OUT = OutF32;
+#define FMD_TAIL_DONE_ARGS
+#define FMD_TAIL_ROWS rows
+#include "fmd_audio_tail.inc"
+#undef FMD_TAIL_ROWS
+#undef FMD_TAIL_DONE_ARGS
+}
+
+__global__ __launch_bounds__(256) void k_audio_tail_s16_sel(const float2* __restrict__ lp, unsigned A, unsigned C,
+                                                           unsigned CP, AudioConsts k, ChannelState st,
+                                                           int16_t* __restrict__ audio, size_t audio_stride,
+                                                           unsigned stereo_q, unsigned call_index,
+                                                           unsigned long long* __restrict__ clipped,
+                                                           const int* __restrict__ rows)
+{
+  using OUT = OutS16;
+#define FMD_TAIL_DONE_ARGS , clipped
+#define FMD_TAIL_ROWS rows
+#include "fmd_audio_tail.inc"
+#undef FMD_TAIL_ROWS
+#undef FMD_TAIL_DONE_ARGS
+}
+
 /* The last kernel of a call: every channel's status record from device memory to the host's snapshot
  * under the per-channel sequence lock (HostStatusWord), a thread per channel -- one kernel of a few
  * waves pays the two system-scope fences, not the latency-bound audio tail. */
