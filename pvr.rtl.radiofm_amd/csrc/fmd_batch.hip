@@ -228,6 +228,8 @@ struct fmd_batch
   int dbg_hb4 = 1, dbg_ring4 = 1; // 0: the generic half-band / ring-FIR kernels where the unrolled ones would run
   int dbg_fir_ro = 2;          // outputs per lane of the headline IF FIR form: 1 k_if_fir_mt, 2 / 3 k_if_fir_mt3
                                // (2: 288 600 MS/s and the FIR 0.975 ms inside the pipeline; 3: 287 500 and 1.00)
+  bool dbg_fir_interior = true; // k_if_fir_mt3<.., 2>: tiles inside a call take the interior body ("fir_ro" -2: none
+                               // does; the sign of that key and not a key of its own: the key table is held to 14)
   int dbg_lpf_late = -1;       // stream layout of an overlapped call (process_device_impl): -1 the library decides,
                                // 0 low-pass filters on the heavy stream, 1 on a stream of their own, 2 at the
                                // heads of the light part's two streams
@@ -2143,7 +2145,12 @@ int fmd_batch_debug_set(fmd_batch* b, const char* key, int value)
   else if (k == "stage_mask")
     b->dbg_stage_mask = value & 63;
   else if (k == "fir_ro")
-    b->dbg_fir_ro = (value == 2 || value == 3) ? value : 1;
+  { // (-2: 2 with every tile on the edge path, the one body a tile had before the interior one; -3 is 3, which has
+    // the edge body only.  The sign of this key and not a key `fir_interior`: the keys are held to 14)
+    const int ro = value < 0 ? -value : value;
+    b->dbg_fir_ro = (ro == 2 || ro == 3) ? ro : 1;
+    b->dbg_fir_interior = value >= 0;
+  }
   else if (k == "serial_probe")
   { // per-workgroup timing of the serial stage's last 8 launches (fmd_batch_debug_serial_probe)
     HIPCHK(hipSetDevice(b->device));

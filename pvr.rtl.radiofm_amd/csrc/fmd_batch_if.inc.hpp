@@ -85,7 +85,10 @@ int launch_if_stage_t(fmd_batch* b, const void* d_iq, size_t iq_channel_stride, 
              : fma   ? &fmd::k_if_fir_mt3<IN, 12, 2, 2, 88, 11, true, MAP>
                      : &fmd::k_if_fir_mt3<IN, 12, 2, 2, 88, 11, false, MAP>;
       ntiles_l = (M + T3 - 1) / T3;
-      lds_l = (size_t(T3 - 1) * D + d.if_order + 4) * sizeof(float2);
+      // (two outputs per lane: room for all 12 rounds' pairs, 12 288 B and still 13 waves per CU -- an interior tile
+      // stores every round without a range test, k_if_fir_mt3)
+      lds_l = RO == 2 ? size_t(12) * 64 * 2 * sizeof(float2) : (size_t(T3 - 1) * D + d.if_order + 4) * sizeof(float2);
+      static_assert(size_t(12) * 64 * 2 >= size_t(127) * 11 + 88 + 4, "the rounds' pairs hold the window");
       nblocks = C * ((ntiles_l + 1) / 2);
     }
   }
@@ -102,7 +105,8 @@ int launch_if_stage_t(fmd_batch* b, const void* d_iq, size_t iq_channel_stride, 
   // profiled calls: the two events take the kernel's own start and stop
   launch(kfn3 ? kfn3 : kfn, dim3(nblocks), dim3(TILE), unsigned(lds_l), sF, ev_start, ev_stop, x, iq_channel_stride,
          N, b->hist[b->hist_sel].p, b->hist[b->hist_sel ^ 1].p, b->lut.p, T, b->lut_idx, b->if_coeff.p, d.if_order, D,
-         pos, M, b->demod[q].p, b->Mstride, ntiles_l, (C % 8 == 0) ? 1u : 0u, b->cpc,
+         pos, M, b->demod[q].p, b->Mstride, ntiles_l,
+         ((C % 8 == 0) ? 1u : 0u) | ((kfn3 && !b->dbg_fir_interior) ? 2u : 0u), b->cpc, // (bit 1: k_if_fir_mt3 only)
          MAP ? (const uint2*)b->d_walk.p : nullptr);
   mark(1);
   hipLaunchKernelGGL((fmd::k_if_level<IN, MAP>), dim3(C), dim3(64), 0, sF, x, iq_channel_stride, N, b->lut.p, T,

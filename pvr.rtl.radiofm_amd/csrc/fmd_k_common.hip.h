@@ -192,10 +192,33 @@ __device__ __forceinline__ unsigned walk_take(const uint2* __restrict__ walk, un
   return w.y;
 }
 
+/* A 64-bit value every lane of the wave holds the same of, for the compiler to keep in scalar registers. */
+__device__ __forceinline__ size_t uniform_u64(size_t a)
+{
+  const unsigned lo = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)a);
+  const unsigned hi = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)(a >> 32));
+  return ((size_t)hi << 32) | lo;
+}
+
 __device__ __forceinline__ float2 cmul(float2 a, float2 b)
 {
   // std::complex<float> product: (ac - bd) + i(ad + bc), four products and two sums, each rounded
   return make_float2(a.x * b.x - a.y * b.y, a.x * b.y + a.y * b.x);
+}
+
+/* cmul in three packed operations: (a.x l.x, a.x l.y), (a.y l.y, a.y l.x) and their sum with the low half of the
+ * second negated -- the four products and two sums of cmul on the same operands, each rounded (x - y and x + (-y)
+ * are one IEEE operation): the same bits.  From vector types the compiler forms difference and sum in both halves
+ * and picks one of each (four packed products, four packed sums and two moves a sample); a packed operation takes
+ * either half of each operand for either half of its result (op_sel / op_sel_hi), so this says it with the
+ * instruction itself, like hb_tap_mul. */
+__device__ __forceinline__ float2 cmul_pk(float2 a, float2 l)
+{
+  float2 p, q, r;
+  asm("v_pk_mul_f32 %0, %1, %2 op_sel_hi:[0,1]" : "=v"(p) : "v"(a), "v"(l));
+  asm("v_pk_mul_f32 %0, %1, %2 op_sel:[1,1] op_sel_hi:[1,0]" : "=v"(q) : "v"(a), "v"(l));
+  asm("v_pk_add_f32 %0, %1, %2 neg_lo:[0,1]" : "=v"(r) : "v"(p), "v"(q));
+  return r;
 }
 
 typedef float fmd_f2v __attribute__((ext_vector_type(2)));
