@@ -138,6 +138,24 @@ public:
     return n > 0 ? static_cast<unsigned int>(n) : 0u;
   }
 
+  /* Not in the reference: what its block synchroniser computes and drops (fmd.h, "Every RDS block decision").
+   * SetRdsBlocks: the observation of every ProcessStream from now on (FMD_RDS_BLOCKS_*); CollectRdsBlocks: the block
+   * records queued so far, in order, into `out` (returns their number; *lost: records that did not fit);
+   * GetRdsQuality: the reception counters since the decoder was made (no Reset clears them). */
+  bool SetRdsBlocks(int mode, unsigned int queue_records = 0)
+  {
+    return fmd_batch_set_rds_blocks(fmd_decoder_batch(m_dec), mode, queue_records) == FMD_OK;
+  }
+  unsigned int CollectRdsBlocks(fmd_rds_block* out, unsigned int cap, unsigned int* lost = nullptr)
+  {
+    const int n = fmd_batch_collect_rds_blocks(fmd_decoder_batch(m_dec), out, cap, 0, nullptr, lost);
+    return n > 0 ? static_cast<unsigned int>(n) : 0u;
+  }
+  bool GetRdsQuality(fmd_rds_quality* out)
+  {
+    return fmd_batch_read_rds_quality(fmd_decoder_batch(m_dec), 0, 1, out) == FMD_OK;
+  }
+
 private:
   fmd_status Status() const
   {

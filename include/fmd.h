@@ -359,6 +359,71 @@ int fmd_batch_get_mpx_selection(fmd_batch* b, unsigned* out, unsigned cap);
  * stream).  A single decoder: through fmd_decoder_batch. */
 int fmd_batch_read_pcm_clipped(fmd_batch* b, unsigned first_channel, unsigned n, uint64_t* out);
 
+/* ---- Every RDS block decision, and per-channel reception counters ----
+ *
+ * RDS leaves a batch as whole groups: four blocks in a row that passed.  The block observation delivers what the
+ * synchroniser knows besides -- every 26-bit block it tested, against which offset word, whether it passed clean,
+ * was repaired or failed, and when block sync was found, confirmed and lost -- as records, and as eight counters per
+ * channel (the block error rate is failed / blocks).  Every value is an integer the reference's own state machine
+ * computes (cRDSRxSignalProcessor::ProcessNewRdsBit / CheckBlock, RDSProcess.cpp:272-431); the decoder itself is
+ * untouched: audio, groups and status are bit for bit those of a batch that never enabled it.
+ *
+ * Events.  Every ProcessNewRdsBit: bits++.
+ *   BITSYNC (:277-286), whenever CheckBlock(A, no FEC) returns 0: a record (state 0, position 0, status 0,
+ *     corrected 0); candidates++.
+ *   BLOCKSYNC / GROUPDECODE (:288-359), each time the bit position reaches 26: a record; blocks++.  position is the
+ *     entry of BLK_OFFSET_TBL[m_CurrentBlock + m_BGroupOffset] tested: 0 A, 1 B, 2 C, 3 D, 4 C' (entries 4, 5, 7 of
+ *     the table are A, B, D again, entry 6 is C').  status 0: the syndrome was zero before the error correction; 1:
+ *     non-zero before and zero after it (only GROUPDECODE corrects), corrected++; 2: CheckBlock returned non-zero,
+ *     failed++ -- the flips stay applied, as in the reference: `word` and `corrected` say so.  sync_acquired++ when a
+ *     state-1 record at D passes, sync_lost++ when a state-2 record fails.
+ *   Every DecodeRDS (a group delivered): groups++.
+ *   GROUPRESYNC cannot be reached with the reference's BLOCK_ERROR_LIMIT 0; a block boundary passed in it writes and
+ *     counts nothing.
+ * The counters, and with them bit_index, advance only in calls submitted in mode >= 1.  They belong to the
+ * observation of a slot like the clip counter, not to the decoder: fmd_batch_reset, fmd_batch_reset_channels,
+ * retunes, capture switches, fmd_batch_load_state and fmd_batch_import_channels restart the machine where they always
+ * did and leave the counters alone.  Counters, mode and queues are no part of a state blob (its record format is
+ * unchanged). */
+typedef struct fmd_rds_block { /* 24 bytes */
+  uint32_t channel;
+  uint32_t call_index; /* 1-based, as in fmd_rds_group */
+  uint32_t bit_index;  /* the channel's `bits` counter after this block's last bit */
+  uint32_t raw;        /* low 26 bits of m_InBitStream BEFORE CheckBlock */
+  uint16_t word;       /* (m_InBitStream AFTER CheckBlock >> 10) & 0xFFFF */
+  uint16_t sample;     /* index in the call's RDS-rate row where the slicer fired for the last bit */
+  uint8_t position;    /* offset word tested: 0 A, 1 B, 2 C, 3 D, 4 C' */
+  uint8_t status;      /* 0 clean, 1 corrected, 2 failed */
+  uint8_t state;       /* machine state BEFORE the check: 0 BITSYNC, 1 BLOCKSYNC, 2 GROUPDECODE */
+  uint8_t corrected;   /* bits the Meggitt loop flipped (the reference's correctedbits), failed blocks included */
+} fmd_rds_block;
+
+typedef struct fmd_rds_quality { /* 32 bytes, all modulo 2^32 */
+  uint32_t bits, candidates, blocks, corrected, failed, sync_acquired, sync_lost, groups;
+} fmd_rds_quality;
+
+#define FMD_RDS_BLOCKS_OFF 0
+#define FMD_RDS_BLOCKS_COUNT 1  /* counters only */
+#define FMD_RDS_BLOCKS_RECORD 2 /* counters + records */
+/* The mode of every call submitted from now on; it travels with the call like the formats: nothing waits, calls in
+ * flight keep the mode they were submitted with.  A mode-0 call launches what a batch without this launches.
+ * queue_records: the record capacity of each of the per-call block queues, 0 = max(8192, 4 * channels) (a shell: per
+ * sub-batch); fixed by the first call that enables mode 2, which allocates the queues -- a later different non-zero
+ * value is refused. */
+int fmd_batch_set_rds_blocks(fmd_batch* b, int mode, unsigned queue_records);
+int fmd_batch_get_rds_blocks(const fmd_batch* b); /* the mode, or a negative error */
+/* Like fmd_batch_collect_rds_lagged, with bookkeeping of its own: the two drains are independent and either may be
+ * called at any cadence.  Copies the block records of the calls at least `lag` (0..4) calls old to `out`, sorted by
+ * (call_index, channel, bit_index -- compared wrapping), waits for `stream`; returns their number (<= cap).  Records
+ * that did not fit a call's queue, or `out`, are dropped and added to *lost (may be null); no warning flag is touched
+ * and the counters never lose anything.  A call's queue is used again eight calls later: records left in it that
+ * long come with the later call's, once that call is `lag` calls old (collect at least every eight calls and `lag`
+ * means what it says).  fmd_batch_load_state drops queued records, as it drops queued groups. */
+int fmd_batch_collect_rds_blocks(fmd_batch* b, fmd_rds_block* out, unsigned cap, int lag, void* stream,
+                                 unsigned* lost);
+/* The counters of channels [first_channel, first_channel + n).  Synchronous, like fmd_batch_read_pcm_clipped. */
+int fmd_batch_read_rds_quality(fmd_batch* b, unsigned first_channel, unsigned n, fmd_rds_quality* out);
+
 /* Copies the queued RDS groups (all channels, call order) to `out`, waits for `stream`.
  * Returns the number of groups (<= cap) or a negative error.  When run_group_decoder != 0
  * each group is also fed to that channel's UECP group decoder (callbacks fire).  The return value is

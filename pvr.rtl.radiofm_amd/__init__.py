@@ -87,6 +87,27 @@ class FmdRdsGroup(C.Structure):
 RDS_GROUP_DTYPE = np.dtype([("channel", "<u4"), ("call_index", "<u4"), ("blocks", "<u2", (4,))])
 assert RDS_GROUP_DTYPE.itemsize == C.sizeof(FmdRdsGroup)
 
+
+class FmdRdsBlock(C.Structure):
+    _fields_ = [("channel", C.c_uint32), ("call_index", C.c_uint32), ("bit_index", C.c_uint32), ("raw", C.c_uint32),
+                ("word", C.c_uint16), ("sample", C.c_uint16), ("position", C.c_uint8), ("status", C.c_uint8),
+                ("state", C.c_uint8), ("corrected", C.c_uint8)]
+
+
+class FmdRdsQuality(C.Structure):
+    _fields_ = [(f, C.c_uint32) for f in ("bits", "candidates", "blocks", "corrected", "failed", "sync_acquired",
+                                          "sync_lost", "groups")]
+
+
+RDS_BLOCK_DTYPE = np.dtype([("channel", "<u4"), ("call_index", "<u4"), ("bit_index", "<u4"), ("raw", "<u4"),
+                            ("word", "<u2"), ("sample", "<u2"), ("position", "u1"), ("status", "u1"), ("state", "u1"),
+                            ("corrected", "u1")])
+RDS_QUALITY_DTYPE = np.dtype([(f, "<u4") for f, _ in FmdRdsQuality._fields_])
+assert C.sizeof(FmdRdsBlock) == 24 and RDS_BLOCK_DTYPE.itemsize == 24
+assert C.sizeof(FmdRdsQuality) == 32 and RDS_QUALITY_DTYPE.itemsize == 32
+# block observation modes (include/fmd.h FMD_RDS_BLOCKS_*)
+FMD_RDS_BLOCKS_OFF, FMD_RDS_BLOCKS_COUNT, FMD_RDS_BLOCKS_RECORD = 0, 1, 2
+
 class FmdAudioLevel(C.Structure):
     _fields_ = [("mean", C.c_float), ("rms", C.c_float), ("level", C.c_float)]
 
@@ -153,6 +174,8 @@ EXPORTS = [
     "fmd_batch_state_size", "fmd_batch_save_state", "fmd_batch_load_state", "fmd_batch_export_channels",
     "fmd_batch_import_channels", "fmd_save_state", "fmd_load_state", "fmd_batch_debug_state_skip",
     "fmd_batch_select_audio", "fmd_batch_select_mpx", "fmd_batch_get_audio_selection", "fmd_batch_get_mpx_selection",
+    "fmd_batch_set_rds_blocks", "fmd_batch_get_rds_blocks", "fmd_batch_collect_rds_blocks",
+    "fmd_batch_read_rds_quality",
 ]
 
 
@@ -301,6 +324,10 @@ def lib():
         L.fmd_batch_select_mpx.argtypes = [vp, vp, u]
         L.fmd_batch_get_audio_selection.argtypes = [vp, vp, u]
         L.fmd_batch_get_mpx_selection.argtypes = [vp, vp, u]
+        L.fmd_batch_set_rds_blocks.argtypes = [vp, i, u]
+        L.fmd_batch_get_rds_blocks.argtypes = [vp]
+        L.fmd_batch_collect_rds_blocks.argtypes = [vp, vp, u, i, vp, C.POINTER(u)]
+        L.fmd_batch_read_rds_quality.argtypes = [vp, u, u, vp]
         _LIB = L
     return _LIB
 
@@ -700,6 +727,31 @@ class Batch:
         out = np.zeros(self.n_channels, dtype=np.uint64)
         _check(lib().fmd_batch_read_pcm_clipped(self._h, 0, self.n_channels, out.ctypes.data))
         return out
+
+    def set_rds_blocks(self, mode, queue_records=0):
+        """The block observation of every call submitted from now on (fmd_batch_set_rds_blocks): 0 off, 1 reception
+        counters, 2 counters and a record of every block decision."""
+        _check(lib().fmd_batch_set_rds_blocks(self._h, int(mode), int(queue_records)))
+
+    def rds_blocks(self):
+        return _check(lib().fmd_batch_get_rds_blocks(self._h))
+
+    def collect_rds_blocks(self, cap=65536, lag=0, stream=None):
+        """(records, lost): the block records of the calls at least `lag` old as a structured array (RDS_BLOCK_DTYPE),
+        sorted by (call_index, channel, bit_index), and how many were dropped (a full queue, or cap)."""
+        buf = np.zeros(max(cap, 1), dtype=RDS_BLOCK_DTYPE)
+        lost = C.c_uint(0)
+        n = _check(lib().fmd_batch_collect_rds_blocks(self._h, buf.ctypes.data if cap else None, cap, lag, stream,
+                                                      C.byref(lost)))
+        return buf[:n].copy(), lost.value
+
+    def rds_quality(self, first=0, n=None):
+        """The reception counters of channels [first, first + n) as a structured array (RDS_QUALITY_DTYPE); waits for
+        every call submitted so far."""
+        n = self.n_channels - first if n is None else n
+        out = np.zeros(max(n, 1), dtype=RDS_QUALITY_DTYPE)
+        _check(lib().fmd_batch_read_rds_quality(self._h, first, n, out.ctypes.data))
+        return out[:n]
 
     def collect_rds_array(self, cap=65536, run_group_decoder=False, stream=None, lag=0):
         """Queued RDS groups as a numpy structured array (channel, call_index, blocks[4])."""

@@ -255,6 +255,24 @@ struct fmd_batch
   HostBuf<unsigned> h_counts;
   HostBuf<fmd::RdsGroupRec> h_recs;
   unsigned queue_cap = 0;
+  /* The block observation (fmd_batch_set_rds_blocks).  The mode is the caller-facing batch's
+   * and every sub-batch's next call's; a call takes it along in its LightJob.  Nothing of this exists on the device
+   * until the first call of fmd_batch_set_rds_blocks that enables a mode: then the counters ([RQ_N][CP], zero, and
+   * from there on touched by nothing but the observing kernels), and with the first mode 2 the block queues -- one
+   * per event slot like the group queues, with counts, staging and drained bookkeeping of their own: the two drains
+   * are independent. */
+  int rb_mode = 0;
+  unsigned rb_cap = 0;                 // records per block queue, fixed by the first mode 2
+  DevBuf<unsigned> rb_quality;         // [RQ_N][CP]
+  DevBuf<uint4> rb_queue[NSLOT];       // two uint4 per record
+  DevBuf<unsigned> rb_counts;          // [NSLOT]
+  // A mode-2 call has used the slot's queue since it was last drained.  A slot's age is its NEWEST call's
+  // (slot_call), whatever that call's mode: records left in a queue for NSLOT calls or more are delivered once the
+  // call that has since reused the slot is `lag` calls old -- later than their own call's age would allow, never
+  // earlier than a call that may still append.  Collecting at least every NSLOT calls never meets this.
+  bool rb_dirty[NSLOT] = {};
+  HostBuf<unsigned> rb_h_counts;
+  HostBuf<uint4> rb_h_recs;
   // fmd_batch_export_rds_device drains a queue asynchronously on the caller's stream: the event tells
   // the next call that appends to the same queue (NSLOT calls later) when it is empty
   Event ev_drained[NSLOT];
@@ -343,6 +361,7 @@ struct fmd_batch
     bool status_after_rds = false;     // the two halves are on different streams: the status record waits for EV_RDS
     hipEvent_t prev_aud = nullptr;     // ... and the bit recovery for the previous call's status record
     uint32_t call_index = 0;
+    int rb_mode = 0;                   // FMD_RDS_BLOCKS_*: which form of the bit recovery the call launches
     void* d_audio = nullptr;           // rows of the call's output format (pcm: FMD_PCM_*), stride in its elements
     int pcm = 0;
     size_t audio_stride = 0;
@@ -2837,6 +2856,218 @@ int fmd_batch_read_pcm_clipped(fmd_batch* b, unsigned first_channel, unsigned n,
     const unsigned run = std::min(first_channel + n - c, ob->C - lc);
     HIPCHK(hipMemcpy(out + (c - first_channel), ob->pcm_clip.p + lc, size_t(run) * sizeof(uint64_t),
                      hipMemcpyDeviceToHost));
+    c += run;
+  }
+  return FMD_OK;
+}
+
+/* ---- the block observation (fmd.h) ---- */
+static_assert(sizeof(fmd_rds_block) == 24 && sizeof(fmd_rds_quality) == 32, "the records of fmd.h");
+static_assert(sizeof(fmd_rds_quality) == fmd::RQ_N * sizeof(unsigned), "one word per counter, in the kernel's order");
+
+/* the batches with buffers of their own behind a caller-facing one */
+static std::vector<fmd_batch*> rb_owners(fmd_batch* b)
+{
+  std::vector<fmd_batch*> xs;
+  if (is_shell(b))
+    for (auto& sb : b->subs)
+      xs.push_back(sb.get());
+  else
+    xs.push_back(b);
+  return xs;
+}
+
+int fmd_batch_set_rds_blocks(fmd_batch* b, int mode, unsigned queue_records)
+{
+  if (!b)
+    return fail(FMD_ERR_ARG, "fmd_batch_set_rds_blocks: null batch");
+  if (mode < FMD_RDS_BLOCKS_OFF || mode > FMD_RDS_BLOCKS_RECORD)
+    return fail(FMD_ERR_ARG, "fmd_batch_set_rds_blocks: mode must be FMD_RDS_BLOCKS_OFF, _COUNT or _RECORD (0..2)");
+  if (queue_records && b->rb_cap && queue_records != b->rb_cap)
+    return fail(FMD_ERR_ARG, "fmd_batch_set_rds_blocks: the block queues hold " + std::to_string(b->rb_cap) +
+                                 " records since the first call that enabled mode 2; " +
+                                 std::to_string(queue_records) + " refused");
+  if (mode != FMD_RDS_BLOCKS_OFF)
+  {
+    HIPCHK(hipSetDevice(b->device));
+    const std::vector<fmd_batch*> xs = rb_owners(b);
+    for (fmd_batch* x : xs)
+      if (!x->rb_quality.p && x->rb_quality.alloc(size_t(fmd::RQ_N) * x->CP))
+        return fail(FMD_ERR_DEVICE, "fmd_batch_set_rds_blocks: allocation of the counters failed");
+    if (mode == FMD_RDS_BLOCKS_RECORD && !b->rb_cap)
+    {
+      for (fmd_batch* x : xs)
+      {
+        const unsigned cap = queue_records ? queue_records : std::max(8192u, 4u * x->C);
+        int bad = x->rb_counts.alloc(fmd_batch::NSLOT) | x->rb_h_counts.alloc(fmd_batch::NSLOT);
+        for (int q = 0; q < fmd_batch::NSLOT && !bad; q++)
+          bad |= x->rb_queue[q].alloc(size_t(2) * cap);
+        if (bad)
+        { // nothing half-made stays: the batch is as before the call
+          for (fmd_batch* y : xs)
+          {
+            for (auto& qb : y->rb_queue)
+              qb.release();
+            y->rb_counts.release();
+            y->rb_h_counts.release();
+            y->rb_cap = 0;
+          }
+          return fail(FMD_ERR_DEVICE, "fmd_batch_set_rds_blocks: allocation of the block queues failed");
+        }
+        x->rb_cap = cap;
+      }
+      b->rb_cap = queue_records ? queue_records : xs[0]->rb_cap;
+    }
+  }
+  b->rb_mode = mode;
+  for (auto& sb : b->subs)
+    sb->rb_mode = mode;
+  return FMD_OK;
+}
+
+int fmd_batch_get_rds_blocks(const fmd_batch* b)
+{
+  if (!b)
+    return fail(FMD_ERR_ARG, "fmd_batch_get_rds_blocks: null batch");
+  return b->rb_mode;
+}
+
+int fmd_batch_collect_rds_blocks(fmd_batch* b, fmd_rds_block* out, unsigned cap, int lag, void* stream_,
+                                 unsigned* lost)
+{
+  if (!b || lag < 0 || lag > 4 || (!out && cap))
+    return fail(FMD_ERR_ARG, "fmd_batch_collect_rds_blocks: bad argument (lag must be 0..4)");
+  if (lost)
+    *lost = 0;
+  if (!b->rb_cap) // mode 2 was never enabled: no queue exists
+    return 0;
+  hipStream_t stream = static_cast<hipStream_t>(stream_);
+  HIPCHK(hipSetDevice(b->device));
+  // the same two synchronisations as fmd_batch_collect_rds_lagged, whatever the number of queues and sub-batches
+  struct Drain
+  {
+    fmd_batch* x;
+    unsigned ch0;
+    int todo[fmd_batch::NSLOT], ntodo = 0;
+    unsigned cnt[fmd_batch::NSLOT];
+    size_t total = 0;
+  };
+  std::vector<Drain> drains;
+  {
+    const std::vector<fmd_batch*> xs = rb_owners(b);
+    for (size_t k = 0; k < xs.size(); k++)
+      drains.push_back(Drain{xs[k], is_shell(b) ? b->sub_ch0[k] : 0u});
+  }
+  bool any = false, any_recs = false;
+  for (Drain& d : drains)
+  {
+    fmd_batch* x = d.x;
+    for (int q = 0; q < fmd_batch::NSLOT; q++)
+      if (x->rb_dirty[q] && slot_eligible(x, q, lag))
+      {
+        HIPCHK(hipStreamWaitEvent(stream, x->cev[q][fmd_batch::EV_RDS], 0));
+        d.todo[d.ntodo++] = q;
+      }
+    if (d.ntodo)
+      HIPCHK(hipMemcpyAsync(x->rb_h_counts.p, x->rb_counts.p, fmd_batch::NSLOT * sizeof(unsigned),
+                            hipMemcpyDeviceToHost, stream));
+    any = any || d.ntodo > 0;
+  }
+  std::vector<fmd_rds_block> recs;
+  uint64_t dropped = 0;
+  if (any)
+  {
+    HIPCHK(hipStreamSynchronize(stream));
+    for (Drain& d : drains)
+    {
+      fmd_batch* x = d.x;
+      for (int i = 0; i < d.ntodo; i++)
+      {
+        const unsigned n = x->rb_h_counts.p[d.todo[i]];
+        d.cnt[i] = std::min(n, x->rb_cap); // a full queue kept its first rb_cap records
+        dropped += n - d.cnt[i];
+        d.total += d.cnt[i];
+      }
+      if (2 * d.total > x->rb_h_recs.n && x->rb_h_recs.alloc(2 * std::max<size_t>(d.total, size_t(4) * x->C + 1024)))
+        return fail(FMD_ERR_DEVICE, "fmd_batch_collect_rds_blocks: page-locked staging allocation failed");
+      size_t at = 0;
+      for (int i = 0; i < d.ntodo; i++)
+      {
+        const int q = d.todo[i];
+        if (d.cnt[i])
+          HIPCHK(hipMemcpyAsync(x->rb_h_recs.p + 2 * at, x->rb_queue[q].p, size_t(d.cnt[i]) * 2 * sizeof(uint4),
+                                hipMemcpyDeviceToHost, stream));
+        if (x->rb_h_counts.p[q])
+          HIPCHK(hipMemsetAsync(x->rb_counts.p + q, 0, sizeof(unsigned), stream));
+        at += d.cnt[i];
+      }
+      any_recs = any_recs || d.ntodo > 0;
+    }
+    if (any_recs)
+      HIPCHK(hipStreamSynchronize(stream));
+    for (Drain& d : drains)
+    {
+      for (int i = 0; i < d.ntodo; i++)
+        d.x->rb_dirty[d.todo[i]] = false;
+      const size_t at = recs.size();
+      recs.resize(at + d.total);
+      for (size_t i = 0; i < d.total; i++)
+      { // the device record's first 24 bytes are the caller's record
+        std::memcpy(&recs[at + i], d.x->rb_h_recs.p + 2 * i, sizeof(fmd_rds_block));
+        recs[at + i].channel += d.ch0;
+      }
+    }
+  }
+  if (int rc = check_device_errors(b))
+    return rc;
+  std::sort(recs.begin(), recs.end(), [](const fmd_rds_block& x, const fmd_rds_block& y) {
+    if (x.call_index != y.call_index)
+      return x.call_index < y.call_index;
+    if (x.channel != y.channel)
+      return x.channel < y.channel;
+    return int32_t(x.bit_index - y.bit_index) < 0; // (wrapping: the counter is modulo 2^32)
+  });
+  const size_t k = std::min<size_t>(recs.size(), cap);
+  if (k)
+    std::memcpy(out, recs.data(), k * sizeof(fmd_rds_block));
+  dropped += recs.size() - k;
+  if (lost)
+    *lost = unsigned(std::min<uint64_t>(dropped, 0xFFFFFFFFu));
+  return int(k);
+}
+
+int fmd_batch_read_rds_quality(fmd_batch* b, unsigned first_channel, unsigned n, fmd_rds_quality* out)
+{
+  if (!b || !out)
+    return fail(FMD_ERR_ARG, "fmd_batch_read_rds_quality: null argument");
+  if (first_channel > b->C || n > b->C - first_channel)
+    return fail(FMD_ERR_ARG, "fmd_batch_read_rds_quality: channels [" + std::to_string(first_channel) + ", " +
+                                 std::to_string(size_t(first_channel) + n) + ") out of range (" +
+                                 std::to_string(b->C) + " channels)");
+  std::memset(out, 0, size_t(n) * sizeof(fmd_rds_quality));
+  unsigned probe = 0;
+  if (!n || !owner_of(b, 0, &probe)->rb_quality.p) // never enabled: every counter is zero, and no device call
+    return FMD_OK;
+  HIPCHK(hipSetDevice(b->device));
+  if (int rc = wait_impl(b, 0, nullptr, false); rc < 0)
+    return rc;
+  HIPCHK(hipStreamSynchronize(nullptr));
+  std::vector<unsigned> rows;
+  for (unsigned c = first_channel; c < first_channel + n;)
+  { // run by run of channels with one owner (a shell: its sub-batches); the counters' rows, then transposed
+    unsigned lc = 0;
+    const fmd_batch* ob = owner_of(b, c, &lc);
+    const unsigned run = std::min(first_channel + n - c, ob->C - lc);
+    rows.resize(size_t(fmd::RQ_N) * run);
+    HIPCHK(hipMemcpy2D(rows.data(), size_t(run) * sizeof(unsigned), ob->rb_quality.p + lc,
+                       size_t(ob->CP) * sizeof(unsigned), size_t(run) * sizeof(unsigned), fmd::RQ_N,
+                       hipMemcpyDeviceToHost));
+    for (unsigned i = 0; i < run; i++)
+    {
+      uint32_t* w = reinterpret_cast<uint32_t*>(out + (c - first_channel) + i);
+      for (int q = 0; q < fmd::RQ_N; q++)
+        w[q] = rows[size_t(q) * run + i];
+    }
     c += run;
   }
   return FMD_OK;

@@ -139,8 +139,25 @@ void launch_light_rds(fmd_batch* b, const fmd_batch::LightJob& j, hipStream_t s)
   // kernel is about to overwrite -- it goes first (its call's audio half ended a period ago: never a wait in practice)
   if (j.prev_aud && hipStreamWaitEvent(s, j.prev_aud, 0) != hipSuccess)
     mark_failed(b, "hipStreamWaitEvent failed in front of the bit recovery of a call");
-  hipLaunchKernelGGL(fmd::k_rds_bits, dim3(CP / 64), dim3(64, 1), 0, s, b->rmf.p, j.R, C, CP, k, b->st,
-                     j.call_index, b->queue[j.es].p, b->qcount(j.es), b->queue_cap, b->tap_sync.p, b->write_taps);
+  if (j.rb_mode == FMD_RDS_BLOCKS_OFF)
+    hipLaunchKernelGGL(fmd::k_rds_bits, dim3(CP / 64), dim3(64, 1), 0, s, b->rmf.p, j.R, C, CP, k, b->st,
+                       j.call_index, b->queue[j.es].p, b->qcount(j.es), b->queue_cap, b->tap_sync.p, b->write_taps);
+  else
+  { // the observing forms (fmd_batch_set_rds_blocks): the same decoder, plus counters / block records
+    fmd::RdsObs ob;
+    ob.quality = b->rb_quality.p;
+    const bool record = j.rb_mode == FMD_RDS_BLOCKS_RECORD;
+    if (record)
+    {
+      ob.blocks = b->rb_queue[j.es].p;
+      ob.block_count = b->rb_counts.p + j.es;
+      ob.block_cap = b->rb_cap;
+      b->rb_dirty[j.es] = true;
+    }
+    hipLaunchKernelGGL(record ? fmd::k_rds_bits_obs<true> : fmd::k_rds_bits_obs<false>, dim3(CP / 64), dim3(64, 1), 0,
+                       s, b->rmf.p, j.R, C, CP, k, b->st, j.call_index, b->queue[j.es].p, b->qcount(j.es),
+                       b->queue_cap, b->tap_sync.p, b->write_taps, ob);
+  }
   if (j.events && hipEventRecord(b->cev[j.es][fmd_batch::EV_RDS], s) != hipSuccess)
     mark_failed(b, "hipEventRecord failed behind the RDS part of a call");
 }
@@ -992,6 +1009,7 @@ int process_device_impl(fmd_batch* b, const void* d_iq, IqFormat fmt, size_t iq_
   job.es = es;
   job.sq = sq;
   job.call_index = ci;
+  job.rb_mode = b->rb_mode;
   job.d_audio = d_audio;
   job.pcm = pcm;
   job.audio_stride = audio_channel_stride;

@@ -563,6 +563,11 @@ int load_replace(fmd_batch* b, const StateView& v, char* dev_p, const char* who)
     x->imports.clear();
     take_clock(x, v);
     HIPCHK(hipMemset(x->queue_counts.p, 0, fmd_batch::NSLOT * sizeof(unsigned))); // queued groups are dropped
+    if (x->rb_counts.p) // ... and queued block records (the counters of the observation stay: not the decoder's)
+    {
+      HIPCHK(hipMemset(x->rb_counts.p, 0, fmd_batch::NSLOT * sizeof(unsigned)));
+      std::memset(x->rb_dirty, 0, sizeof(x->rb_dirty));
+    }
     if (x->h_err.p)
     {
       __atomic_store_n(&x->h_err.p[0], 0u, __ATOMIC_RELEASE);

@@ -902,7 +902,11 @@ __global__ __launch_bounds__(256) void k_ring_fir4_org(const E* __restrict__ in,
 /* K5: RDS recurrences at the RDS rate.  The matched filter between the two serial kernels     */
 /*     (cFirFilter::Process(real), FirFilter.cpp:360-377) runs time-parallel in k_ring_fir.      */
 /* ------------------------------------------------------------------------------------------ */
-__device__ __forceinline__ uint32_t rds_check_block(uint32_t& in_bits, uint32_t offset, bool fec)
+/* OBS (the observing forms of the bit recovery): *pre takes the syndrome before the error correction, *flips the
+ * bits the Meggitt loop flipped (the reference's correctedbits, RDSProcess.cpp:398-410: counted and never used). */
+template <bool OBS = false>
+__device__ __forceinline__ uint32_t rds_check_block(uint32_t& in_bits, uint32_t offset, bool fec,
+                                                    uint32_t* pre = nullptr, unsigned* flips = nullptr)
 {
   const uint32_t parckh[16] = {0x2DC, 0x16E, 0x0B7, 0x287, 0x39F, 0x313, 0x355, 0x376,
                                0x1BB, 0x201, 0x3DC, 0x1EE, 0x0F7, 0x2A7, 0x38F, 0x31B};
@@ -916,6 +920,8 @@ __device__ __forceinline__ uint32_t rds_check_block(uint32_t& in_bits, uint32_t 
     tb <<= 1;
   }
   syn ^= offset;
+  if constexpr (OBS)
+    *pre = syn;
   if (syn && fec)
   {
     uint32_t mask = 1u << 25;
@@ -927,6 +933,8 @@ __device__ __forceinline__ uint32_t rds_check_block(uint32_t& in_bits, uint32_t 
         {
           in_bits ^= mask;
           syn <<= 1;
+          if constexpr (OBS)
+            (*flips)++;
         }
         else
         {
@@ -1016,199 +1024,55 @@ __global__ __launch_bounds__(64 * RP_WAVES) void k_rds_pll(const float2* __restr
  *      a bit. */
 constexpr int RB_TILE = 32;
 
+/* What the observing forms of the bit recovery (k_rds_bits_obs; fmd_batch_set_rds_blocks)
+ * take beside k_rds_bits' arguments.  The counters are the observation's and not the decoder's: an array of their
+ * own, [RQ_N][CP] in coalesced rows, that no reset, retune, import or load touches.  A block record is 32 bytes on
+ * the device, two 16-byte stores: the 24 bytes of fmd_rds_block and 8 of padding. */
+enum RdsQuality
+{
+  RQ_BITS,
+  RQ_CANDIDATES,
+  RQ_BLOCKS,
+  RQ_CORRECTED,
+  RQ_FAILED,
+  RQ_ACQUIRED,
+  RQ_LOST,
+  RQ_GROUPS,
+  RQ_N
+};
+struct RdsObs
+{
+  unsigned* quality = nullptr;     // [RQ_N][CP]
+  uint4* blocks = nullptr;         // the call's block queue, two uint4 per record
+  unsigned* block_count = nullptr; // records appended so far (counts on past block_cap: the host works out the loss)
+  unsigned block_cap = 0;
+};
+
+/* The bit recovery proper, and its two observing forms: ONE text (fmd_rds_bits.inc), like the audio tail's.  A call
+ * submitted with the block observation off launches k_rds_bits, which is what it always was. */
 __global__ __launch_bounds__(256) void k_rds_bits(const float* __restrict__ mf, unsigned R, unsigned C,
                                                  unsigned CP, RdsConsts k, ChannelState st,
                                                  uint32_t call_index, RdsGroupRec* __restrict__ queue,
                                                  unsigned* __restrict__ queue_count, unsigned queue_cap,
                                                  float* __restrict__ tap_sync, int write_taps)
 {
-  __builtin_amdgcn_s_setprio(3);
-  const unsigned c = (blockIdx.x * blockDim.y + threadIdx.y) * 64 + threadIdx.x; // (blockDim.y groups: light_pack)
-  if (c >= C)
-    return;
-  const uint32_t offs[8] = {0x3D8, 0x3D4, 0x25C, 0x258, 0x3D8, 0x3D4, 0x3CC, 0x258};
-  float w1 = st.F(F_R_W1)[c], w2 = st.F(F_R_W2)[c];
-  float last_sync = st.F(F_R_LAST_SYNC)[c], last_slope = st.F(F_R_LAST_SLOPE)[c],
-        last_data = st.F(F_R_LAST_DATA)[c];
-  int last_bit = st.I(I_R_LAST_BIT)[c];
-  uint32_t bits = (uint32_t)st.I(I_R_BITS)[c];
-  int block = st.I(I_R_BLOCK)[c], bitpos = st.I(I_R_BITPOS)[c], state = st.I(I_R_STATE)[c],
-      boff = st.I(I_R_BOFF)[c], errors = st.I(I_R_ERRORS)[c];
-  uint16_t bd[4];
-#pragma unroll
-  for (int q = 0; q < 4; q++)
-    bd[q] = st.r_data[(size_t)q * CP + c];
-  uint32_t seq = (uint32_t)st.I(I_R_SEQ)[c];
+  constexpr int OBS = 0;
+  const RdsObs ob{};
+#include "fmd_rds_bits.inc"
+}
 
-  float dnext[RB_TILE];
-#pragma unroll
-  for (unsigned u = 0; u < RB_TILE; u++)
-    dnext[u] = mf[(size_t)min(u, R - 1) * CP + c];
-  for (unsigned i0 = 0; i0 < R; i0 += RB_TILE)
-  {
-    const unsigned cnt = min((unsigned)RB_TILE, R - i0);
-    float din[RB_TILE];
-#pragma unroll
-    for (unsigned u = 0; u < RB_TILE; u++)
-      din[u] = dnext[u];
-#pragma unroll
-    for (unsigned u = 0; u < RB_TILE; u++) // the next tile's loads are in flight during this tile's recurrence
-      dnext[u] = mf[(size_t)min(i0 + RB_TILE + u, R - 1) * CP + c];
-    uint64_t qbits = 0; // bits sliced in this tile, oldest in the MSBs
-    int qcount = 0;
-#pragma unroll
-    for (unsigned u = 0; u < RB_TILE; u++)
-    {
-      if (u >= cnt)
-        break;
-      const float d = din[u];
-      const float mag = d * d;
-      const float w0 = mag - k.bs_a1 * w1 - k.bs_a2 * w2;
-      const float sv = k.bs_b0 * w0 + k.bs_b1 * w1 + k.bs_b2 * w2;
-      w2 = w1;
-      w1 = w0;
-      if (write_taps)
-        tap_sync[(size_t)(i0 + u) * CP + c] = sv;
-      const float slope = sv - last_sync;
-      last_sync = sv;
-      if ((slope < 0.0f) && (last_slope * slope) < 0.0f)
-      { // top of the sync sine: read the previous matched-filter sample, differential decode
-        const int bit = (last_data >= 0) ? 1 : 0;
-        qbits = (qbits << 1) | (uint64_t)(bit ^ last_bit);
-        qcount++;
-        last_bit = bit;
-      }
-      last_data = d;
-      last_slope = slope;
-    }
-
-    while (__any(qcount > 0))
-    {
-      if (qcount > 0)
-      {
-        qcount--;
-        const uint32_t nb = (uint32_t)((qbits >> qcount) & 1u);
-        bits = (bits << 1) | nb;
-        bool emit = false;
-        if (state == 0)
-        { // BITSYNC: look for a clean block A at every bit position
-          if (!rds_check_block(bits, offs[0], false))
-          {
-            bitpos = 0;
-            boff = 0;
-            bd[0] = (uint16_t)(bits >> 10);
-            block = 1;
-            state = 1;
-          }
-        }
-        else if (++bitpos >= 26)
-        {
-          bitpos = 0;
-          if (state == 3)
-          { // GROUPRESYNC: skip to the start of the next group
-            if (++block > 3)
-            {
-              block = 0;
-              state = 2;
-            }
-          }
-          else
-          {
-            const uint32_t bad = rds_check_block(bits, offs[block + boff], state == 2);
-            if (bad)
-            {
-              if (state == 1)
-                state = 0;
-              else
-              {
-                errors++;
-                if (errors > 0) // BLOCK_ERROR_LIMIT 0
-                  state = 0;
-                else
-                {
-                  if (++block > 3)
-                    block = 0;
-                  if (block != 0)
-                    state = 3;
-                }
-              }
-            }
-            else
-            {
-              const uint16_t word = (uint16_t)(bits >> 10);
-              if (block == 0)
-                bd[0] = word;
-              else if (block == 1)
-                bd[1] = word;
-              else if (block == 2)
-                bd[2] = word;
-              else
-                bd[3] = word;
-              boff = (block == 1 && (word & 0x0800)) ? 4 : 0;
-              if (state == 1)
-              { // BLOCKSYNC: four good blocks in sequence confirm the bit position
-                if (block >= 3)
-                {
-                  block = 0;
-                  errors = 0;
-                  state = 2;
-                  emit = true;
-                }
-                else
-                  block++;
-              }
-              else if (++block > 3)
-              { // GROUPDECODE: a complete group
-                block = 0;
-                errors = 0;
-                emit = true;
-              }
-            }
-          }
-        }
-        if (emit)
-        {
-          const unsigned slot = atomicAdd(queue_count, 1u);
-          if (slot < queue_cap)
-          {
-            RdsGroupRec r;
-            r.channel = c;
-            r.call_index = call_index;
-            r.seq = seq;
-            r.blocks[0] = bd[0];
-            r.blocks[1] = bd[1];
-            r.blocks[2] = bd[2];
-            r.blocks[3] = bd[3];
-            queue[slot] = r;
-          }
-          else
-            dev_error(st.err + 1, DEVERR_RDS_QUEUE_FULL);
-          seq++;
-        }
-      }
-    }
-  }
-
-  st.F(F_R_W1)[c] = w1;
-  st.F(F_R_W2)[c] = w2;
-  st.F(F_R_LAST_SYNC)[c] = last_sync;
-  st.F(F_R_LAST_SLOPE)[c] = last_slope;
-  st.F(F_R_LAST_DATA)[c] = last_data;
-  st.I(I_R_LAST_BIT)[c] = last_bit;
-  st.I(I_R_BITS)[c] = (int)bits;
-  st.I(I_R_BLOCK)[c] = block;
-  st.I(I_R_BITPOS)[c] = bitpos;
-  st.I(I_R_STATE)[c] = state;
-  // the status snapshot's RDS state (not a cFmDecoder getter) is this kernel's to write: a word of its
-  // own, outside the audio tail's sequence-locked record, so that the tail need not wait for the RDS
-  // chain where the two run on different streams
-  st.ds[(size_t)HS_R_STATE * st.CP + c] = (unsigned)state;
-  st.I(I_R_BOFF)[c] = boff;
-  st.I(I_R_ERRORS)[c] = errors;
-#pragma unroll
-  for (int q = 0; q < 4; q++)
-    st.r_data[(size_t)q * CP + c] = bd[q];
-  st.I(I_R_SEQ)[c] = (int)seq;
+/* The bit recovery of a call submitted with the block observation on (fmd_batch_set_rds_blocks): the same decoder,
+ * bit for bit, plus the channel's reception counters (RECORD false: FMD_RDS_BLOCKS_COUNT) and a record of every
+ * block decision in the call's block queue (RECORD true: FMD_RDS_BLOCKS_RECORD). */
+template <bool RECORD>
+__global__ __launch_bounds__(256) void k_rds_bits_obs(const float* __restrict__ mf, unsigned R, unsigned C,
+                                                     unsigned CP, RdsConsts k, ChannelState st,
+                                                     uint32_t call_index, RdsGroupRec* __restrict__ queue,
+                                                     unsigned* __restrict__ queue_count, unsigned queue_cap,
+                                                     float* __restrict__ tap_sync, int write_taps, RdsObs ob)
+{
+  constexpr int OBS = RECORD ? 2 : 1;
+#include "fmd_rds_bits.inc"
 }
 
 } // namespace fmd
