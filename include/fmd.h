@@ -518,8 +518,10 @@ int fmd_batch_debug_capture_walk(fmd_batch* b, int on);
  *  - Nothing is synchronised: the call applies the edits on the device, behind the calls before it (a call
  *    with edits waits for its predecessors to complete instead of overlapping them).
  *  - Groups of calls before the edit go through the channel's old group decoder state, also when they are
- *    collected later; the group decoder is reset between the last call before the edit and the first behind
- *    it.  fmd_batch_get_status's tuning_offset is that of the call the snapshot is of.
+ *    collected later; between the last call before the edit and the first behind it the channel gets a new group
+ *    decoder, as the new cFmDecoder would bring one: its UECP sequence counter starts at 0 and it reports the PTY
+ *    again (a reset, fmd_batch_reset_channels, keeps both, as cFmDecoder::Reset does).
+ *    fmd_batch_get_status's tuning_offset is that of the call the snapshot is of.
  *  - FMD_ERR_ARG: a null batch or list, a channel out of range or listed twice, a failed batch (fmd_last_error
  *    says which).  FMD_ERR_STATE: retuning was not enabled.  Same threading rule as the process calls; the
  *    getters stay safe from any thread.

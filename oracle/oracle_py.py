@@ -228,21 +228,23 @@ class OracleDecoder:
             "rds_sync": arr(t.rds_sync, t.n_rds),
         }
 
-    def rds_groups(self):
+    def rds_groups(self, since=0):
+        """(call index, blocks) of the groups decoded so far, from group number `since` on"""
         out = []
         n = lib().fmo_rds_group_count(self._h)
         blk = (C.c_uint16 * 4)()
         ci = C.c_uint()
-        for i in range(n):
+        for i in range(since, n):
             lib().fmo_rds_group_get(self._h, i, blk, C.byref(ci))
             out.append((ci.value, tuple(int(x) for x in blk)))
         return out
 
-    def uecp_frames(self):
+    def uecp_frames(self, since=0):
+        """the UECP frames delivered so far, from frame number `since` on"""
         out = []
         n = lib().fmo_uecp_frame_count(self._h)
         buf = (C.c_uint8 * 270)()
-        for i in range(n):
+        for i in range(since, n):
             k = lib().fmo_uecp_frame_get(self._h, i, buf, 270)
             out.append(bytes(buf[:k]))
         return out

@@ -419,6 +419,8 @@ struct fmd_batch
   // per channel: (first call, shift) of every call with a retune or reset in front of it, call order; empty until
   // the first edit (enable_retune or reset_channels sizes it)
   std::vector<std::vector<std::pair<uint32_t, int>>> shift_log;
+  // per channel: the calls of shift_log with a retune in front of them (the others: resets and imports), call order
+  std::vector<std::vector<uint32_t>> retune_log;
   std::vector<uint32_t> gdec_epoch;    // per channel: the edit whose reset the group decoder has seen
   struct Edit
   {
@@ -1706,8 +1708,31 @@ int shift_at(fmd_batch* b, unsigned c, uint32_t ci)
   return s;
 }
 
-/* The group decoder of channel c before a group of call ci: reset once at the first group of a call at or behind
- * a retune or reset of the channel (groups of earlier calls, collected late, still go through the old state). */
+/* What the edits of channel c in front of the calls (epoch, ci] ask of its group decoder: 0 nothing; 1 a reset
+ * (fmd_batch_reset_channels: cFmDecoder::Reset keeps the UECP sequence counter, the last PTY and the A/B flags); 2 a
+ * new decoder (a retune: the decoder created with the new shift has a group decoder no group has reached, and a reset
+ * of that one changes nothing).  *k_last: the last of those calls. */
+int gdec_edit_between(fmd_batch* b, unsigned c, uint32_t epoch, uint32_t ci, uint32_t* k_last)
+{
+  std::lock_guard<std::mutex> lk(b->log_mu);
+  *k_last = 0;
+  if (c >= b->shift_log.size())
+    return 0;
+  for (const auto& [k, v] : b->shift_log[c])
+    if (k <= ci)
+      *k_last = k;
+  if (*k_last <= epoch)
+    return 0;
+  if (c < b->retune_log.size())
+    for (uint32_t k : b->retune_log[c])
+      if (k > epoch && k <= *k_last)
+        return 2;
+  return 1;
+}
+
+/* The group decoder of channel c before a group of call ci: reset (a reset) or replaced by a new one (a retune) once
+ * at the first group of a call at or behind an edit of the channel (groups of earlier calls, collected late, still
+ * go through the old state). */
 void gdec_follow_edits(fmd_batch* b, unsigned c, uint32_t ci)
 {
   // the decoders of imported channels (fmd_batch_import_channels) whose first call has come, in call order
@@ -1724,15 +1749,11 @@ void gdec_follow_edits(fmd_batch* b, unsigned c, uint32_t ci)
       b->gdec_imports.erase(it);
   }
   uint32_t k_last = 0;
+  if (const int what = gdec_edit_between(b, c, b->gdec_epoch[c], ci, &k_last))
   {
-    std::lock_guard<std::mutex> lk(b->log_mu);
-    for (const auto& [k, v] : b->shift_log[c])
-      if (k <= ci)
-        k_last = k;
-  }
-  if (k_last > b->gdec_epoch[c])
-  {
-    if (b->gdec[c])
+    if (what == 2)
+      b->gdec[c].reset(); // (the caller creates the new one with the first group)
+    else if (b->gdec[c])
       b->gdec[c]->reset();
     b->gdec_epoch[c] = k_last;
   }
@@ -2259,6 +2280,11 @@ int fmd_batch_retune_channels(fmd_batch* b, const unsigned* channels, const int*
       log.back().second = shifts[i];
     else
       log.emplace_back(k, shifts[i]);
+    if (b->retune_log.size() < b->C)
+      b->retune_log.resize(b->C);
+    auto& rlog = b->retune_log[channels[i]];
+    if (rlog.empty() || rlog.back() != k)
+      rlog.push_back(k);
   }
   b->edits_pending = true;
   return FMD_OK;

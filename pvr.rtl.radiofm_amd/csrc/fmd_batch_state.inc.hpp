@@ -261,10 +261,10 @@ int drain_batch(fmd_batch* b)
 }
 
 /* the group decoder channel c continues with behind every call submitted so far (the one an edit still has to
- * reset or bring in included); *fresh: a reset one */
-const fmd::GroupDecoder* effective_gdec(fmd_batch* b, unsigned c, bool* fresh)
+ * reset, replace or bring in included); *fresh: 1 a reset one, 2 a new one (gdec_edit_between) */
+const fmd::GroupDecoder* effective_gdec(fmd_batch* b, unsigned c, int* fresh)
 {
-  *fresh = false;
+  *fresh = 0;
   const fmd::GroupDecoder* g = b->gdec[c].get();
   uint32_t epoch = c < b->gdec_epoch.size() ? b->gdec_epoch[c] : 0u;
   if (auto it = b->gdec_imports.find(c); it != b->gdec_imports.end() && !it->second.empty())
@@ -273,15 +273,8 @@ const fmd::GroupDecoder* effective_gdec(fmd_batch* b, unsigned c, bool* fresh)
     epoch = std::max(epoch, it->second.back().k);
   }
   uint32_t k_last = 0;
-  {
-    std::lock_guard<std::mutex> lk(b->log_mu);
-    if (c < b->shift_log.size())
-      for (const auto& [k, v] : b->shift_log[c])
-        k_last = k;
-  }
-  if (k_last > epoch)
-    *fresh = true;
-  return g;
+  *fresh = gdec_edit_between(b, c, epoch, ~0u, &k_last);
+  return *fresh == 2 ? nullptr : g;
 }
 
 /* header, oscillator entries and host records of the listed channels (null: all) of b into blob; the payload's
@@ -321,7 +314,7 @@ void write_host_part(fmd_batch* b, const unsigned* channels, unsigned n, uint32_
     unsigned w[fmd::HS_WORDS] = {};
     (void)host_status_read(ob, lc, w); // (no call in flight: never torn)
     std::memcpy(r.status, w, sizeof(w));
-    bool fresh = false;
+    int fresh = 0;
     const fmd::GroupDecoder* g = effective_gdec(b, c, &fresh);
     r.has_gdec = g ? 1u : 0u;
     std::memcpy(p, &r, sizeof(r));
@@ -522,6 +515,8 @@ int load_replace(fmd_batch* b, const StateView& v, char* dev_p, const char* who)
   {
     std::lock_guard<std::mutex> lk(b->log_mu);
     for (auto& log : b->shift_log)
+      log.clear();
+    for (auto& log : b->retune_log)
       log.clear();
   }
   std::fill(b->gdec_epoch.begin(), b->gdec_epoch.end(), 0u);

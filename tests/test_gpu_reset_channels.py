@@ -36,12 +36,13 @@ def _shift_of(f_offset):
     return -int(round(f_offset / 100e3))
 
 
-def _params(pkg):
-    return pkg.make_params(FS, 0.0, 48000.0, 15000.0, D, table_size=T)
+def _params(pkg, fs=FS, d=D, t=T, order=0):
+    return pkg.make_params(fs, 0.0, 48000.0, 15000.0, d, table_size=t, if_filter_order=order)
 
 
-def _oracle(oracle, shift):
-    return oracle.OracleDecoder(FS, 0.0, 48000.0, 15000.0, D, table_size=T, tuning_shift=int(shift))
+def _oracle(oracle, shift, fs=FS, d=D, t=T, order=0):
+    return oracle.OracleDecoder(fs, 0.0, 48000.0, 15000.0, d, table_size=t, if_filter_order=order,
+                                tuning_shift=int(shift))
 
 
 def _bits(a, b):

@@ -64,14 +64,20 @@ class Run:
     getters, the status call index, the audio meter, the RDS groups with their call index, UECP frames and names."""
 
     def __init__(self, pkg, shifts=SHIFTS0, enable=False, debug=None, conc=None, prof=None, pcm=None, cmap=None,
-                 n_cap=1, params=None):
+                 n_cap=1, params=None, taps=False, keep_phase=False, callbacks=True):
         self.pkg, self.pcm, self.C = pkg, pcm, len(shifts)
-        self.b = pkg.Batch(params or _params(pkg), self.C, tuning_shifts=np.array(shifts, np.int32))
-        self.b.sink.names = _Log()
+        self.b = pkg.Batch(params or _params(pkg), self.C, tuning_shifts=np.array(shifts, np.int32),
+                           record_callbacks=callbacks)
+        if callbacks:
+            self.b.sink.names = _Log()
         if enable:
             self.b.enable_retune()
         for k, v in (debug or {}).items():
             self.b.debug_set(k, v)
+        if keep_phase:
+            self.b.debug_reset_keep_ring_phase(1)
+        if taps:
+            self.b.enable_taps(True)
         if conc is not None:
             self.b.set_concurrency(conc)
         if prof is not None:
@@ -83,16 +89,17 @@ class Run:
         self.s = torch.cuda.current_stream().cuda_stream
         self.rec = []
 
-    def submit(self, block):
-        """one call without waiting; block: [n_cap, 2 n] float32 / uint8 rows (one row: shared).  Returns what
-        finish() needs."""
+    def submit(self, block, samples=None):
+        """one call without waiting; block: [n_cap, 2 n] float32 / uint8 rows (one row: shared); with `samples`, the
+        rows are longer than the call (a row stride of its own).  Returns what finish() needs."""
         x = torch.from_numpy(np.ascontiguousarray(block)).cuda()
         rows = x.reshape(self.n_cap, -1)
-        n = rows.shape[1] // 2
+        stride = rows.shape[1] // 2
+        n = stride if samples is None else samples
         out = torch.zeros((self.C, self.stride), dtype=torch.int16 if self.pcm else torch.float32, device="cuda")
         fmt = self.pkg.FMD_IQ_U8 if x.dtype == torch.uint8 else self.pkg.FMD_IQ_F32
-        nf = self.b.process_device(rows.data_ptr(), n if self.n_cap > 1 else 0, n, out.data_ptr(), self.stride, self.s,
-                                   fmt=fmt, pcm=np.int16 if self.pcm else None)
+        nf = self.b.process_device(rows.data_ptr(), stride if self.n_cap > 1 else 0, n, out.data_ptr(), self.stride,
+                                   self.s, fmt=fmt, pcm=np.int16 if self.pcm else None)
         return x, out, nf
 
     def getters(self):
