@@ -138,6 +138,19 @@ public:
     return n > 0 ? static_cast<unsigned int>(n) : 0u;
   }
 
+  /* Not in the reference: a mono feed at sample_rate_pcm / divisor beside the audio (fmd.h, FMD_FEED_*), what a
+   * speech or fingerprinting model takes.  SetFeed(2 or 3) turns it on and zeroes its history, SetFeed(0) turns it
+   * off; ProcessStreamWithFeed writes *feed_samples 16-bit samples into `feed`, a caller buffer of
+   * samples / divisor + 1 elements at least.  The audio is ProcessStream's. */
+  bool SetFeed(int divisor) { return fmd_batch_set_feed(fmd_decoder_batch(m_dec), divisor) == FMD_OK; }
+  unsigned int ProcessStreamWithFeed(const ComplexType* samples_in, unsigned int samples, float* audio,
+                                     int16_t* feed, unsigned int* feed_samples)
+  {
+    const int n = fmd_process_stream_feed(m_dec, samples_in, FMD_IQ_F32, samples, audio, FMD_PCM_F32, feed,
+                                          FMD_FEED_S16, feed_samples);
+    return n > 0 ? static_cast<unsigned int>(n) : 0u;
+  }
+
   /* Not in the reference: what its block synchroniser computes and drops (fmd.h, "Every RDS block decision").
    * SetRdsBlocks: the observation of every ProcessStream from now on (FMD_RDS_BLOCKS_*); CollectRdsBlocks: the block
    * records queued so far, in order, into `out` (returns their number; *lost: records that did not fit);

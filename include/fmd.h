@@ -114,6 +114,33 @@ extern "C" {
 #define FMD_MPX_F32 0
 #define FMD_MPX_S16 1
 
+/* The mono feed beside the audio: the `feed_format` argument of the _feed entry points.
+ * Speech-to-text, fingerprinting and loudness logging take mono at 16 or 24 kHz; the feed is every channel's mono mix,
+ * low-passed and decimated by D = 2 or 3 (fmd_batch_set_feed) on the device, one row per channel, host byte order:
+ *   FMD_FEED_F32  float     the filter's sum y as is                                              4 bytes
+ *   FMD_FEED_S16  int16_t   fmd_f32_to_s16(y): FMD_PCM_S16's rule, saturating, NaN gives 0        2
+ * There is no clip counter: a saturated sample reads 32767 or -32768.
+ * Definition, exact (no tolerance): for audio frame g of a channel x[g] = (L[g] + R[g]) * 0.5f in float, L and R the
+ * floats the FMD_PCM_F32 call writes for that frame (a frame decoded as mono: the sample itself); g counts the frames
+ * of the calls that asked for the feed since fmd_batch_set_feed, x[g] = 0 for g < 0.  Taps
+ * h = make_kaiser_lp(1.0f, 60.0f, 0.425f * fo, 0.575f * fo, fs) with fs = (float)sample_rate_pcm, fo = fs / D in float
+ * (fmd_design_lp_kaiser with these arguments; fmd_batch_get_feed_taps returns them): 49 taps for D = 2, 73 for D = 3,
+ * stop band from 0.575 fo at -58 dB.  y[n] = sum over k = 0 .. T - 1 of h[k] * x[n D - k], accumulated in float from
+ * acc = 0 with k ascending, acc = acc + h[k] * x[n D - k], multiply and add rounded separately: a numpy float32 loop
+ * over k gives the same bits.  A call whose frames are g0 .. g0 + A - 1 delivers the outputs n with
+ * g0 <= n D < g0 + A: ceil((g0 + A) / D) - ceil(g0 / D) samples, in order, the same number for every channel, known
+ * when the call returns; it may be 0.
+ * Rate: fmd_batch_feed_rate(b) = sample_rate_pcm / D (24 000 or 16 000 at 48 kHz).
+ * The feed is the concatenation of the calls that asked for it: a call without it (d_feed == NULL) is a SPLICE in the
+ * feed, not a gap of zeros -- its frames are never seen by the filter.  A call that asks for the feed leaves channel
+ * state, audio, multiplex, status record, audio meter and RDS groups with the bits of the same call without it.
+ * The feed belongs to the output like the audio meter and the clip counter: fmd_batch_reset, fmd_batch_reset_channels,
+ * retunes, capture switches and imports leave its history and g alone (it goes on with whatever audio the slot now
+ * produces); it is no part of a state blob and fmd_batch_load_state does not touch it.  Only fmd_batch_set_feed zeroes
+ * it.  A format outside 0..1 is refused with FMD_ERR_ARG before anything else is looked at. */
+#define FMD_FEED_F32 0
+#define FMD_FEED_S16 1
+
 /* Constructor arguments of cFmDecoder (FmDecode.h:110-116).  table_size / if_filter_order are
  * the two internal constants BASELINE configs 3 and 5 override; 0 selects the reference
  * values 64 (FmDecode.cpp:249) and 8*downsample (FmDecode.cpp:262). */
@@ -207,6 +234,12 @@ int fmd_process_stream_pcm(fmd_decoder* d, const void* iq, int iq_format, unsign
  * alignment), *mpx_samples = how many were written.  mpx == NULL: fmd_process_stream_pcm. */
 int fmd_process_stream_mpx(fmd_decoder* d, const void* iq, int iq_format, unsigned samples, void* audio,
                            int pcm_format, void* mpx, int mpx_format, unsigned* mpx_samples);
+/* ... or the mono feed beside the audio (FMD_FEED_*; turned on with fmd_batch_set_feed(fmd_decoder_batch(d), 2 or
+ * 3)): feed = caller buffer of fmd_batch_max_feed_samples elements of feed_format (any alignment), *feed_samples =
+ * how many were written.  feed == NULL: fmd_process_stream_pcm.  A feed pointer while the feed is off:
+ * FMD_ERR_STATE. */
+int fmd_process_stream_feed(fmd_decoder* d, const void* iq, int iq_format, unsigned samples, void* audio,
+                            int pcm_format, void* feed, int feed_format, unsigned* feed_samples);
 int fmd_get_status(fmd_decoder* d, fmd_status* st);
 /* The one-channel batch behind a decoder: for the profiling / development calls below (fmd_batch_set_
  * profiling, fmd_batch_get_stage_ms, fmd_batch_debug_*); not for processing (the decoder owns it). */
@@ -239,6 +272,22 @@ unsigned fmd_batch_max_audio_floats(const fmd_batch* b, unsigned samples);
 unsigned fmd_batch_max_mpx_samples(const fmd_batch* b, unsigned samples);
 /* multiplex samples per second: sample_rate_if / downsample */
 double fmd_batch_mpx_rate(const fmd_batch* b);
+
+/* The feed's divisor (FMD_FEED_*).  2 or 3 turns the feed on: the taps are designed and uploaded, the scratch of mono
+ * frames ((taps - 1 + the longest call's frames) x channels floats per 8192 channels) is allocated, the history is
+ * zeroed and g = 0 -- also when the feed was already on, with the same divisor or the other.  0 turns it off and frees
+ * the scratch.  Anything else is FMD_ERR_ARG (any other divisor would be cut off by the design's cap of 75 taps:
+ * -32 dB at 4), as are a null or failed batch.  It applies in front of the next call submitted, like
+ * fmd_batch_set_rds_blocks; it is a setup call and it allocates: it WAITS for the calls in flight. */
+int fmd_batch_set_feed(fmd_batch* b, int divisor);
+/* the divisor (0: off), or a negative error */
+int fmd_batch_get_feed(const fmd_batch* b);
+/* feed samples per second: sample_rate_pcm / divisor; 0 while the feed is off */
+double fmd_batch_feed_rate(const fmd_batch* b);
+/* feed samples per channel a call of `samples` delivers at most: the bound for sizing rows; 0 while the feed is off */
+unsigned fmd_batch_max_feed_samples(const fmd_batch* b, unsigned samples);
+/* the taps in use into out[0 .. cap); returns their number (0 while the feed is off) */
+int fmd_batch_get_feed_taps(const fmd_batch* b, float* out, unsigned cap);
 
 /* Device-resident call, asynchronous on `stream` (hipStream_t, NULL = default stream).
  *  d_iq            complex<float> IQ in HBM; channel c starts at d_iq + 2*c*iq_channel_stride
@@ -290,6 +339,22 @@ int fmd_batch_process_device_mpx(fmd_batch* b, const void* d_iq, int iq_format, 
                                  unsigned* out_samples, void* d_mpx, int mpx_format, size_t mpx_channel_stride,
                                  unsigned* out_mpx_samples, void* stream);
 
+/* The _mpx call with every channel's mono feed beside audio and multiplex (FMD_FEED_*): channel c's row starts
+ * feed_channel_stride elements of feed_format behind channel c - 1's and takes *out_feed_samples samples.
+ * d_feed == NULL makes it exactly the _mpx call: *out_feed_samples = 0, the feed's frame count g does not advance, and
+ * the call launches what the _mpx call launches -- the feed is the concatenation of the calls that asked for it, such a
+ * call is a splice in it, not a gap of zeros.  A non-NULL d_feed while the feed is off is FMD_ERR_STATE.  d_feed must
+ * be 16-byte aligned and feed_channel_stride a multiple of 4 elements (FMD_FEED_F32) or 8 (FMD_FEED_S16) and >= the
+ * call's sample count (fmd_batch_max_feed_samples(b, samples), rounded up, always is), else FMD_ERR_ARG and the batch
+ * is exactly as it was; a feed_format outside 0..1 is refused first.  Nothing is written behind a row's samples.  The
+ * rows are written behind the call's audio tail, in front of its status record: like d_audio's rows they are complete
+ * when the call is (see fmd_batch_process_device_mpx for what that means with concurrency 2). */
+int fmd_batch_process_device_feed(fmd_batch* b, const void* d_iq, int iq_format, size_t iq_channel_stride,
+                                  unsigned samples, void* d_audio, int pcm_format, size_t audio_channel_stride,
+                                  unsigned* out_samples, void* d_mpx, int mpx_format, size_t mpx_channel_stride,
+                                  unsigned* out_mpx_samples, void* d_feed, int feed_format, size_t feed_channel_stride,
+                                  unsigned* out_feed_samples, void* stream);
+
 /* Host-buffer call: copies in, runs fmd_batch_process_device, copies audio out, collects RDS
  * groups and runs the UECP group decoder (callbacks fire here).  Synchronous.  Returns FMD_OK, a
  * negative error, or FMD_WARN_RDS_LOST (once) when groups were dropped because a queue was full:
@@ -315,6 +380,14 @@ int fmd_batch_process_host_mpx(fmd_batch* b, const void* iq, int iq_format, size
                                unsigned samples, void* audio, int pcm_format, size_t audio_channel_stride,
                                unsigned* out_samples, void* mpx, int mpx_format, size_t mpx_channel_stride,
                                unsigned* out_mpx_samples);
+
+/* ... and the feed (FMD_FEED_*) into host rows of any stride >= the call's sample count and any alignment (rows are
+ * copied through a device staging buffer that is sized on first use); feed == NULL: fmd_batch_process_host_mpx. */
+int fmd_batch_process_host_feed(fmd_batch* b, const void* iq, int iq_format, size_t iq_channel_stride,
+                                unsigned samples, void* audio, int pcm_format, size_t audio_channel_stride,
+                                unsigned* out_samples, void* mpx, int mpx_format, size_t mpx_channel_stride,
+                                unsigned* out_mpx_samples, void* feed, int feed_format, size_t feed_channel_stride,
+                                unsigned* out_feed_samples);
 
 /* Which channels deliver rows.  By default a call writes one audio row and -- where it is
  * asked for the multiplex -- one multiplex row per channel.  From the next call submitted on,
@@ -350,6 +423,15 @@ int fmd_batch_select_audio(fmd_batch* b, const unsigned* channels, unsigned n);
 int fmd_batch_select_mpx(fmd_batch* b, const unsigned* channels, unsigned n);
 int fmd_batch_get_audio_selection(fmd_batch* b, unsigned* out, unsigned cap);
 int fmd_batch_get_mpx_selection(fmd_batch* b, unsigned* out, unsigned cap);
+/* The same for the feed rows (d_feed / feed), with fmd_batch_select_mpx's semantics word for word: applied in front
+ * of the next call submitted, nothing waits, calls in flight keep the selection they were submitted with; global
+ * channel numbers, also above 8192 channels; channels == NULL restores one row per channel.  A list with n == 0 makes
+ * the call a call with d_feed == NULL (*out_feed_samples = 0, nothing is written) EXCEPT that the feed's frame count g
+ * advances and the history is kept: d_feed must still be a non-NULL, aligned pointer for the call to count as one that
+ * asked for the feed.  The scratch rows of EVERY channel are written whatever the selection: a channel selected later
+ * has its true history.  The same errors as above. */
+int fmd_batch_select_feed(fmd_batch* b, const unsigned* channels, unsigned n);
+int fmd_batch_get_feed_selection(fmd_batch* b, unsigned* out, unsigned cap);
 
 /* out[i] = the number of audio samples of channel first_channel + i (L and R counted separately) that FMD_PCM_S16
  * calls have saturated since the batch was created: samples whose rounded value lay outside [-32768, 32767] and was
@@ -760,6 +842,10 @@ int fmd_batch_debug_restart_skip(fmd_batch* b, int region);
  * resets of the calls that follow leave the channels' ring origins at the batch's phase (0), and a reset channel's
  * RDS low-pass and matched filter are no longer exact.  0 (the default) restores the origins. */
 int fmd_batch_debug_reset_keep_ring_phase(fmd_batch* b, int on);
+/* Test aid (mutation test of the feed's tests): on = 1 leaves out the roll behind every feed call, so the history rows
+ * in front of a call's frames stay what they were -- the first feed sample that reaches back over a call boundary is
+ * then wrong.  An entry point of its own: the fmd_batch_debug_set key table is held to 14 keys. */
+int fmd_batch_debug_feed_skip_roll(fmd_batch* b, int on);
 
 const char* fmd_last_error(void);
 const char* fmd_version(void);

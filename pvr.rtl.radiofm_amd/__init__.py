@@ -29,6 +29,9 @@ PCM_BYTES = {FMD_PCM_F32: 4, FMD_PCM_S16: 2}  # per audio sample
 # multiplex output formats (include/fmd.h FMD_MPX_*): the `mpx_format` argument of the _mpx entry points
 FMD_MPX_F32, FMD_MPX_S16 = 0, 1
 MPX_BYTES = {FMD_MPX_F32: 4, FMD_MPX_S16: 2}  # per multiplex sample
+# mono feed formats (include/fmd.h FMD_FEED_*): the `feed_format` argument of the _feed entry points
+FMD_FEED_F32, FMD_FEED_S16 = 0, 1
+FEED_BYTES = {FMD_FEED_F32: 4, FMD_FEED_S16: 2}  # per feed sample
 
 TAPS = {"demod": 0, "baseband": 1, "pilot38": 2, "mono_rs": 3, "stereo_rs": 4, "rds_lpf": 5,
         "rds_pll": 6, "rds_mf": 7, "rds_sync": 8}
@@ -173,6 +176,10 @@ EXPORTS = [
     "fmd_batch_max_mpx_samples", "fmd_batch_mpx_rate", "fmd_batch_debug_mpx_ms",
     "fmd_batch_state_size", "fmd_batch_save_state", "fmd_batch_load_state", "fmd_batch_export_channels",
     "fmd_batch_import_channels", "fmd_save_state", "fmd_load_state", "fmd_batch_debug_state_skip",
+    "fmd_batch_set_feed", "fmd_batch_get_feed", "fmd_batch_feed_rate", "fmd_batch_max_feed_samples",
+    "fmd_batch_get_feed_taps", "fmd_batch_process_device_feed", "fmd_batch_process_host_feed",
+    "fmd_process_stream_feed", "fmd_batch_select_feed", "fmd_batch_get_feed_selection",
+    "fmd_batch_debug_feed_skip_roll",
     "fmd_batch_select_audio", "fmd_batch_select_mpx", "fmd_batch_get_audio_selection", "fmd_batch_get_mpx_selection",
     "fmd_batch_set_rds_blocks", "fmd_batch_get_rds_blocks", "fmd_batch_collect_rds_blocks",
     "fmd_batch_read_rds_quality",
@@ -322,6 +329,23 @@ def lib():
         L.fmd_batch_debug_state_skip.argtypes = [vp, i]
         L.fmd_batch_select_audio.argtypes = [vp, vp, u]
         L.fmd_batch_select_mpx.argtypes = [vp, vp, u]
+        L.fmd_batch_set_feed.argtypes = [vp, i]
+        L.fmd_batch_get_feed.argtypes = [vp]
+        L.fmd_batch_feed_rate.restype = C.c_double
+        L.fmd_batch_feed_rate.argtypes = [vp]
+        L.fmd_batch_max_feed_samples.restype = u
+        L.fmd_batch_max_feed_samples.argtypes = [vp, u]
+        L.fmd_batch_get_feed_taps.argtypes = [vp, vp, u]
+        L.fmd_batch_process_device_feed.argtypes = [vp, vp, i, C.c_size_t, u, vp, i, C.c_size_t, C.POINTER(u),
+                                                    vp, i, C.c_size_t, C.POINTER(u),
+                                                    vp, i, C.c_size_t, C.POINTER(u), vp]
+        L.fmd_batch_process_host_feed.argtypes = [vp, vp, i, C.c_size_t, u, vp, i, C.c_size_t, C.POINTER(u),
+                                                  vp, i, C.c_size_t, C.POINTER(u),
+                                                  vp, i, C.c_size_t, C.POINTER(u)]
+        L.fmd_process_stream_feed.argtypes = [vp, vp, i, u, vp, i, vp, i, C.POINTER(u)]
+        L.fmd_batch_select_feed.argtypes = [vp, vp, u]
+        L.fmd_batch_get_feed_selection.argtypes = [vp, vp, u]
+        L.fmd_batch_debug_feed_skip_roll.argtypes = [vp, i]
         L.fmd_batch_get_audio_selection.argtypes = [vp, vp, u]
         L.fmd_batch_get_mpx_selection.argtypes = [vp, vp, u]
         L.fmd_batch_set_rds_blocks.argtypes = [vp, i, u]
@@ -376,6 +400,23 @@ def pcm_format_of(pcm):
         if fmt is not None:
             return fmt
     raise FmdError(FMD_ERR_ARG_TEXT % ("no audio format for %r (float32, int16, FMD_PCM_F32, FMD_PCM_S16)" % (pcm,)))
+
+
+def feed_format_of(feed):
+    """FMD_FEED_* of a `feed=` argument: np.float32, np.int16, or the constant itself.  Anything else raises: no
+    silent conversion."""
+    if isinstance(feed, (int, np.integer)) and not isinstance(feed, bool):
+        if int(feed) in FEED_BYTES:
+            return int(feed)
+    elif feed is not None:
+        try:
+            fmt = {np.dtype(np.float32): FMD_FEED_F32, np.dtype(np.int16): FMD_FEED_S16}.get(np.dtype(feed))
+        except TypeError:
+            fmt = None
+        if fmt is not None:
+            return fmt
+    raise FmdError(FMD_ERR_ARG_TEXT % ("no feed format for %r (float32, int16, FMD_FEED_F32, FMD_FEED_S16)"
+                                       % (feed,)))
 
 
 def mpx_format_of(mpx):
@@ -585,6 +626,49 @@ class Batch:
         keep = ch if ch.size else np.zeros(1, dtype=np.uint32)
         _check(lib().fmd_batch_select_mpx(self._h, keep.ctypes.data, ch.size))
 
+    def select_feed(self, channels):
+        """The same for the feed rows (fmd_batch_select_feed); an empty list: no rows are written, the feed's history
+        and frame count go on."""
+        if channels is None:
+            _check(lib().fmd_batch_select_feed(self._h, None, 0))
+            return
+        ch = self._selection_list(channels, "select_feed")
+        keep = ch if ch.size else np.zeros(1, dtype=np.uint32)
+        _check(lib().fmd_batch_select_feed(self._h, keep.ctypes.data, ch.size))
+
+    def feed_selection(self):
+        """uint32[n]: the channels of the feed rows the next call writes (fmd_batch_get_feed_selection)."""
+        out = np.zeros(self.n_channels, dtype=np.uint32)
+        n = _check(lib().fmd_batch_get_feed_selection(self._h, out.ctypes.data, out.size))
+        return out[:n].copy()
+
+    def set_feed(self, divisor):
+        """Turn the mono feed at sample_rate_pcm / divisor on (2 or 3) or off (0): fmd_batch_set_feed.  A setup call:
+        it waits for the calls in flight, zeroes the feed's history and starts its frame count at 0."""
+        _check(lib().fmd_batch_set_feed(self._h, int(divisor)))
+
+    def feed(self):
+        """The feed's divisor, 0 while it is off (fmd_batch_get_feed)."""
+        return _check(lib().fmd_batch_get_feed(self._h))
+
+    def feed_rate(self):
+        """Feed samples per second: sample_rate_pcm / divisor (fmd_batch_feed_rate)."""
+        return lib().fmd_batch_feed_rate(self._h)
+
+    def max_feed_samples(self, samples):
+        """Feed samples per channel a call of `samples` delivers at most (fmd_batch_max_feed_samples)."""
+        return lib().fmd_batch_max_feed_samples(self._h, samples)
+
+    def feed_taps(self):
+        """float32[T]: the feed's low-pass taps in use (fmd_batch_get_feed_taps)."""
+        out = np.zeros(80, dtype=np.float32)
+        n = _check(lib().fmd_batch_get_feed_taps(self._h, out.ctypes.data, out.size))
+        return out[:n].copy()
+
+    def debug_feed_skip_roll(self, on):
+        """Test aid: leave out the roll of the feed's history (fmd_batch_debug_feed_skip_roll)."""
+        _check(lib().fmd_batch_debug_feed_skip_roll(self._h, int(on)))
+
     def audio_selection(self):
         """uint32[n]: the channels of the audio rows the next call writes (fmd_batch_get_audio_selection)."""
         out = np.zeros(self.n_channels, dtype=np.uint32)
@@ -597,8 +681,9 @@ class Batch:
         n = _check(lib().fmd_batch_get_mpx_selection(self._h, out.ctypes.data, out.size))
         return out[:n].copy()
 
-    def _rows(self, mpx=False):
-        fn = lib().fmd_batch_get_mpx_selection if mpx else lib().fmd_batch_get_audio_selection
+    def _rows(self, mpx=False, feed=False):
+        fn = (lib().fmd_batch_get_feed_selection if feed else
+              lib().fmd_batch_get_mpx_selection if mpx else lib().fmd_batch_get_audio_selection)
         return _check(fn(self._h, None, 0))
 
     def min_samples(self):
@@ -654,14 +739,16 @@ class Batch:
                                                audio.ctypes.data, a_stride, C.byref(nf)))
         return audio[:, :nf.value]
 
-    def process_host_fmt(self, iq, shared=False, pcm=None, mpx=None):
+    def process_host_fmt(self, iq, shared=False, pcm=None, mpx=None, feed=None):
         """iq: [C, N] complex64, or [C, 2N] float32 / uint8 / int8 / int16 holding I, Q, I, Q, ... (rows as for
         process_host; one row when shared); the input format is the array's dtype (fmd_batch_process_host_fmt).
         Signed integers are v * 2^-7 / v * 2^-15: the same bits as process_host on the converted block.
         With a selection (select_audio / select_mpx) the arrays hold its rows, in its order.
         pcm=np.int16: the audio as int16 (FMD_PCM_S16, fmd_batch_process_host_pcm).
         mpx=np.float32 / np.int16: returns (audio, multiplex), the multiplex as [C, M] rows of that format
-        (FMD_MPX_*, fmd_batch_process_host_mpx: a deviation of f Hz reads f / 30 000, times 8192 as int16)."""
+        (FMD_MPX_*, fmd_batch_process_host_mpx: a deviation of f Hz reads f / 30 000, times 8192 as int16).
+        feed=np.int16 / np.float32: also returns the mono feed as [C, n] rows of that format, last of the tuple
+        (FMD_FEED_*, fmd_batch_process_host_feed; set_feed turns the feed on)."""
         iq, fmt, per = iq_format_of(iq)
         pcm_fmt = pcm_format_of(pcm)
         mpx_fmt = None if mpx is None else mpx_format_of(mpx)
@@ -675,6 +762,25 @@ class Batch:
         a_stride = self.max_audio_floats(n)
         audio = np.zeros((self._rows(), a_stride), dtype=np.int16 if pcm_fmt == FMD_PCM_S16 else np.float32)
         nf = C.c_uint()
+        if feed is not None:
+            feed_fmt = feed_format_of(feed)
+            m_stride = self.max_mpx_samples(n) if mpx_fmt is not None else 0
+            rows = (np.zeros((self._rows(mpx=True), m_stride), dtype=np.int16 if mpx_fmt == FMD_MPX_S16 else np.float32)
+                    if mpx_fmt is not None else None)
+            f_stride = max(self.max_feed_samples(n), 1)
+            frows = np.zeros((max(self._rows(feed=True), 1), f_stride),
+                             dtype=np.int16 if feed_fmt == FMD_FEED_S16 else np.float32)
+            nm, nfeed = C.c_uint(), C.c_uint()
+            _check(lib().fmd_batch_process_host_feed(self._h, iq.ctypes.data, fmt, stride, n, audio.ctypes.data,
+                                                     pcm_fmt, a_stride, C.byref(nf),
+                                                     None if rows is None else rows.ctypes.data,
+                                                     FMD_MPX_F32 if mpx_fmt is None else mpx_fmt, m_stride,
+                                                     C.byref(nm), frows.ctypes.data, feed_fmt, f_stride,
+                                                     C.byref(nfeed)))
+            frows = frows[:self._rows(feed=True), :nfeed.value]
+            if rows is None:
+                return audio[:, :nf.value], frows
+            return audio[:, :nf.value], rows[:, :nm.value], frows
         if mpx_fmt is not None:
             m_stride = self.max_mpx_samples(n)
             rows = np.zeros((self._rows(mpx=True), m_stride), dtype=np.int16 if mpx_fmt == FMD_MPX_S16 else np.float32)
@@ -692,13 +798,28 @@ class Batch:
         return audio[:, :nf.value]
 
     def process_device(self, d_iq_ptr, iq_stride, samples, d_audio_ptr, audio_stride, stream=None,
-                       u8=False, fmt=None, pcm=None, d_mpx_ptr=None, mpx_stride=0, mpx=None):
+                       u8=False, fmt=None, pcm=None, d_mpx_ptr=None, mpx_stride=0, mpx=None, d_feed_ptr=None,
+                       feed_stride=0, feed=None):
         """iq_stride in IQ samples; u8=True: d_iq_ptr holds RTL-SDR byte pairs; fmt (FMD_IQ_*): the input format,
         through fmd_batch_process_device_fmt; pcm (np.int16 / FMD_PCM_*): the output format, audio_stride and the
         returned count in its elements, through fmd_batch_process_device_pcm.
         d_mpx_ptr / mpx_stride / mpx (np.float32, np.int16 / FMD_MPX_*): the call's multiplex rows, through
-        fmd_batch_process_device_mpx; returns (audio samples, multiplex samples) per channel."""
+        fmd_batch_process_device_mpx; returns (audio samples, multiplex samples) per channel.
+        d_feed_ptr / feed_stride / feed (np.int16, np.float32 / FMD_FEED_*): the call's feed rows, through
+        fmd_batch_process_device_feed; the feed samples per channel are the last of the returned tuple."""
         nf = C.c_uint()
+        if d_feed_ptr is not None or feed is not None:
+            in_fmt = int(fmt) if fmt is not None else FMD_IQ_U8 if u8 else FMD_IQ_F32
+            nm, nfeed = C.c_uint(), C.c_uint()
+            _check(lib().fmd_batch_process_device_feed(self._h, d_iq_ptr, in_fmt, iq_stride, samples, d_audio_ptr,
+                                                       pcm_format_of(pcm), audio_stride, C.byref(nf), d_mpx_ptr,
+                                                       mpx_format_of(FMD_MPX_F32 if mpx is None else mpx), mpx_stride,
+                                                       C.byref(nm), d_feed_ptr,
+                                                       feed_format_of(FMD_FEED_S16 if feed is None else feed),
+                                                       feed_stride, C.byref(nfeed), stream))
+            if d_mpx_ptr is not None or mpx is not None:
+                return nf.value, nm.value, nfeed.value
+            return nf.value, nfeed.value
         if d_mpx_ptr is not None or mpx is not None:
             in_fmt = int(fmt) if fmt is not None else FMD_IQ_U8 if u8 else FMD_IQ_F32
             nm = C.c_uint()
@@ -973,6 +1094,25 @@ class FmDecoder:
         n = _check(lib().fmd_process_stream_mpx(self._h, iq.ctypes.data, FMD_IQ_F32, iq.size, audio.ctypes.data,
                                                 FMD_PCM_F32, rows.ctypes.data, mpx_fmt, C.byref(nm)))
         return audio[:n], rows[:nm.value]
+
+    def SetFeed(self, divisor):
+        """Turn the decoder's mono feed at sample_rate_pcm / divisor on (2 or 3) or off (0): fmd_batch_set_feed on
+        the batch behind the decoder."""
+        _check(lib().fmd_batch_set_feed(lib().fmd_decoder_batch(self._h), int(divisor)))
+
+    def ProcessStreamWithFeed(self, samples_in, feed=np.int16):
+        """(ProcessStream's audio, the mono feed of the block as int16 or float32): FMD_FEED_*,
+        fmd_process_stream_feed; SetFeed first."""
+        iq = np.ascontiguousarray(samples_in)
+        if iq.dtype != np.complex64:
+            iq = iq.astype(np.float32).view(np.complex64)
+        feed_fmt = feed_format_of(feed)
+        audio = np.empty(2 * iq.size, dtype=np.float32)
+        rows = np.empty(iq.size, dtype=np.int16 if feed_fmt == FMD_FEED_S16 else np.float32)
+        nfeed = C.c_uint()
+        n = _check(lib().fmd_process_stream_feed(self._h, iq.ctypes.data, FMD_IQ_F32, iq.size, audio.ctypes.data,
+                                                 FMD_PCM_F32, rows.ctypes.data, feed_fmt, C.byref(nfeed)))
+        return audio[:n], rows[:nfeed.value]
 
     def ProcessStreamU8(self, buf):
         """ReadAsyncCB + ProcessStream (RTL_SDR_Source.cpp:196-213): buf = I,Q byte pairs."""

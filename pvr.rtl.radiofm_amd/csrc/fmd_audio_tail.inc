@@ -6,6 +6,9 @@
  * call's selection: the output row of every channel, -1 for a channel that delivers none.  Such a lane runs the
  * recurrence, the meter and the status record like every other lane and leaves out what belongs to the output:
  * take(), store(), flush() and done() (the conversion and the clip count with them).
+ * The feed forms (k_audio_tail*_feed) also define FMD_TAIL_FEED: the first of the call's rows in the feed's time-major
+ * scratch ([A][CP] floats from there).  Every lane that has a channel, selected or not, stores the mono mix
+ * (o.x + o.y) * 0.5f of frame i into row i: one 4-byte store a lane, 256 contiguous bytes a wave.
  */
   __builtin_amdgcn_s_setprio(3);
   const unsigned lane = threadIdx.x;
@@ -78,6 +81,10 @@
     for (unsigned u = 0; u < AT_STEPS; u++)
     {
       const float2 f = frame(vin[u]);
+#ifdef FMD_TAIL_FEED
+      if (active)
+        FMD_TAIL_FEED[(size_t)(i0 + u) * CP + c] = (f.x + f.y) * 0.5f;
+#endif
       if (all_take || deliver)
         OUT::take(os, u, f);
       if (deliver)
@@ -92,6 +99,10 @@
       if (u < cnt)
       {
         const float2 f = frame(vnext[u]);
+#ifdef FMD_TAIL_FEED
+        if (active)
+          FMD_TAIL_FEED[(size_t)(i0 + u) * CP + c] = (f.x + f.y) * 0.5f;
+#endif
         if (all_take || deliver)
           OUT::take(os, u, f);
         if (deliver)

@@ -325,6 +325,25 @@ struct fmd_batch
     int cur = -1;
   };
   Selection sel_audio, sel_mpx;
+  /* The mono feed at sample_rate_pcm / feed_div (fmd_batch_set_feed).  Every batch knows the
+   * divisor; the caller-facing one keeps the taps for fmd_batch_get_feed_taps.  A batch with buffers of its own holds
+   * the taps on the device, the time-major scratch of mono frames -- [feed_T - 1 + Amax][CP] floats: the history rows
+   * in front of a call's rows, rolled behind every call that asked for the feed -- and feed_g, the frames of those
+   * calls so far: a call's first output and its sample count follow from it on the host, at submission.  One scratch,
+   * not two by call parity: a batch's audio tails run in submission order on one stream (the channel state and the
+   * clip counter rely on the same); should the stream ever differ from the last feed call's, the tail first waits for
+   * feed_done, recorded behind that call's roll.  The feed belongs to the output: resets, retunes, capture switches,
+   * imports and loads leave all of this alone. */
+  unsigned feed_div = 0, feed_T = 0;
+  uint64_t feed_g = 0;
+  std::vector<float> feed_taps_h;
+  DevBuf<float> feed_taps, feed_x;
+  Event feed_done;
+  hipStream_t feed_stream = nullptr;
+  bool feed_used = false;
+  int dbg_feed_skip_roll = 0;     // fmd_batch_debug_feed_skip_roll (mutation test): the history rows stay stale
+  Selection sel_feed;             // which channels deliver feed rows (fmd_batch_select_feed): the multiplex's form
+  DevBuf<float> h_feed;           // staging of the host-buffer call's feed rows (sized on first use)
   bool decoder_owned = false;     // the one-channel batch behind an fmd_decoder: it takes no selection
 
   std::vector<std::unique_ptr<fmd::GroupDecoder>> gdec;
@@ -367,6 +386,12 @@ struct fmd_batch
     size_t audio_stride = 0;
     hipEvent_t tl0 = nullptr, tl1 = nullptr; // profiling level 1: the audio tail's own start / stop
     Selection* asel = nullptr;         // the call's audio selection, or null: one row per channel
+    // the feed of a call that asked for it (feed: the tail's feed form, the roll; feed_deliver: k_feed_out as well)
+    bool feed = false, feed_deliver = false;
+    void* d_feed = nullptr;            // rows of feed_fmt (FMD_FEED_*), stride in its elements
+    int feed_fmt = 0;
+    size_t feed_stride = 0;
+    unsigned feed_p0 = 0, feed_n = 0;  // the call's first frame with an output, outputs of the call
   };
   /* More channels than the whole-CU pipeline is built for (kSubBatchChannels = 64 CUs' worth of serial stage): the
    * batch the caller holds is a SHELL over ceil(C / 8192) sub-batches of equal size, each a complete batch of its own
@@ -1851,17 +1876,17 @@ static int wait_impl(fmd_batch* b, int lag, void* stream_, bool take_lost);
  * same streams (fmd_batch::subs). */
 static int process_shell(fmd_batch* b, const void* d_iq, IqFormat fmt, size_t iq_channel_stride, unsigned samples,
                          void* d_audio, PcmFormat pcm, size_t audio_channel_stride, unsigned* out_floats,
-                         void* stream, const MpxJob& mpx = MpxJob());
+                         void* stream, const MpxJob& mpx = MpxJob(), const FeedJob& feed = FeedJob());
 
 /* Pending single-channel edits (retunes, resets) in front of the call; with retuning enabled, the silent twin's call
  * (zeros of the same size, on the same streams) behind it.  A batch with neither takes the plain path alone. */
 static int process_any(fmd_batch* b, const void* d_iq, IqFormat fmt, size_t iq_channel_stride, unsigned samples,
                        void* d_audio, PcmFormat pcm, size_t audio_channel_stride, unsigned* out_floats, void* stream,
-                       const MpxJob& mpx = MpxJob())
+                       const MpxJob& mpx = MpxJob(), const FeedJob& feed = FeedJob())
 {
   if (!b || (!b->twin && !b->edits_pending))
     return process_shell(b, d_iq, fmt, iq_channel_stride, samples, d_audio, pcm, audio_channel_stride, out_floats,
-                         stream, mpx);
+                         stream, mpx, feed);
   if (!d_iq || (!d_audio && audio_rows_due(b)))
     return fail(FMD_ERR_ARG, "fmd_batch_process_device: null argument");
   if (samples > FMD_MAX_BLOCK || samples < b->min_samples)
@@ -1879,10 +1904,11 @@ static int process_any(fmd_batch* b, const void* d_iq, IqFormat fmt, size_t iq_c
     }
   b->edits_pending = false;
   const int rc = process_shell(b, d_iq, fmt, iq_channel_stride, samples, d_audio, pcm, audio_channel_stride,
-                               out_floats, stream, mpx);
+                               out_floats, stream, mpx, feed);
   if (rc != FMD_OK || !tw)
     return rc;
-  // (the twin's audio is discarded: it stays float whatever the call's format; its multiplex is not written at all)
+  // (the twin's audio is discarded: it stays float whatever the call's format; its multiplex is not written at all,
+  // and it has no feed)
   const int trc = process_device_impl(tw, b->twin_iq.p, IQ_F32, 0, samples, b->twin_audio.p, PCM_F32,
                                       b->twin_audio.n, nullptr, stream);
   if (trc != FMD_OK)
@@ -1892,11 +1918,11 @@ static int process_any(fmd_batch* b, const void* d_iq, IqFormat fmt, size_t iq_c
 
 static int process_shell(fmd_batch* b, const void* d_iq, IqFormat fmt, size_t iq_channel_stride, unsigned samples,
                          void* d_audio, PcmFormat pcm, size_t audio_channel_stride, unsigned* out_floats, void* stream,
-                         const MpxJob& mpx)
+                         const MpxJob& mpx, const FeedJob& feed)
 {
   if (!b || b->subs.empty())
     return process_device_impl(b, d_iq, fmt, iq_channel_stride, samples, d_audio, pcm, audio_channel_stride,
-                               out_floats, stream, mpx);
+                               out_floats, stream, mpx, feed);
   if (!d_iq || (!d_audio && audio_rows_due(b)))
     return fail(FMD_ERR_ARG, "fmd_batch_process_device: null argument");
   if (int rc = check_device_errors(b))
@@ -1918,8 +1944,11 @@ static int process_shell(fmd_batch* b, const void* d_iq, IqFormat fmt, size_t iq
     MpxJob sub_mpx = mpx; // (the sub-batch's first multiplex row, like its first audio row)
     if (mpx.d && !b->sel_mpx.on)
       sub_mpx.d = static_cast<char*>(mpx.d) + size_t(ch0) * mpx.stride * mpx_esz(mpx.fmt);
+    FeedJob sub_feed = feed; // (... and its first feed row; every sub-batch counts the feed's frames for itself)
+    if (feed.d && !b->sel_feed.on)
+      sub_feed.d = static_cast<char*>(feed.d) + size_t(ch0) * feed.stride * feed_esz(feed.fmt);
     const int rc = process_device_impl(sb, iq, fmt, iq_channel_stride, samples, audio, pcm, audio_channel_stride, &nf,
-                                       stream, sub_mpx);
+                                       stream, sub_mpx, sub_feed);
     if (rc != FMD_OK)
     { // the first sub-batch refuses what every one of them would refuse (same geometry, same positions): nothing
       // has been submitted.  Later: part of the call is on the device -- the batch is unusable until reset.
@@ -2003,6 +2032,72 @@ int fmd_batch_process_device_mpx(fmd_batch* b, const void* d_iq, int iq_format, 
   mpx.out = out_mpx_samples;
   return process_any(b, d_iq, IqFormat(iq_format), iq_channel_stride, samples, d_audio, PcmFormat(pcm_format),
                      audio_channel_stride, out_samples, stream, mpx);
+}
+
+int fmd_batch_process_device_feed(fmd_batch* b, const void* d_iq, int iq_format, size_t iq_channel_stride,
+                                  unsigned samples, void* d_audio, int pcm_format, size_t audio_channel_stride,
+                                  unsigned* out_samples, void* d_mpx, int mpx_format, size_t mpx_channel_stride,
+                                  unsigned* out_mpx_samples, void* d_feed, int feed_format, size_t feed_channel_stride,
+                                  unsigned* out_feed_samples, void* stream)
+{
+  if (!feed_format_ok(feed_format))
+    return fail(FMD_ERR_ARG, "fmd_batch_process_device_feed: feed_format must be FMD_FEED_F32 or FMD_FEED_S16 (0..1)");
+  if (out_feed_samples)
+    *out_feed_samples = 0;
+  if (!d_feed) // no feed: the _mpx call, nothing else
+    return fmd_batch_process_device_mpx(b, d_iq, iq_format, iq_channel_stride, samples, d_audio, pcm_format,
+                                        audio_channel_stride, out_samples, d_mpx, mpx_format, mpx_channel_stride,
+                                        out_mpx_samples, stream);
+  if (!mpx_format_ok(mpx_format))
+    return fail(FMD_ERR_ARG, "fmd_batch_process_device_feed: mpx_format must be FMD_MPX_F32 or FMD_MPX_S16 (0..1)");
+  if (!iq_format_ok(iq_format))
+    return fail(FMD_ERR_ARG,
+                "fmd_batch_process_device_feed: iq_format must be one of FMD_IQ_F32, _U8, _S8, _S16 (0..3)");
+  if (!pcm_format_ok(pcm_format))
+    return fail(FMD_ERR_ARG, "fmd_batch_process_device_feed: pcm_format must be FMD_PCM_F32 or FMD_PCM_S16 (0..1)");
+  // a lane stores 16 bytes of a row at a time: every row has to start on a 16-byte boundary
+  if ((reinterpret_cast<uintptr_t>(d_feed) % 16) || (feed_channel_stride % (feed_format == FMD_FEED_S16 ? 8 : 4)))
+    return fail(FMD_ERR_ARG, "fmd_batch_process_device_feed: the feed pointer must be 16-byte aligned and "
+                             "feed_channel_stride a multiple of 4 (FMD_FEED_F32) / 8 (FMD_FEED_S16) elements");
+  if (!b)
+    return fail(FMD_ERR_ARG, "fmd_batch_process_device_feed: null argument");
+  if (!b->feed_div)
+    return fail(FMD_ERR_STATE, "fmd_batch_process_device_feed: a feed pointer while the feed is off "
+                               "(fmd_batch_set_feed turns it on)");
+  if (pcm_format == FMD_PCM_S16 && d_iq && d_audio &&
+      ((reinterpret_cast<uintptr_t>(d_audio) % 16) || (audio_channel_stride % 8)))
+    return fail(FMD_ERR_ARG, "fmd_batch_process_device_feed: for FMD_PCM_S16 the audio pointer must be 16-byte aligned "
+                             "and audio_channel_stride a multiple of 8 elements");
+  MpxJob mpx;
+  if (d_mpx && !(b->sel_mpx.on && b->sel_mpx.n_total == 0))
+  {
+    if ((reinterpret_cast<uintptr_t>(d_mpx) % 16) || (mpx_channel_stride % (mpx_format == FMD_MPX_S16 ? 8 : 4)))
+      return fail(FMD_ERR_ARG, "fmd_batch_process_device_feed: the multiplex pointer must be 16-byte aligned and "
+                               "mpx_channel_stride a multiple of 4 (FMD_MPX_F32) / 8 (FMD_MPX_S16) elements");
+    if (mpx_channel_stride < next_baseband_length(b, samples))
+      return fail(FMD_ERR_ARG, "fmd_batch_process_device_feed: mpx_channel_stride smaller than the call's baseband "
+                               "length (fmd_batch_max_mpx_samples is the bound)");
+    mpx.d = d_mpx;
+    mpx.fmt = MpxFormat(mpx_format);
+    mpx.stride = mpx_channel_stride;
+  }
+  mpx.out = out_mpx_samples;
+  if (out_mpx_samples)
+    *out_mpx_samples = 0;
+  // the rows hold the call's samples -- looked at here, in front of the pending channel edits: a refused call leaves
+  // the batch as it was
+  const fmd_batch* x = b->subs.empty() ? b : b->subs[0].get();
+  if (feed_channel_stride < feed_samples_of(x->feed_g, next_audio_frames(b, samples), b->feed_div))
+    return fail(FMD_ERR_ARG, "fmd_batch_process_device_feed: feed_channel_stride smaller than the call's feed samples "
+                             "(fmd_batch_max_feed_samples is the bound)");
+  FeedJob feed;
+  feed.d = d_feed;
+  feed.fmt = FeedFormat(feed_format);
+  feed.stride = feed_channel_stride;
+  feed.out = out_feed_samples;
+  feed.deliver = !(b->sel_feed.on && b->sel_feed.n_total == 0);
+  return process_any(b, d_iq, IqFormat(iq_format), iq_channel_stride, samples, d_audio, PcmFormat(pcm_format),
+                     audio_channel_stride, out_samples, stream, mpx, feed);
 }
 
 int fmd_batch_process_device_fmt(fmd_batch* b, const void* d_iq, int format, size_t iq_channel_stride,
@@ -2440,7 +2535,7 @@ int fmd_batch_switch_captures(fmd_batch* b, const unsigned* channels, const unsi
 /* fmd_batch_select_audio / _mpx: checked as a whole, then every batch with buffers takes its part -- (local channel,
  * global row), sorted by channel: the audio table is indexed by channel anyway, and the multiplex writer's gathers
  * coalesce over neighbouring channels -- and builds a new table version in front of its next call (sel_table). */
-static int select_rows(fmd_batch* b, bool mpx, const unsigned* channels, unsigned n, const char* who)
+static int select_rows(fmd_batch* b, int which, const unsigned* channels, unsigned n, const char* who)
 {
   if (!b)
     return fail(FMD_ERR_ARG, std::string(who) + ": null batch");
@@ -2462,13 +2557,17 @@ static int select_rows(fmd_batch* b, bool mpx, const unsigned* channels, unsigne
   }
   else
     n = 0;
-  fmd_batch::Selection& top = mpx ? b->sel_mpx : b->sel_audio;
+  // which: 0 audio, 1 multiplex, 2 feed
+  auto pick = [which](fmd_batch* y) -> fmd_batch::Selection& {
+    return which == 2 ? y->sel_feed : which == 1 ? y->sel_mpx : y->sel_audio;
+  };
+  fmd_batch::Selection& top = pick(b);
   const std::vector<fmd_batch*> xs = buffer_batches(b);
   for (size_t k = 0; k < xs.size(); k++)
   {
     fmd_batch* x = xs[k];
     const unsigned ch0 = is_shell(b) ? b->sub_ch0[k] : 0u;
-    fmd_batch::Selection& sel = mpx ? x->sel_mpx : x->sel_audio;
+    fmd_batch::Selection& sel = pick(x);
     sel.ent.clear();
     for (unsigned i = 0; i < n; i++)
       if (channels[i] >= ch0 && channels[i] - ch0 < x->C)
@@ -2487,11 +2586,11 @@ static int select_rows(fmd_batch* b, bool mpx, const unsigned* channels, unsigne
   return FMD_OK;
 }
 
-static int get_selection(fmd_batch* b, bool mpx, unsigned* out, unsigned cap, const char* who)
+static int get_selection(fmd_batch* b, int which, unsigned* out, unsigned cap, const char* who)
 {
   if (!b || (cap && !out))
     return fail(FMD_ERR_ARG, std::string(who) + ": null argument");
-  const fmd_batch::Selection& sel = mpx ? b->sel_mpx : b->sel_audio;
+  const fmd_batch::Selection& sel = which == 2 ? b->sel_feed : which == 1 ? b->sel_mpx : b->sel_audio;
   const unsigned n = sel.on ? sel.n_total : b->C;
   for (unsigned i = 0; i < std::min(cap, n); i++)
     out[i] = sel.on ? sel.list[i] : i;
@@ -2500,22 +2599,116 @@ static int get_selection(fmd_batch* b, bool mpx, unsigned* out, unsigned cap, co
 
 int fmd_batch_select_audio(fmd_batch* b, const unsigned* channels, unsigned n)
 {
-  return select_rows(b, false, channels, n, "fmd_batch_select_audio");
+  return select_rows(b, 0, channels, n, "fmd_batch_select_audio");
 }
 
 int fmd_batch_select_mpx(fmd_batch* b, const unsigned* channels, unsigned n)
 {
-  return select_rows(b, true, channels, n, "fmd_batch_select_mpx");
+  return select_rows(b, 1, channels, n, "fmd_batch_select_mpx");
 }
 
 int fmd_batch_get_audio_selection(fmd_batch* b, unsigned* out, unsigned cap)
 {
-  return get_selection(b, false, out, cap, "fmd_batch_get_audio_selection");
+  return get_selection(b, 0, out, cap, "fmd_batch_get_audio_selection");
 }
 
 int fmd_batch_get_mpx_selection(fmd_batch* b, unsigned* out, unsigned cap)
 {
-  return get_selection(b, true, out, cap, "fmd_batch_get_mpx_selection");
+  return get_selection(b, 1, out, cap, "fmd_batch_get_mpx_selection");
+}
+
+int fmd_batch_select_feed(fmd_batch* b, const unsigned* channels, unsigned n)
+{
+  return select_rows(b, 2, channels, n, "fmd_batch_select_feed");
+}
+
+int fmd_batch_get_feed_selection(fmd_batch* b, unsigned* out, unsigned cap)
+{
+  return get_selection(b, 2, out, cap, "fmd_batch_get_feed_selection");
+}
+
+/* fmd_batch_set_feed: a setup call.  It waits for the calls in flight (the scratch they may still write is freed or
+ * replaced), then every batch with buffers takes the taps, a zeroed scratch and a frame count of 0. */
+int fmd_batch_set_feed(fmd_batch* b, int divisor)
+{
+  if (divisor != 0 && divisor != 2 && divisor != 3)
+    return fail(FMD_ERR_ARG, "fmd_batch_set_feed: the divisor must be 2 or 3, or 0 for no feed (any other is cut off "
+                             "by the low-pass design's cap of 75 taps)");
+  if (!b)
+    return fail(FMD_ERR_ARG, "fmd_batch_set_feed: null batch");
+  if (b->failed)
+    return fail(FMD_ERR_ARG, "fmd_batch_set_feed: the batch has failed (fmd_batch_reset clears it)");
+  std::vector<float> taps;
+  if (divisor)
+  {
+    const float fs = float(b->params.sample_rate_pcm), fo = fs / float(divisor);
+    taps = fmd::make_kaiser_lp(1.0f, 60.0f, 0.425f * fo, 0.575f * fo, fs);
+    if (taps.size() < 2 || taps.size() > fmd::FEED_TAPS_MAX)
+      return fail(FMD_ERR_ARG, "fmd_batch_set_feed: the low-pass design has no usable length at this rate");
+  }
+  HIPCHK(hipSetDevice(b->device));
+  HIPCHK(hipDeviceSynchronize());
+  const unsigned T = unsigned(taps.size());
+  for (fmd_batch* x : buffer_batches(b))
+  {
+    x->feed_div = 0; // (off until everything below is in place)
+    x->feed_T = 0;
+    x->feed_g = 0;
+    x->feed_used = false;
+    x->feed_x.release();
+    x->feed_taps.release();
+    if (!divisor)
+      continue;
+    if (x->feed_x.alloc(size_t(T - 1 + x->Amax) * x->CP) || x->feed_taps.alloc(T))
+      return fail(FMD_ERR_DEVICE, "fmd_batch_set_feed: device allocation failed");
+    HIPCHK(hipMemcpy(x->feed_taps.p, taps.data(), T * sizeof(float), hipMemcpyHostToDevice));
+    if (!x->feed_done.e)
+      HIPCHK(x->feed_done.create());
+    x->feed_div = unsigned(divisor);
+    x->feed_T = T;
+  }
+  HIPCHK(hipDeviceSynchronize());
+  b->feed_div = unsigned(divisor);
+  b->feed_T = T;
+  b->feed_g = 0;
+  b->feed_taps_h = taps;
+  return FMD_OK;
+}
+
+int fmd_batch_get_feed(const fmd_batch* b)
+{
+  return b ? int(b->feed_div) : fail(FMD_ERR_ARG, "fmd_batch_get_feed: null batch");
+}
+
+double fmd_batch_feed_rate(const fmd_batch* b)
+{
+  return (b && b->feed_div) ? b->params.sample_rate_pcm / double(b->feed_div) : 0.0;
+}
+
+unsigned fmd_batch_max_feed_samples(const fmd_batch* b, unsigned samples)
+{
+  if (!b || !b->feed_div)
+    return 0;
+  // a call of A frames holds at most ceil(A / D) multiples of D
+  return (fmd_batch_max_audio_floats(b, samples) / 2 + b->feed_div - 1) / b->feed_div;
+}
+
+int fmd_batch_get_feed_taps(const fmd_batch* b, float* out, unsigned cap)
+{
+  if (!b || (cap && !out))
+    return fail(FMD_ERR_ARG, "fmd_batch_get_feed_taps: null argument");
+  for (unsigned i = 0; i < std::min<size_t>(cap, b->feed_taps_h.size()); i++)
+    out[i] = b->feed_taps_h[i];
+  return int(b->feed_taps_h.size());
+}
+
+int fmd_batch_debug_feed_skip_roll(fmd_batch* b, int on)
+{
+  if (!b)
+    return fail(FMD_ERR_ARG, "null batch");
+  for (fmd_batch* x : buffer_batches(b))
+    x->dbg_feed_skip_roll = on != 0;
+  return FMD_OK;
 }
 
 int fmd_batch_retune_channels_to(fmd_batch* b, const unsigned* channels, const int* shifts, const unsigned* captures,
@@ -2733,10 +2926,15 @@ int fmd_batch_export_rds_device(fmd_batch* b, int32_t* d_records, unsigned cap, 
 static int process_host_impl(fmd_batch* b, const void* iq, IqFormat fmt, size_t iq_channel_stride,
                              unsigned samples, void* audio, PcmFormat pcm, size_t audio_channel_stride,
                              unsigned* out_floats, void* mpx = nullptr, MpxFormat mpx_fmt = MPX_F32,
-                             size_t mpx_channel_stride = 0, unsigned* out_mpx = nullptr)
+                             size_t mpx_channel_stride = 0, unsigned* out_mpx = nullptr, void* feed = nullptr,
+                             FeedFormat feed_fmt = FEED_F32, size_t feed_channel_stride = 0,
+                             unsigned* out_feed = nullptr)
 {
   if (!b || !iq || (!audio && audio_rows_due(b)))
     return fail(FMD_ERR_ARG, "fmd_batch_process_host: null argument");
+  if (feed && !b->feed_div)
+    return fail(FMD_ERR_STATE, "fmd_batch_process_host_feed: a feed pointer while the feed is off (fmd_batch_set_feed "
+                               "turns it on)");
   HIPCHK(hipSetDevice(b->device));
   const unsigned C = b->C;
   // rows of the two outputs: one per channel, or the selections' (fmd_batch_select_audio / _mpx) -- staged, copied
@@ -2765,6 +2963,30 @@ static int process_host_impl(fmd_batch* b, const void* iq, IqFormat fmt, size_t 
     mj.stride = m_stride;
     mj.out = &nm;
   }
+  // feed staging, the same way: rows of f_stride elements on 16-byte boundaries; a selection of no rows stages one
+  // row nobody writes (the call still counts the feed's frames)
+  FeedJob fj;
+  const unsigned f_rows = b->sel_feed.on ? b->sel_feed.n_total : C;
+  const size_t fsz = feed_esz(feed_fmt);
+  const size_t f_round = feed_fmt == FEED_S16 ? 7 : 3;
+  const size_t f_stride = (size_t(fmd_batch_max_feed_samples(b, samples)) + f_round + 1) & ~f_round;
+  unsigned nfeed = 0;
+  if (feed)
+  {
+    const fmd_batch* x = b->subs.empty() ? b : b->subs[0].get();
+    if (f_rows > 1 &&
+        feed_channel_stride < feed_samples_of(x->feed_g, next_audio_frames(b, samples), b->feed_div))
+      return fail(FMD_ERR_ARG, "fmd_batch_process_host_feed: feed_channel_stride smaller than the call's feed samples "
+                               "(fmd_batch_max_feed_samples is the bound)");
+    const size_t feed_floats = f_stride * std::max(f_rows, 1u) * fsz / sizeof(float);
+    if (feed_floats > b->h_feed.n && b->h_feed.alloc(feed_floats))
+      return fail(FMD_ERR_DEVICE, "staging allocation failed");
+    fj.d = b->h_feed.p;
+    fj.fmt = feed_fmt;
+    fj.stride = f_stride;
+    fj.out = &nfeed;
+    fj.deliver = f_rows != 0;
+  }
   const size_t esz = iq_esz(fmt); // bytes per IQ sample
   // device copy: one row per channel, rows padded to a whole pair of samples
   const size_t dev_row = (size_t(samples) + 1) / 2 * 2 * esz;
@@ -2791,7 +3013,7 @@ static int process_host_impl(fmd_batch* b, const void* iq, IqFormat fmt, size_t 
   b->host_ms[0] += ms_since(tp);
   tp = clk::now();
   unsigned nf = 0;
-  int rc = process_any(b, b->h_iq.p, fmt, dev_iq_stride, samples, b->h_audio.p, pcm, a_stride, &nf, nullptr, mj);
+  int rc = process_any(b, b->h_iq.p, fmt, dev_iq_stride, samples, b->h_audio.p, pcm, a_stride, &nf, nullptr, mj, fj);
   if (rc != FMD_OK)
     return rc;
   if (a_rows > 1 && nf > audio_channel_stride)
@@ -2811,6 +3033,11 @@ static int process_host_impl(fmd_batch* b, const void* iq, IqFormat fmt, size_t 
                        size_t(nm) * msz, m_rows, hipMemcpyDeviceToHost));
   if (out_mpx)
     *out_mpx = nm;
+  if (feed && nfeed && f_rows)
+    HIPCHK(hipMemcpy2D(feed, (f_rows > 1 ? feed_channel_stride : size_t(nfeed)) * fsz, b->h_feed.p, f_stride * fsz,
+                       size_t(nfeed) * fsz, f_rows, hipMemcpyDeviceToHost));
+  if (out_feed)
+    *out_feed = nfeed;
   b->host_ms[2] += ms_since(tp);
   tp = clk::now();
   rc = fmd_batch_collect_rds(b, nullptr, 0, 1, nullptr);
@@ -2849,6 +3076,27 @@ int fmd_batch_process_host_mpx(fmd_batch* b, const void* iq, int iq_format, size
   return process_host_impl(b, iq, IqFormat(iq_format), iq_channel_stride, samples, audio, PcmFormat(pcm_format),
                            audio_channel_stride, out_samples, mpx, MpxFormat(mpx_format), mpx_channel_stride,
                            out_mpx_samples);
+}
+
+int fmd_batch_process_host_feed(fmd_batch* b, const void* iq, int iq_format, size_t iq_channel_stride,
+                                unsigned samples, void* audio, int pcm_format, size_t audio_channel_stride,
+                                unsigned* out_samples, void* mpx, int mpx_format, size_t mpx_channel_stride,
+                                unsigned* out_mpx_samples, void* feed, int feed_format, size_t feed_channel_stride,
+                                unsigned* out_feed_samples)
+{
+  if (!feed_format_ok(feed_format))
+    return fail(FMD_ERR_ARG, "fmd_batch_process_host_feed: feed_format must be FMD_FEED_F32 or FMD_FEED_S16 (0..1)");
+  if (!mpx_format_ok(mpx_format))
+    return fail(FMD_ERR_ARG, "fmd_batch_process_host_feed: mpx_format must be FMD_MPX_F32 or FMD_MPX_S16 (0..1)");
+  if (!iq_format_ok(iq_format))
+    return fail(FMD_ERR_ARG, "fmd_batch_process_host_feed: iq_format must be one of FMD_IQ_F32, _U8, _S8, _S16 (0..3)");
+  if (!pcm_format_ok(pcm_format))
+    return fail(FMD_ERR_ARG, "fmd_batch_process_host_feed: pcm_format must be FMD_PCM_F32 or FMD_PCM_S16 (0..1)");
+  if (out_feed_samples)
+    *out_feed_samples = 0;
+  return process_host_impl(b, iq, IqFormat(iq_format), iq_channel_stride, samples, audio, PcmFormat(pcm_format),
+                           audio_channel_stride, out_samples, mpx, MpxFormat(mpx_format), mpx_channel_stride,
+                           out_mpx_samples, feed, FeedFormat(feed_format), feed_channel_stride, out_feed_samples);
 }
 
 int fmd_batch_process_host_fmt(fmd_batch* b, const void* iq, int format, size_t iq_channel_stride, unsigned samples,
@@ -3433,6 +3681,25 @@ int fmd_process_stream_mpx(fmd_decoder* d, const void* iq, int iq_format, unsign
   unsigned nf = 0;
   int rc = fmd_batch_process_host_mpx(d->b, iq, iq_format, 0, samples, audio, pcm_format, 0, &nf, mpx, mpx_format, 0,
                                       mpx_samples);
+  return rc < 0 ? rc : int(nf);
+}
+
+int fmd_process_stream_feed(fmd_decoder* d, const void* iq, int iq_format, unsigned samples, void* audio,
+                            int pcm_format, void* feed, int feed_format, unsigned* feed_samples)
+{
+  if (!feed_format_ok(feed_format))
+    return fail(FMD_ERR_ARG, "fmd_process_stream_feed: feed_format must be FMD_FEED_F32 or FMD_FEED_S16 (0..1)");
+  if (!iq_format_ok(iq_format))
+    return fail(FMD_ERR_ARG, "fmd_process_stream_feed: iq_format must be one of FMD_IQ_F32, _U8, _S8, _S16 (0..3)");
+  if (!pcm_format_ok(pcm_format))
+    return fail(FMD_ERR_ARG, "fmd_process_stream_feed: pcm_format must be FMD_PCM_F32 or FMD_PCM_S16 (0..1)");
+  if (feed_samples)
+    *feed_samples = 0;
+  if (!d)
+    return fail(FMD_ERR_ARG, "null decoder");
+  unsigned nf = 0;
+  int rc = fmd_batch_process_host_feed(d->b, iq, iq_format, 0, samples, audio, pcm_format, 0, &nf, nullptr,
+                                       FMD_MPX_F32, 0, nullptr, feed, feed_format, 0, feed_samples);
   return rc < 0 ? rc : int(nf);
 }
 

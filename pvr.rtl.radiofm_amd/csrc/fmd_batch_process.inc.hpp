@@ -233,6 +233,50 @@ void sel_read_done(fmd_batch* b, fmd_batch::Selection& sel, hipStream_t st)
   t.stream = st;
 }
 
+/* The feed of a call behind the feed form of its audio tail, on the same stream: the decimating filter over history
+ * and new rows into the caller's rows (k_feed_out, or the selected writer), then the roll that makes the last T - 1
+ * rows the next feed call's history (the overlapping form for calls shorter than that), and the event behind it. */
+void launch_feed(fmd_batch* b, const fmd_batch::LightJob& j, hipStream_t s)
+{
+  const unsigned C = b->C, CP = b->CP, T = b->feed_T, D = b->feed_div, n = j.feed_n;
+  const unsigned tiles = (n + fmd::FEED_T - 1) / fmd::FEED_T;
+  if (j.feed_deliver && n && b->sel_feed.on)
+  { // the selected writer (fmd_batch_select_feed): tiles of 64 entries of this batch's part of the list
+    const unsigned ns = unsigned(b->sel_feed.ent.size());
+    const int* tab = ns ? sel_table(b, b->sel_feed, true, s) : nullptr;
+    if (tab)
+    {
+      const dim3 g((ns + 63) / 64, tiles);
+      if (j.feed_fmt == FMD_FEED_S16)
+        hipLaunchKernelGGL(fmd::k_feed_out_sel<fmd::FeedS16>, g, dim3(256), 0, s, b->feed_x.p, b->feed_taps.p, T, D,
+                           j.feed_p0, n, ns, CP, reinterpret_cast<const int2*>(tab), static_cast<int16_t*>(j.d_feed),
+                           j.feed_stride);
+      else
+        hipLaunchKernelGGL(fmd::k_feed_out_sel<fmd::FeedF32>, g, dim3(256), 0, s, b->feed_x.p, b->feed_taps.p, T, D,
+                           j.feed_p0, n, ns, CP, reinterpret_cast<const int2*>(tab), static_cast<float*>(j.d_feed),
+                           j.feed_stride);
+      sel_read_done(b, b->sel_feed, s);
+    }
+  }
+  else if (j.feed_deliver && n)
+  {
+    const dim3 g(CP / 64, tiles);
+    if (j.feed_fmt == FMD_FEED_S16)
+      hipLaunchKernelGGL(fmd::k_feed_out<fmd::FeedS16>, g, dim3(256), 0, s, b->feed_x.p, b->feed_taps.p, T, D,
+                         j.feed_p0, n, C, CP, static_cast<int16_t*>(j.d_feed), j.feed_stride);
+    else
+      hipLaunchKernelGGL(fmd::k_feed_out<fmd::FeedF32>, g, dim3(256), 0, s, b->feed_x.p, b->feed_taps.p, T, D,
+                         j.feed_p0, n, C, CP, static_cast<float*>(j.d_feed), j.feed_stride);
+  }
+  if (!b->dbg_feed_skip_roll)
+    hipLaunchKernelGGL(fmd::k_roll<float>, dim3((CP + 255) / 256, std::max(1u, std::min(T - 1, 64u))), dim3(256), 0, s,
+                       b->feed_x.p, b->feed_x.p, T - 1, j.A, CP);
+  if (hipEventRecord(b->feed_done, s) != hipSuccess)
+    mark_failed(b, "hipEventRecord failed behind the feed of a call");
+  b->feed_stream = s;
+  b->feed_used = true;
+}
+
 /* Audio half on stream s, behind event `audio_after` of the call where it has one: (layout 2: the 29-tap low-pass,)
  * de-emphasis, notch, L/R matrix, audio meter; then -- behind the RDS half -- the status record; records EV_AUD. */
 void launch_light_audio(fmd_batch* b, const fmd_batch::LightJob& j, hipStream_t s)
@@ -254,8 +298,28 @@ void launch_light_audio(fmd_batch* b, const fmd_batch::LightJob& j, hipStream_t 
   // a selection (fmd_batch_select_audio): the selected forms and the call's row table; without, the kernels, the
   // arguments and the launches of a batch that never had one
   const int* rows = j.asel ? sel_table(b, *j.asel, false, s) : nullptr;
+  // a call that asked for the feed (fmd_batch_set_feed): the feed forms, which also store every frame's mono mix into
+  // the scratch rows behind the history.  The scratch is one buffer: this tail runs behind the last feed call's
+  // k_feed_out and roll in stream order -- in every layout and concurrency mode the audio halves of a batch's calls
+  // share one stream (the caller's, s_post, s_rds or s_lpf) until a setup call that drains the device moves them; a
+  // stream that differs from the last feed call's all the same waits for the event behind that call's roll.
+  float* const feed_rows = j.feed ? b->feed_x.p + size_t(b->feed_T - 1) * CP : nullptr;
+  if (j.feed && b->feed_used && b->feed_stream != s && hipStreamWaitEvent(s, b->feed_done, 0) != hipSuccess)
+    mark_failed(b, "hipStreamWaitEvent failed in front of the feed form of the audio tail");
   if (j.asel && !rows)
     ; // (the batch has failed: its state is void, the tail is left out)
+  else if (j.feed && j.asel && j.pcm == FMD_PCM_S16)
+    launch(fmd::k_audio_tail_s16_sel_feed, dim3(CP / 64), dim3(64, 1), 0, s, j.tl0, j.tl1, b->alp[j.q].p, j.A, C, CP,
+           k, b->st, j.d_audio, j.audio_stride, unsigned(j.sq), j.call_index, b->pcm_clip.p, rows, feed_rows);
+  else if (j.feed && j.asel)
+    launch(fmd::k_audio_tail_sel_feed, dim3(CP / 64), dim3(64, 1), 0, s, j.tl0, j.tl1, b->alp[j.q].p, j.A, C, CP, k,
+           b->st, j.d_audio, j.audio_stride, unsigned(j.sq), j.call_index, rows, feed_rows);
+  else if (j.feed && j.pcm == FMD_PCM_S16)
+    launch(fmd::k_audio_tail_s16_feed, dim3(CP / 64), dim3(64, 1), 0, s, j.tl0, j.tl1, b->alp[j.q].p, j.A, C, CP, k,
+           b->st, j.d_audio, j.audio_stride, unsigned(j.sq), j.call_index, b->pcm_clip.p, feed_rows);
+  else if (j.feed)
+    launch(fmd::k_audio_tail_feed, dim3(CP / 64), dim3(64, 1), 0, s, j.tl0, j.tl1, b->alp[j.q].p, j.A, C, CP, k,
+           b->st, j.d_audio, j.audio_stride, unsigned(j.sq), j.call_index, feed_rows);
   else if (j.asel && j.pcm == FMD_PCM_S16)
     launch(fmd::k_audio_tail_s16_sel, dim3(CP / 64), dim3(64, 1), 0, s, j.tl0, j.tl1, b->alp[j.q].p, j.A, C, CP, k,
            b->st, j.d_audio, j.audio_stride, unsigned(j.sq), j.call_index, b->pcm_clip.p, rows);
@@ -271,6 +335,8 @@ void launch_light_audio(fmd_batch* b, const fmd_batch::LightJob& j, hipStream_t 
            k, b->st, j.d_audio, j.audio_stride, unsigned(j.sq), j.call_index);
   if (rows)
     sel_read_done(b, *j.asel, s);
+  if (j.feed)
+    launch_feed(b, j, s);
   // the record's RDS state is the other half's (same stream: stream order)
   if (j.events && j.status_after_rds && hipStreamWaitEvent(s, b->cev[j.es][fmd_batch::EV_RDS], 0) != hipSuccess)
     mark_failed(b, "hipStreamWaitEvent failed in front of the status record of a call");
@@ -349,6 +415,46 @@ struct MpxJob
   unsigned* out = nullptr; // (host, optional) samples per row: the call's baseband length
 };
 
+enum FeedFormat
+{
+  FEED_F32 = 0, // the decimating filter's float sum as is
+  FEED_S16 = 1  // int16 in host byte order, fmd_f32_to_s16 of it
+};
+static_assert(FEED_F32 == FMD_FEED_F32 && FEED_S16 == FMD_FEED_S16, "the plan's formats are the C ABI's");
+
+/* bytes per feed sample */
+inline size_t feed_esz(FeedFormat fmt)
+{
+  return fmt == FEED_S16 ? 2 : 4;
+}
+
+/* the `feed_format` argument of the _feed entry points: 0..1, checked before anything else is touched */
+inline bool feed_format_ok(int format)
+{
+  return format >= FMD_FEED_F32 && format <= FMD_FEED_S16;
+}
+
+/* Where a call delivers its feed (the _feed entry points); d == null: nowhere -- the call launches what a call
+ * without the argument launches, and the feed's frame count does not advance. */
+struct FeedJob
+{
+  void* d = nullptr;       // rows of the format, channel c at d + c * stride elements; 16-byte aligned
+  FeedFormat fmt = FEED_F32;
+  size_t stride = 0;       // elements; a multiple of 4 (F32) / 8 (S16), >= the call's sample count
+  unsigned* out = nullptr; // (host, optional) samples per row
+  bool deliver = true;     // false: a feed selection of no rows -- the scratch and the count advance, nothing is written
+};
+
+/* The feed samples of a call of A frames behind g0 frames: the outputs n with g0 <= n D < g0 + A; *p0 = the call's
+ * first frame that has one. */
+inline unsigned feed_samples_of(uint64_t g0, unsigned A, unsigned D, unsigned* p0 = nullptr)
+{
+  const uint64_t first = (g0 + D - 1) / D;
+  if (p0)
+    *p0 = unsigned(first * D - g0);
+  return unsigned((g0 + A + D - 1) / D - first);
+}
+
 /* The baseband length M of the batch's next call of `samples` (DownConvert.cpp:112,123), 0 where the call would be
  * refused for its size: what an _mpx entry point holds the row stride against before anything is submitted. */
 inline unsigned next_baseband_length(const fmd_batch* b, unsigned samples)
@@ -356,6 +462,24 @@ inline unsigned next_baseband_length(const fmd_batch* b, unsigned samples)
   const fmd_batch* x = b->subs.empty() ? b : b->subs[0].get();
   const unsigned D = x->des.D;
   return x->if_pos < samples ? (samples - x->if_pos + D - 1) / D : 0;
+}
+
+/* The audio frames A of the batch's next call of `samples` (the resampler walk of process_device_impl,
+ * DownConvert.cpp:203-232), 0 where the call would be refused for its size: with it an entry point knows the call's
+ * feed samples before anything is submitted. */
+inline unsigned next_audio_frames(const fmd_batch* b, unsigned samples)
+{
+  const fmd_batch* x = b->subs.empty() ? b : b->subs[0].get();
+  const unsigned M = next_baseband_length(b, samples);
+  const float p = x->rs_pos, pstep = x->des.rs_step;
+  unsigned A = 0;
+  float pf = p;
+  while (unsigned(int(pf)) < M)
+  {
+    A++;
+    pf = p + float(A) * pstep;
+  }
+  return A;
 }
 
 /* launch_if_stage<IN> of the call's format */
@@ -378,7 +502,8 @@ inline int launch_if_stage_fmt(IqFormat fmt, fmd_batch* b, const void* d_iq, siz
 
 int process_device_impl(fmd_batch* b, const void* d_iq, IqFormat fmt, size_t iq_channel_stride,
                         unsigned samples, void* d_audio, PcmFormat pcm, size_t audio_channel_stride,
-                        unsigned* out_floats, void* stream_, const MpxJob& mpx = MpxJob())
+                        unsigned* out_floats, void* stream_, const MpxJob& mpx = MpxJob(),
+                        const FeedJob& feed = FeedJob())
 {
   if (!b || !d_iq || (!d_audio && audio_rows_due(b)))
     return fail(FMD_ERR_ARG, "fmd_batch_process_device: null argument");
@@ -468,6 +593,16 @@ int process_device_impl(fmd_batch* b, const void* d_iq, IqFormat fmt, size_t iq_
     return fail(FMD_ERR_ARG, "audio_channel_stride smaller than the audio produced");
   if (mpx.d && mpx.stride < M)
     return fail(FMD_ERR_ARG, "mpx_channel_stride smaller than the call's baseband length");
+  // the feed of the call: its first output and its sample count, from the frames of the feed calls so far
+  unsigned feed_p0 = 0, feed_n = 0;
+  if (feed.d)
+  {
+    if (!b->feed_div)
+      return fail(FMD_ERR_STATE, "the feed is off (fmd_batch_set_feed)");
+    feed_n = feed_samples_of(b->feed_g, A, b->feed_div, &feed_p0);
+    if (feed.stride < feed_n)
+      return fail(FMD_ERR_ARG, "feed_channel_stride smaller than the call's feed samples");
+  }
 
   const unsigned T_lpf = unsigned(d.rds_lpf_taps.size());
   const unsigned T_mf = unsigned(d.rds_mf_taps.size());
@@ -1014,6 +1149,13 @@ int process_device_impl(fmd_batch* b, const void* d_iq, IqFormat fmt, size_t iq_
   job.pcm = pcm;
   job.audio_stride = audio_channel_stride;
   job.asel = b->sel_audio.on ? &b->sel_audio : nullptr;
+  job.feed = feed.d != nullptr;
+  job.feed_deliver = feed.deliver;
+  job.d_feed = feed.d;
+  job.feed_fmt = feed.fmt;
+  job.feed_stride = feed.stride;
+  job.feed_p0 = feed_p0;
+  job.feed_n = feed_n;
   if (serial_mode || b->split_post)
   { // stage order of the reference (what the per-stage profile is keyed to), or two streams
     rds_heavy();
@@ -1140,6 +1282,10 @@ int process_device_impl(fmd_batch* b, const void* d_iq, IqFormat fmt, size_t iq_
     *out_floats = 2 * A;
   if (mpx.out)
     *mpx.out = mpx.d ? M : 0;
+  if (feed.d)
+    b->feed_g += A;
+  if (feed.out)
+    *feed.out = (feed.d && feed.deliver) ? feed_n : 0;
   return FMD_OK;
 }
 

@@ -142,6 +142,67 @@ __global__ __launch_bounds__(256) void k_audio_tail_s16_sel(const float2* __rest
 #undef FMD_TAIL_DONE_ARGS
 }
 
+/* The feed forms (fmd_batch_set_feed; fmd_k_feed.hip.h): the four kernels above with one argument more, feed_x = the
+ * first of the call's rows in the feed's scratch -- every lane that has a channel also stores the frame's mono mix
+ * there.  The same body text; chosen only for calls that deliver the feed, so the four above keep their
+ * instructions. */
+#define FMD_TAIL_FEED feed_x
+__global__ __launch_bounds__(256) void k_audio_tail_feed(const float2* __restrict__ lp, unsigned A, unsigned C,
+                                                        unsigned CP, AudioConsts k, ChannelState st,
+                                                        float* __restrict__ audio, size_t audio_stride,
+                                                        unsigned stereo_q, unsigned call_index,
+                                                        float* __restrict__ feed_x)
+{
+  using OUT = OutF32;
+#define FMD_TAIL_DONE_ARGS
+#include "fmd_audio_tail.inc"
+#undef FMD_TAIL_DONE_ARGS
+}
+
+__global__ __launch_bounds__(256) void k_audio_tail_s16_feed(const float2* __restrict__ lp, unsigned A, unsigned C,
+                                                            unsigned CP, AudioConsts k, ChannelState st,
+                                                            int16_t* __restrict__ audio, size_t audio_stride,
+                                                            unsigned stereo_q, unsigned call_index,
+                                                            unsigned long long* __restrict__ clipped,
+                                                            float* __restrict__ feed_x)
+{
+  using OUT = OutS16;
+#define FMD_TAIL_DONE_ARGS , clipped
+#include "fmd_audio_tail.inc"
+#undef FMD_TAIL_DONE_ARGS
+}
+
+__global__ __launch_bounds__(256) void k_audio_tail_sel_feed(const float2* __restrict__ lp, unsigned A, unsigned C,
+                                                            unsigned CP, AudioConsts k, ChannelState st,
+                                                            float* __restrict__ audio, size_t audio_stride,
+                                                            unsigned stereo_q, unsigned call_index,
+                                                            const int* __restrict__ rows, float* __restrict__ feed_x)
+{
+  using OUT = OutF32;
+#define FMD_TAIL_DONE_ARGS
+#define FMD_TAIL_ROWS rows
+#include "fmd_audio_tail.inc"
+#undef FMD_TAIL_ROWS
+#undef FMD_TAIL_DONE_ARGS
+}
+
+__global__ __launch_bounds__(256) void k_audio_tail_s16_sel_feed(const float2* __restrict__ lp, unsigned A, unsigned C,
+                                                                unsigned CP, AudioConsts k, ChannelState st,
+                                                                int16_t* __restrict__ audio, size_t audio_stride,
+                                                                unsigned stereo_q, unsigned call_index,
+                                                                unsigned long long* __restrict__ clipped,
+                                                                const int* __restrict__ rows,
+                                                                float* __restrict__ feed_x)
+{
+  using OUT = OutS16;
+#define FMD_TAIL_DONE_ARGS , clipped
+#define FMD_TAIL_ROWS rows
+#include "fmd_audio_tail.inc"
+#undef FMD_TAIL_ROWS
+#undef FMD_TAIL_DONE_ARGS
+}
+#undef FMD_TAIL_FEED
+
 /* The last kernel of a call: every channel's status record from device memory to the host's snapshot
  * under the per-channel sequence lock (HostStatusWord), a thread per channel -- one kernel of a few
  * waves pays the two system-scope fences, not the latency-bound audio tail. */
