@@ -24,6 +24,7 @@
 #include <utility>
 #include <vector>
 
+#include "fmd_call_plan.hpp"
 #include "fmd_design.hpp"
 #include "fmd_groups.hpp"
 #include "fmd_kernels.hip.h"
@@ -141,6 +142,78 @@ void launch(void (*kern)(P...), dim3 grid, dim3 block, unsigned lds, hipStream_t
   else
     hipLaunchKernelGGL(kern, grid, block, lds, s, static_cast<P>(args)...);
 }
+
+enum IqFormat
+{
+  IQ_F32 = 0, // complex<float>, the ProcessStream argument (FmDecode.h:135)
+  IQ_U8 = 1,  // RTL-SDR byte pairs, converted like ReadAsyncCB (RTL_SDR_Source.cpp:207-211)
+  IQ_S8 = 2,  // signed 8-bit pairs, v * 2^-7 (fmd_s8_to_f32)
+  IQ_S16 = 3  // signed 16-bit pairs in host byte order, v * 2^-15 (fmd_s16_to_f32)
+};
+static_assert(IQ_F32 == FMD_IQ_F32 && IQ_U8 == FMD_IQ_U8 && IQ_S8 == FMD_IQ_S8 && IQ_S16 == FMD_IQ_S16,
+              "the plan's formats are the C ABI's");
+
+/* The format arguments of the C ABI (FMD_IQ_*, FMD_PCM_*, FMD_MPX_*, FMD_FEED_*): the values each takes (0 .. last),
+ * the bytes of an element -- an IQ sample, one audio, multiplex or feed sample -- and what a refusal says. */
+enum FormatKind { FMT_IQ, FMT_PCM, FMT_MPX, FMT_FEED };
+struct FormatInfo
+{
+  int last;
+  unsigned char esz[4];
+  const char* must;
+};
+const FormatInfo kFormats[4] = {
+    {FMD_IQ_S16, {8, 2, 2, 4}, "iq_format must be one of FMD_IQ_F32, _U8, _S8, _S16 (0..3)"},
+    {FMD_PCM_S16, {4, 2}, "pcm_format must be FMD_PCM_F32 or FMD_PCM_S16 (0..1)"},
+    {FMD_MPX_S16, {4, 2}, "mpx_format must be FMD_MPX_F32 or FMD_MPX_S16 (0..1)"},
+    {FMD_FEED_S16, {4, 2}, "feed_format must be FMD_FEED_F32 or FMD_FEED_S16 (0..1)"}};
+
+/* a format argument, checked before anything else is touched */
+inline bool format_ok(FormatKind k, int format)
+{
+  return format >= 0 && format <= kFormats[k].last;
+}
+
+inline size_t format_esz(FormatKind k, int format)
+{
+  return kFormats[k].esz[format];
+}
+
+/* Where a call delivers one of its outputs -- the audio, the multiplex (the _mpx entry points), the feed (the _feed
+ * entry points); p == null: nowhere -- the call launches what a call without the argument launches (and the feed's
+ * frame count does not advance). */
+struct Out
+{
+  FormatKind kind;
+  void* p = nullptr;       // rows of the format, channel c at p + c * stride elements
+  int fmt = 0;             // FMD_PCM_* / FMD_MPX_* / FMD_FEED_*
+  size_t stride = 0;       // elements
+  unsigned* out = nullptr; // (host, optional) elements per row the call wrote
+  bool deliver = true;     // false: a feed selection of no rows -- the scratch and the count advance, nothing is written
+  size_t esz() const { return format_esz(kind, fmt); }
+  // a lane stores 16 bytes of a row at a time: every row has to start on a 16-byte boundary
+  bool rows_aligned() const { return !(reinterpret_cast<uintptr_t>(p) % 16) && !(stride % (16 / esz())); }
+  // (the rows of the sub-batch that starts at channel ch0: ch0 * stride elements of the output format on; with a
+  // selection every sub-batch writes into the one compact output, its table holds global row numbers)
+  Out from_channel(unsigned ch0, bool selection) const
+  {
+    Out o = *this;
+    if (p && !selection)
+      o.p = static_cast<char*>(p) + size_t(ch0) * stride * esz();
+    return o;
+  }
+};
+
+/* One call of a batch: the input rows, the three outputs, the caller's stream. */
+struct Call
+{
+  const void* iq = nullptr;
+  int iq_fmt = FMD_IQ_F32; // FMD_IQ_*
+  size_t iq_stride = 0;    // IQ samples between the input rows
+  unsigned samples = 0;
+  Out audio{FMT_PCM}, mpx{FMT_MPX}, feed{FMT_FEED};
+  void* stream = nullptr;
+};
 
 } // namespace
 
@@ -381,16 +454,11 @@ struct fmd_batch
     hipEvent_t prev_aud = nullptr;     // ... and the bit recovery for the previous call's status record
     uint32_t call_index = 0;
     int rb_mode = 0;                   // FMD_RDS_BLOCKS_*: which form of the bit recovery the call launches
-    void* d_audio = nullptr;           // rows of the call's output format (pcm: FMD_PCM_*), stride in its elements
-    int pcm = 0;
-    size_t audio_stride = 0;
+    Out audio{FMT_PCM};                // the call's audio rows
     hipEvent_t tl0 = nullptr, tl1 = nullptr; // profiling level 1: the audio tail's own start / stop
     Selection* asel = nullptr;         // the call's audio selection, or null: one row per channel
-    // the feed of a call that asked for it (feed: the tail's feed form, the roll; feed_deliver: k_feed_out as well)
-    bool feed = false, feed_deliver = false;
-    void* d_feed = nullptr;            // rows of feed_fmt (FMD_FEED_*), stride in its elements
-    int feed_fmt = 0;
-    size_t feed_stride = 0;
+    // the feed of a call that asked for it (feed.p: the tail's feed form, the roll; feed.deliver: k_feed_out as well)
+    Out feed{FMT_FEED};
     unsigned feed_p0 = 0, feed_n = 0;  // the call's first frame with an output, outputs of the call
   };
   /* More channels than the whole-CU pipeline is built for (kSubBatchChannels = 64 CUs' worth of serial stage): the
@@ -1874,81 +1942,65 @@ static int wait_impl(fmd_batch* b, int lag, void* stream_, bool take_lost);
 
 /* One call of any batch: a plain one directly; a shell's as one call of every sub-batch, in channel order, on the
  * same streams (fmd_batch::subs). */
-static int process_shell(fmd_batch* b, const void* d_iq, IqFormat fmt, size_t iq_channel_stride, unsigned samples,
-                         void* d_audio, PcmFormat pcm, size_t audio_channel_stride, unsigned* out_floats,
-                         void* stream, const MpxJob& mpx = MpxJob(), const FeedJob& feed = FeedJob());
+static int process_shell(fmd_batch* b, const Call& c);
 
 /* Pending single-channel edits (retunes, resets) in front of the call; with retuning enabled, the silent twin's call
  * (zeros of the same size, on the same streams) behind it.  A batch with neither takes the plain path alone. */
-static int process_any(fmd_batch* b, const void* d_iq, IqFormat fmt, size_t iq_channel_stride, unsigned samples,
-                       void* d_audio, PcmFormat pcm, size_t audio_channel_stride, unsigned* out_floats, void* stream,
-                       const MpxJob& mpx = MpxJob(), const FeedJob& feed = FeedJob())
+static int process_any(fmd_batch* b, const Call& c)
 {
   if (!b || (!b->twin && !b->edits_pending))
-    return process_shell(b, d_iq, fmt, iq_channel_stride, samples, d_audio, pcm, audio_channel_stride, out_floats,
-                         stream, mpx, feed);
-  if (!d_iq || (!d_audio && audio_rows_due(b)))
-    return fail(FMD_ERR_ARG, "fmd_batch_process_device: null argument");
-  if (samples > FMD_MAX_BLOCK || samples < b->min_samples)
-    return fail(FMD_ERR_SIZE, "samples must be within [fmd_batch_min_samples(), the largest block] = [" +
-                                  std::to_string(b->min_samples) + ", 65536]");
-  if (int rc = check_device_errors(b))
+    return process_shell(b, c);
+  fmd::CallPlan pl;
+  if (int rc = check_call(b, c, pl))
     return rc;
-  HIPCHK(hipSetDevice(b->device));
   fmd_batch* tw = b->twin.get();
   for (fmd_batch* x : buffer_batches(b))
-    if (int rc = submit_edits(x, tw, static_cast<hipStream_t>(stream)))
+    if (int rc = submit_edits(x, tw, static_cast<hipStream_t>(c.stream)))
     {
       mark_failed(b, "a channel edit could not be submitted");
       return rc;
     }
   b->edits_pending = false;
-  const int rc = process_shell(b, d_iq, fmt, iq_channel_stride, samples, d_audio, pcm, audio_channel_stride,
-                               out_floats, stream, mpx, feed);
+  const int rc = process_shell(b, c);
   if (rc != FMD_OK || !tw)
     return rc;
   // (the twin's audio is discarded: it stays float whatever the call's format; its multiplex is not written at all,
   // and it has no feed)
-  const int trc = process_device_impl(tw, b->twin_iq.p, IQ_F32, 0, samples, b->twin_audio.p, PCM_F32,
-                                      b->twin_audio.n, nullptr, stream);
+  Call t;
+  t.iq = b->twin_iq.p;
+  t.samples = c.samples;
+  t.audio.p = b->twin_audio.p;
+  t.audio.stride = b->twin_audio.n;
+  t.stream = c.stream;
+  const int trc = process_device_impl(tw, t);
   if (trc != FMD_OK)
     mark_failed(b, "the silent twin refused a call the batch took");
   return trc;
 }
 
-static int process_shell(fmd_batch* b, const void* d_iq, IqFormat fmt, size_t iq_channel_stride, unsigned samples,
-                         void* d_audio, PcmFormat pcm, size_t audio_channel_stride, unsigned* out_floats, void* stream,
-                         const MpxJob& mpx, const FeedJob& feed)
+static int process_shell(fmd_batch* b, const Call& c)
 {
   if (!b || b->subs.empty())
-    return process_device_impl(b, d_iq, fmt, iq_channel_stride, samples, d_audio, pcm, audio_channel_stride,
-                               out_floats, stream, mpx, feed);
-  if (!d_iq || (!d_audio && audio_rows_due(b)))
-    return fail(FMD_ERR_ARG, "fmd_batch_process_device: null argument");
-  if (int rc = check_device_errors(b))
+    return process_device_impl(b, c);
+  fmd::CallPlan pl;
+  if (int rc = check_call(b, c, pl))
     return rc;
-  const size_t esz = iq_esz(fmt); // bytes per IQ sample
   unsigned nf = 0;
   for (size_t k = 0; k < b->subs.size(); k++)
   {
     fmd_batch* sb = b->subs[k].get();
     const unsigned ch0 = b->sub_ch0[k];
     sb->sched_prev2 = b->vheavy[1];
+    Call sc = c;
     // (a capture map: every sub-batch takes the first row, its walk names the rows it reads)
     const size_t row0 = b->map_on ? 0 : ch0 / b->cpc;
-    const char* iq = static_cast<const char*>(d_iq) + row0 * iq_channel_stride * esz;
-    // (the sub-batch's first row: ch0 * stride elements of the output format; with a selection every sub-batch
-    // writes into the one compact output, its table holds global row numbers)
-    char* audio = static_cast<char*>(d_audio) +
-                  (b->sel_audio.on ? size_t(0) : size_t(ch0) * audio_channel_stride * pcm_esz(pcm));
-    MpxJob sub_mpx = mpx; // (the sub-batch's first multiplex row, like its first audio row)
-    if (mpx.d && !b->sel_mpx.on)
-      sub_mpx.d = static_cast<char*>(mpx.d) + size_t(ch0) * mpx.stride * mpx_esz(mpx.fmt);
-    FeedJob sub_feed = feed; // (... and its first feed row; every sub-batch counts the feed's frames for itself)
-    if (feed.d && !b->sel_feed.on)
-      sub_feed.d = static_cast<char*>(feed.d) + size_t(ch0) * feed.stride * feed_esz(feed.fmt);
-    const int rc = process_device_impl(sb, iq, fmt, iq_channel_stride, samples, audio, pcm, audio_channel_stride, &nf,
-                                       stream, sub_mpx, sub_feed);
+    sc.iq = static_cast<const char*>(c.iq) + row0 * c.iq_stride * format_esz(FMT_IQ, c.iq_fmt);
+    // (the sub-batch's first row of every output; every sub-batch counts the feed's frames for itself)
+    sc.audio = c.audio.from_channel(ch0, b->sel_audio.on);
+    sc.audio.out = &nf;
+    sc.mpx = c.mpx.from_channel(ch0, b->sel_mpx.on);
+    sc.feed = c.feed.from_channel(ch0, b->sel_feed.on);
+    const int rc = process_device_impl(sb, sc);
     if (rc != FMD_OK)
     { // the first sub-batch refuses what every one of them would refuse (same geometry, same positions): nothing
       // has been submitted.  Later: part of the call is on the device -- the batch is unusable until reset.
@@ -1966,30 +2018,104 @@ static int process_shell(fmd_batch* b, const void* d_iq, IqFormat fmt, size_t iq
   b->lastM = b->subs[0]->lastM;
   b->lastA = b->subs[0]->lastA;
   b->lastR = b->subs[0]->lastR;
-  if (out_floats)
-    *out_floats = nf;
+  if (c.audio.out)
+    *c.audio.out = nf;
   if (b->concurrency == 1) // the caller's stream is ordered after every call (the sub-batches run in mode 2)
-    return wait_impl(b, 0, stream, false);
+    return wait_impl(b, 0, c.stream, false);
   return FMD_OK;
+}
+
+/* A call as the entry points take it: the input, the audio rows and the stream (mpx and feed: the entry point's). */
+static Call make_call(const void* iq, int iq_format, size_t iq_stride, unsigned samples, void* audio, int pcm_format,
+                      size_t audio_stride, unsigned* out_samples, void* stream = nullptr)
+{
+  Call c;
+  c.iq = iq;
+  c.iq_fmt = iq_format;
+  c.iq_stride = iq_stride;
+  c.samples = samples;
+  c.audio = Out{FMT_PCM, audio, pcm_format, audio_stride, out_samples};
+  c.stream = stream;
+  return c;
+}
+
+/* What an entry point `who` checks of its arguments before the call goes on, for all of them in one order -- the
+ * formats; then WAY_DEVICE: the pointers and strides the kernels store through, WAY_HOST: what the staged copy needs
+ * (no alignment; a stride only between rows), WAY_FORMATS: nothing more (fmd_process_stream_*: the decoder comes
+ * next).  Checks of an output apply only when its pointer is given and, for the multiplex, its selection is not
+ * empty (a feed selection of no rows still counts the feed's frames).  Clears the out-counts a refused call would
+ * leave behind, drops the multiplex of a selection of no rows, and says whether the feed is delivered.  No HIP call
+ * in here: the refusals hold without a device. */
+enum CallWay { WAY_DEVICE, WAY_HOST, WAY_FORMATS };
+static int check_call_args(const char* who, CallWay way, fmd_batch* b, Call& c)
+{
+  auto refuse = [&](int code, const char* what) { return fail(code, std::string(who) + ": " + what); };
+  if (!format_ok(FMT_FEED, c.feed.fmt))
+    return refuse(FMD_ERR_ARG, kFormats[FMT_FEED].must);
+  if (c.feed.out)
+    *c.feed.out = 0;
+  if (!format_ok(FMT_MPX, c.mpx.fmt))
+    return refuse(FMD_ERR_ARG, kFormats[FMT_MPX].must);
+  if (!format_ok(FMT_IQ, c.iq_fmt))
+    return refuse(FMD_ERR_ARG, kFormats[FMT_IQ].must);
+  if (!format_ok(FMT_PCM, c.audio.fmt))
+    return refuse(FMD_ERR_ARG, kFormats[FMT_PCM].must);
+  if (way == WAY_FORMATS)
+    return FMD_OK;
+  const bool dev = way == WAY_DEVICE;
+  // a lane stores 16 bytes of a row at a time: every row has to start on a 16-byte boundary
+  if (dev && c.feed.p && !c.feed.rows_aligned())
+    return refuse(FMD_ERR_ARG, "the feed pointer must be 16-byte aligned and feed_channel_stride a multiple of 4 "
+                               "(FMD_FEED_F32) / 8 (FMD_FEED_S16) elements");
+  // (a device call's other null arguments get their own sentence further down)
+  if (!b || (!dev && (!c.iq || (!c.audio.p && audio_rows_due(b)))))
+    return refuse(FMD_ERR_ARG, "null argument");
+  if (c.feed.p && !b->feed_div)
+    return refuse(FMD_ERR_STATE, "a feed pointer while the feed is off (fmd_batch_set_feed turns it on)");
+  // four 16-bit frames go out as one 16-byte store: every row has to start on a 16-byte boundary
+  if (dev && c.audio.fmt == FMD_PCM_S16 && c.iq && c.audio.p && !c.audio.rows_aligned())
+    return refuse(FMD_ERR_ARG, "for FMD_PCM_S16 the audio pointer must be 16-byte aligned and audio_channel_stride a "
+                               "multiple of 8 elements");
+  const unsigned m_rows = b->sel_mpx.on ? b->sel_mpx.n_total : b->C;
+  const unsigned f_rows = b->sel_feed.on ? b->sel_feed.n_total : b->C;
+  if (m_rows == 0) // a selection of no rows: the call without the multiplex
+    c.mpx.p = nullptr;
+  if (c.mpx.out)
+    *c.mpx.out = 0;
+  c.feed.deliver = f_rows != 0;
+  if (!c.mpx.p && !c.feed.p)
+    return FMD_OK;
+  // the rows hold the call's samples -- looked at here, in front of the pending channel edits: a refused call leaves
+  // the batch as it was (a call refused for its size has no samples: check_call has the sentence)
+  const fmd_batch* x = b->subs.empty() ? b : b->subs[0].get();
+  fmd::CallPlan pl;
+  (void)fmd::plan_call(x->des, x->if_pos, x->rs_pos, x->feed_g, b->feed_div, c.samples, pl);
+  if (c.mpx.p && dev && !c.mpx.rows_aligned())
+    return refuse(FMD_ERR_ARG, "the multiplex pointer must be 16-byte aligned and mpx_channel_stride a multiple of 4 "
+                               "(FMD_MPX_F32) / 8 (FMD_MPX_S16) elements");
+  if (c.mpx.p && (dev || m_rows > 1) && c.mpx.stride < pl.M)
+    return refuse(FMD_ERR_ARG, "mpx_channel_stride smaller than the call's baseband length "
+                               "(fmd_batch_max_mpx_samples is the bound)");
+  if (c.feed.p && (dev || f_rows > 1) && c.feed.stride < pl.feed_n)
+    return refuse(FMD_ERR_ARG, "feed_channel_stride smaller than the call's feed samples "
+                               "(fmd_batch_max_feed_samples is the bound)");
+  return FMD_OK;
+}
+
+static int process_device_checked(const char* who, fmd_batch* b, Call& c)
+{
+  if (int rc = check_call_args(who, WAY_DEVICE, b, c))
+    return rc;
+  return process_any(b, c);
 }
 
 int fmd_batch_process_device_pcm(fmd_batch* b, const void* d_iq, int iq_format, size_t iq_channel_stride,
                                  unsigned samples, void* d_audio, int pcm_format, size_t audio_channel_stride,
                                  unsigned* out_samples, void* stream)
 {
-  if (!iq_format_ok(iq_format))
-    return fail(FMD_ERR_ARG,
-                "fmd_batch_process_device_pcm: iq_format must be one of FMD_IQ_F32, _U8, _S8, _S16 (0..3)");
-  if (!pcm_format_ok(pcm_format))
-    return fail(FMD_ERR_ARG, "fmd_batch_process_device_pcm: pcm_format must be FMD_PCM_F32 or FMD_PCM_S16 (0..1)");
-  // four 16-bit frames go out as one 16-byte store: every row has to start on a 16-byte boundary (a null argument
-  // gets its own sentence further down)
-  if (pcm_format == FMD_PCM_S16 && b && d_iq && d_audio &&
-      ((reinterpret_cast<uintptr_t>(d_audio) % 16) || (audio_channel_stride % 8)))
-    return fail(FMD_ERR_ARG, "fmd_batch_process_device_pcm: for FMD_PCM_S16 the audio pointer must be 16-byte aligned "
-                             "and audio_channel_stride a multiple of 8 elements");
-  return process_any(b, d_iq, IqFormat(iq_format), iq_channel_stride, samples, d_audio, PcmFormat(pcm_format),
-                     audio_channel_stride, out_samples, stream);
+  Call c = make_call(d_iq, iq_format, iq_channel_stride, samples, d_audio, pcm_format, audio_channel_stride,
+                     out_samples, stream);
+  return process_device_checked("fmd_batch_process_device_pcm", b, c);
 }
 
 int fmd_batch_process_device_mpx(fmd_batch* b, const void* d_iq, int iq_format, size_t iq_channel_stride,
@@ -1997,41 +2123,10 @@ int fmd_batch_process_device_mpx(fmd_batch* b, const void* d_iq, int iq_format, 
                                  unsigned* out_samples, void* d_mpx, int mpx_format, size_t mpx_channel_stride,
                                  unsigned* out_mpx_samples, void* stream)
 {
-  if (!mpx_format_ok(mpx_format))
-    return fail(FMD_ERR_ARG, "fmd_batch_process_device_mpx: mpx_format must be FMD_MPX_F32 or FMD_MPX_S16 (0..1)");
-  if (!iq_format_ok(iq_format))
-    return fail(FMD_ERR_ARG,
-                "fmd_batch_process_device_mpx: iq_format must be one of FMD_IQ_F32, _U8, _S8, _S16 (0..3)");
-  if (!pcm_format_ok(pcm_format))
-    return fail(FMD_ERR_ARG, "fmd_batch_process_device_mpx: pcm_format must be FMD_PCM_F32 or FMD_PCM_S16 (0..1)");
-  if (!d_mpx || (b && b->sel_mpx.on && b->sel_mpx.n_total == 0))
-  { // no multiplex (or a selection of no rows): the _pcm call, nothing else
-    if (out_mpx_samples)
-      *out_mpx_samples = 0;
-    return fmd_batch_process_device_pcm(b, d_iq, iq_format, iq_channel_stride, samples, d_audio, pcm_format,
-                                        audio_channel_stride, out_samples, stream);
-  }
-  if (!b)
-    return fail(FMD_ERR_ARG, "fmd_batch_process_device_mpx: null argument");
-  if (pcm_format == FMD_PCM_S16 && d_iq && d_audio &&
-      ((reinterpret_cast<uintptr_t>(d_audio) % 16) || (audio_channel_stride % 8)))
-    return fail(FMD_ERR_ARG, "fmd_batch_process_device_mpx: for FMD_PCM_S16 the audio pointer must be 16-byte aligned "
-                             "and audio_channel_stride a multiple of 8 elements");
-  // a lane stores 16 bytes of a row at a time: every row has to start on a 16-byte boundary, and hold the call's
-  // samples -- looked at here, in front of the pending channel edits: a refused call leaves the batch as it was
-  if ((reinterpret_cast<uintptr_t>(d_mpx) % 16) || (mpx_channel_stride % (mpx_format == FMD_MPX_S16 ? 8 : 4)))
-    return fail(FMD_ERR_ARG, "fmd_batch_process_device_mpx: the multiplex pointer must be 16-byte aligned and "
-                             "mpx_channel_stride a multiple of 4 (FMD_MPX_F32) / 8 (FMD_MPX_S16) elements");
-  if (mpx_channel_stride < next_baseband_length(b, samples))
-    return fail(FMD_ERR_ARG, "fmd_batch_process_device_mpx: mpx_channel_stride smaller than the call's baseband "
-                             "length (fmd_batch_max_mpx_samples is the bound)");
-  MpxJob mpx;
-  mpx.d = d_mpx;
-  mpx.fmt = MpxFormat(mpx_format);
-  mpx.stride = mpx_channel_stride;
-  mpx.out = out_mpx_samples;
-  return process_any(b, d_iq, IqFormat(iq_format), iq_channel_stride, samples, d_audio, PcmFormat(pcm_format),
-                     audio_channel_stride, out_samples, stream, mpx);
+  Call c = make_call(d_iq, iq_format, iq_channel_stride, samples, d_audio, pcm_format, audio_channel_stride,
+                     out_samples, stream);
+  c.mpx = Out{FMT_MPX, d_mpx, mpx_format, mpx_channel_stride, out_mpx_samples};
+  return process_device_checked("fmd_batch_process_device_mpx", b, c);
 }
 
 int fmd_batch_process_device_feed(fmd_batch* b, const void* d_iq, int iq_format, size_t iq_channel_stride,
@@ -2040,71 +2135,18 @@ int fmd_batch_process_device_feed(fmd_batch* b, const void* d_iq, int iq_format,
                                   unsigned* out_mpx_samples, void* d_feed, int feed_format, size_t feed_channel_stride,
                                   unsigned* out_feed_samples, void* stream)
 {
-  if (!feed_format_ok(feed_format))
-    return fail(FMD_ERR_ARG, "fmd_batch_process_device_feed: feed_format must be FMD_FEED_F32 or FMD_FEED_S16 (0..1)");
-  if (out_feed_samples)
-    *out_feed_samples = 0;
-  if (!d_feed) // no feed: the _mpx call, nothing else
-    return fmd_batch_process_device_mpx(b, d_iq, iq_format, iq_channel_stride, samples, d_audio, pcm_format,
-                                        audio_channel_stride, out_samples, d_mpx, mpx_format, mpx_channel_stride,
-                                        out_mpx_samples, stream);
-  if (!mpx_format_ok(mpx_format))
-    return fail(FMD_ERR_ARG, "fmd_batch_process_device_feed: mpx_format must be FMD_MPX_F32 or FMD_MPX_S16 (0..1)");
-  if (!iq_format_ok(iq_format))
-    return fail(FMD_ERR_ARG,
-                "fmd_batch_process_device_feed: iq_format must be one of FMD_IQ_F32, _U8, _S8, _S16 (0..3)");
-  if (!pcm_format_ok(pcm_format))
-    return fail(FMD_ERR_ARG, "fmd_batch_process_device_feed: pcm_format must be FMD_PCM_F32 or FMD_PCM_S16 (0..1)");
-  // a lane stores 16 bytes of a row at a time: every row has to start on a 16-byte boundary
-  if ((reinterpret_cast<uintptr_t>(d_feed) % 16) || (feed_channel_stride % (feed_format == FMD_FEED_S16 ? 8 : 4)))
-    return fail(FMD_ERR_ARG, "fmd_batch_process_device_feed: the feed pointer must be 16-byte aligned and "
-                             "feed_channel_stride a multiple of 4 (FMD_FEED_F32) / 8 (FMD_FEED_S16) elements");
-  if (!b)
-    return fail(FMD_ERR_ARG, "fmd_batch_process_device_feed: null argument");
-  if (!b->feed_div)
-    return fail(FMD_ERR_STATE, "fmd_batch_process_device_feed: a feed pointer while the feed is off "
-                               "(fmd_batch_set_feed turns it on)");
-  if (pcm_format == FMD_PCM_S16 && d_iq && d_audio &&
-      ((reinterpret_cast<uintptr_t>(d_audio) % 16) || (audio_channel_stride % 8)))
-    return fail(FMD_ERR_ARG, "fmd_batch_process_device_feed: for FMD_PCM_S16 the audio pointer must be 16-byte aligned "
-                             "and audio_channel_stride a multiple of 8 elements");
-  MpxJob mpx;
-  if (d_mpx && !(b->sel_mpx.on && b->sel_mpx.n_total == 0))
-  {
-    if ((reinterpret_cast<uintptr_t>(d_mpx) % 16) || (mpx_channel_stride % (mpx_format == FMD_MPX_S16 ? 8 : 4)))
-      return fail(FMD_ERR_ARG, "fmd_batch_process_device_feed: the multiplex pointer must be 16-byte aligned and "
-                               "mpx_channel_stride a multiple of 4 (FMD_MPX_F32) / 8 (FMD_MPX_S16) elements");
-    if (mpx_channel_stride < next_baseband_length(b, samples))
-      return fail(FMD_ERR_ARG, "fmd_batch_process_device_feed: mpx_channel_stride smaller than the call's baseband "
-                               "length (fmd_batch_max_mpx_samples is the bound)");
-    mpx.d = d_mpx;
-    mpx.fmt = MpxFormat(mpx_format);
-    mpx.stride = mpx_channel_stride;
-  }
-  mpx.out = out_mpx_samples;
-  if (out_mpx_samples)
-    *out_mpx_samples = 0;
-  // the rows hold the call's samples -- looked at here, in front of the pending channel edits: a refused call leaves
-  // the batch as it was
-  const fmd_batch* x = b->subs.empty() ? b : b->subs[0].get();
-  if (feed_channel_stride < feed_samples_of(x->feed_g, next_audio_frames(b, samples), b->feed_div))
-    return fail(FMD_ERR_ARG, "fmd_batch_process_device_feed: feed_channel_stride smaller than the call's feed samples "
-                             "(fmd_batch_max_feed_samples is the bound)");
-  FeedJob feed;
-  feed.d = d_feed;
-  feed.fmt = FeedFormat(feed_format);
-  feed.stride = feed_channel_stride;
-  feed.out = out_feed_samples;
-  feed.deliver = !(b->sel_feed.on && b->sel_feed.n_total == 0);
-  return process_any(b, d_iq, IqFormat(iq_format), iq_channel_stride, samples, d_audio, PcmFormat(pcm_format),
-                     audio_channel_stride, out_samples, stream, mpx, feed);
+  Call c = make_call(d_iq, iq_format, iq_channel_stride, samples, d_audio, pcm_format, audio_channel_stride,
+                     out_samples, stream);
+  c.mpx = Out{FMT_MPX, d_mpx, mpx_format, mpx_channel_stride, out_mpx_samples};
+  c.feed = Out{FMT_FEED, d_feed, feed_format, feed_channel_stride, out_feed_samples};
+  return process_device_checked("fmd_batch_process_device_feed", b, c);
 }
 
 int fmd_batch_process_device_fmt(fmd_batch* b, const void* d_iq, int format, size_t iq_channel_stride,
                                  unsigned samples, float* d_audio, size_t audio_channel_stride,
                                  unsigned* out_floats, void* stream)
 {
-  if (!iq_format_ok(format))
+  if (!format_ok(FMT_IQ, format))
     return fail(FMD_ERR_ARG, "fmd_batch_process_device_fmt: format must be one of FMD_IQ_F32, _U8, _S8, _S16 (0..3)");
   return fmd_batch_process_device_pcm(b, d_iq, format, iq_channel_stride, samples, d_audio, FMD_PCM_F32,
                                       audio_channel_stride, out_floats, stream);
@@ -2923,100 +2965,88 @@ int fmd_batch_export_rds_device(fmd_batch* b, int32_t* d_records, unsigned cap, 
   return take_lost_groups(b);
 }
 
-static int process_host_impl(fmd_batch* b, const void* iq, IqFormat fmt, size_t iq_channel_stride,
-                             unsigned samples, void* audio, PcmFormat pcm, size_t audio_channel_stride,
-                             unsigned* out_floats, void* mpx = nullptr, MpxFormat mpx_fmt = MPX_F32,
-                             size_t mpx_channel_stride = 0, unsigned* out_mpx = nullptr, void* feed = nullptr,
-                             FeedFormat feed_fmt = FEED_F32, size_t feed_channel_stride = 0,
-                             unsigned* out_feed = nullptr)
+/* One output of a host call on its way through the device.  stage(): the device-side descriptor of host output h --
+ * rows (one per channel, or the selection's) of at most cap elements in buf, grown on demand, at a stride that puts
+ * every row on a 16-byte boundary; its count goes to n.  fetch(): the rows' n elements back into the caller's array,
+ * laid out as that many rows (one row: packed). */
+struct StagedOut
 {
-  if (!b || !iq || (!audio && audio_rows_due(b)))
-    return fail(FMD_ERR_ARG, "fmd_batch_process_host: null argument");
-  if (feed && !b->feed_div)
-    return fail(FMD_ERR_STATE, "fmd_batch_process_host_feed: a feed pointer while the feed is off (fmd_batch_set_feed "
-                               "turns it on)");
+  Out dev{FMT_PCM};
+  unsigned rows = 0, n = 0;
+  int stage(DevBuf<float>& buf, const Out& h, const fmd_batch::Selection& sel, unsigned C, size_t cap)
+  {
+    rows = sel.on ? sel.n_total : C;
+    const size_t round = 16 / h.esz() - 1;
+    dev = h;
+    dev.stride = (cap + round) & ~round;
+    dev.out = &n;
+    // (a selection of no rows stages one row nobody writes)
+    const size_t floats = dev.stride * std::max(rows, 1u) * h.esz() / sizeof(float);
+    if (floats > buf.n && buf.alloc(floats))
+      return fail(FMD_ERR_DEVICE, "staging allocation failed");
+    dev.p = buf.p;
+    return FMD_OK;
+  }
+  int fetch(const Out& h) const
+  {
+    const size_t esz = h.esz();
+    if (h.p && n && rows)
+      HIPCHK(hipMemcpy2D(h.p, (rows > 1 ? h.stride : size_t(n)) * esz, dev.p, dev.stride * esz, size_t(n) * esz, rows,
+                         hipMemcpyDeviceToHost));
+    return FMD_OK;
+  }
+};
+
+/* A host call that check_call_args has passed: staged in, one device call, staged out. */
+static int process_host_impl(fmd_batch* b, const Call& c)
+{
   HIPCHK(hipSetDevice(b->device));
-  const unsigned C = b->C;
-  // rows of the two outputs: one per channel, or the selections' (fmd_batch_select_audio / _mpx) -- staged, copied
-  // back and laid out in the caller's arrays as that many rows
-  const unsigned a_rows = b->sel_audio.on ? b->sel_audio.n_total : C;
-  const unsigned m_rows = b->sel_mpx.on ? b->sel_mpx.n_total : C;
-  if (m_rows == 0) // a selection of no rows: the call without the multiplex
-    mpx = nullptr;
-  // multiplex staging: rows of m_stride elements, every row on a 16-byte boundary; the caller's rows have to hold
-  // the call's samples (known before the call: nothing is submitted for a refused one)
-  MpxJob mj;
-  const size_t msz = mpx_esz(mpx_fmt);
-  const size_t m_round = mpx_fmt == MPX_S16 ? 7 : 3;
-  const size_t m_stride = (size_t(fmd_batch_max_mpx_samples(b, samples)) + m_round) & ~m_round;
-  unsigned nm = 0;
-  if (mpx)
+  const unsigned C = b->C, samples = c.samples;
+  // the outputs' staging -- audio; multiplex and feed where the call has them (the feed's rows one element longer
+  // than fmd_batch_max_feed_samples)
+  Call d = c;
+  d.stream = nullptr;
+  StagedOut sa, sm, sf;
+  if (int rc = sa.stage(b->h_audio, c.audio, b->sel_audio, C, fmd_batch_max_audio_floats(b, samples)))
+    return rc;
+  d.audio = sa.dev;
+  if (c.mpx.p)
   {
-    if (m_rows > 1 && mpx_channel_stride < next_baseband_length(b, samples))
-      return fail(FMD_ERR_ARG, "fmd_batch_process_host_mpx: mpx_channel_stride smaller than the call's baseband "
-                               "length (fmd_batch_max_mpx_samples is the bound)");
-    const size_t mpx_floats = m_stride * m_rows * msz / sizeof(float);
-    if (mpx_floats > b->h_mpx.n && b->h_mpx.alloc(mpx_floats))
-      return fail(FMD_ERR_DEVICE, "staging allocation failed");
-    mj.d = b->h_mpx.p;
-    mj.fmt = mpx_fmt;
-    mj.stride = m_stride;
-    mj.out = &nm;
+    if (int rc = sm.stage(b->h_mpx, c.mpx, b->sel_mpx, C, fmd_batch_max_mpx_samples(b, samples)))
+      return rc;
+    d.mpx = sm.dev;
   }
-  // feed staging, the same way: rows of f_stride elements on 16-byte boundaries; a selection of no rows stages one
-  // row nobody writes (the call still counts the feed's frames)
-  FeedJob fj;
-  const unsigned f_rows = b->sel_feed.on ? b->sel_feed.n_total : C;
-  const size_t fsz = feed_esz(feed_fmt);
-  const size_t f_round = feed_fmt == FEED_S16 ? 7 : 3;
-  const size_t f_stride = (size_t(fmd_batch_max_feed_samples(b, samples)) + f_round + 1) & ~f_round;
-  unsigned nfeed = 0;
-  if (feed)
+  if (c.feed.p)
   {
-    const fmd_batch* x = b->subs.empty() ? b : b->subs[0].get();
-    if (f_rows > 1 &&
-        feed_channel_stride < feed_samples_of(x->feed_g, next_audio_frames(b, samples), b->feed_div))
-      return fail(FMD_ERR_ARG, "fmd_batch_process_host_feed: feed_channel_stride smaller than the call's feed samples "
-                               "(fmd_batch_max_feed_samples is the bound)");
-    const size_t feed_floats = f_stride * std::max(f_rows, 1u) * fsz / sizeof(float);
-    if (feed_floats > b->h_feed.n && b->h_feed.alloc(feed_floats))
-      return fail(FMD_ERR_DEVICE, "staging allocation failed");
-    fj.d = b->h_feed.p;
-    fj.fmt = feed_fmt;
-    fj.stride = f_stride;
-    fj.out = &nfeed;
-    fj.deliver = f_rows != 0;
+    if (int rc = sf.stage(b->h_feed, c.feed, b->sel_feed, C, size_t(fmd_batch_max_feed_samples(b, samples)) + 1))
+      return rc;
+    d.feed = sf.dev;
   }
-  const size_t esz = iq_esz(fmt); // bytes per IQ sample
+  const size_t esz = format_esz(FMT_IQ, c.iq_fmt); // bytes per IQ sample
   // device copy: one row per channel, rows padded to a whole pair of samples
   const size_t dev_row = (size_t(samples) + 1) / 2 * 2 * esz;
-  const size_t dev_iq_stride = iq_channel_stride ? dev_row / esz : 0;
+  d.iq_stride = c.iq_stride ? dev_row / esz : 0;
   // input rows: one per capture of the map, per channel, per cpc channels, or one
-  const unsigned streams = !iq_channel_stride ? 1u : b->map_on ? b->n_cap : C / b->cpc;
+  const unsigned streams = !c.iq_stride ? 1u : b->map_on ? b->n_cap : C / b->cpc;
   const size_t iq_floats = (dev_row * streams + 3) / 4;
-  // audio staging: rows of a_stride elements of the output format, every row on a 16-byte boundary
-  const size_t asz = pcm_esz(pcm);
-  const size_t a_round = pcm == PCM_S16 ? 7 : 3;
-  const size_t a_stride = (size_t(fmd_batch_max_audio_floats(b, samples)) + a_round) & ~a_round;
-  const size_t audio_floats = a_stride * a_rows * asz / sizeof(float);
-  if ((iq_floats > b->h_iq.n && b->h_iq.alloc(iq_floats)) ||
-      (audio_floats > b->h_audio.n && b->h_audio.alloc(audio_floats)))
+  if (iq_floats > b->h_iq.n && b->h_iq.alloc(iq_floats))
     return fail(FMD_ERR_DEVICE, "staging allocation failed");
+  d.iq = b->h_iq.p;
   using clk = std::chrono::steady_clock;
   auto ms_since = [](clk::time_point t) { return std::chrono::duration<double, std::milli>(clk::now() - t).count(); };
   clk::time_point tp = clk::now();
-  if (iq_channel_stride)
-    HIPCHK(hipMemcpy2D(b->h_iq.p, dev_row, iq, iq_channel_stride * esz, size_t(samples) * esz, streams,
+  if (c.iq_stride)
+    HIPCHK(hipMemcpy2D(b->h_iq.p, dev_row, c.iq, c.iq_stride * esz, size_t(samples) * esz, streams,
                        hipMemcpyHostToDevice));
   else
-    HIPCHK(hipMemcpy(b->h_iq.p, iq, size_t(samples) * esz, hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(b->h_iq.p, c.iq, size_t(samples) * esz, hipMemcpyHostToDevice));
   b->host_ms[0] += ms_since(tp);
   tp = clk::now();
-  unsigned nf = 0;
-  int rc = process_any(b, b->h_iq.p, fmt, dev_iq_stride, samples, b->h_audio.p, pcm, a_stride, &nf, nullptr, mj, fj);
+  int rc = process_any(b, d);
   if (rc != FMD_OK)
     return rc;
-  if (a_rows > 1 && nf > audio_channel_stride)
+  const unsigned nf = sa.n;
+  if (sa.rows > 1 && nf > c.audio.stride)
     return fail(FMD_ERR_ARG, "audio_channel_stride smaller than the audio produced");
   b->host_ms[1] += ms_since(tp);
   tp = clk::now();
@@ -3025,19 +3055,12 @@ static int process_host_impl(fmd_batch* b, const void* iq, IqFormat fmt, size_t 
   rc = wait_impl(b, 0, nullptr, false); // the groups-lost flag is this call's to report, at its end
   if (rc < 0)
     return rc;
-  if (a_rows)
-    HIPCHK(hipMemcpy2D(audio, (a_rows > 1 ? audio_channel_stride : size_t(nf)) * asz, b->h_audio.p, a_stride * asz,
-                       size_t(nf) * asz, a_rows, hipMemcpyDeviceToHost));
-  if (mpx && nm)
-    HIPCHK(hipMemcpy2D(mpx, (m_rows > 1 ? mpx_channel_stride : size_t(nm)) * msz, b->h_mpx.p, m_stride * msz,
-                       size_t(nm) * msz, m_rows, hipMemcpyDeviceToHost));
-  if (out_mpx)
-    *out_mpx = nm;
-  if (feed && nfeed && f_rows)
-    HIPCHK(hipMemcpy2D(feed, (f_rows > 1 ? feed_channel_stride : size_t(nfeed)) * fsz, b->h_feed.p, f_stride * fsz,
-                       size_t(nfeed) * fsz, f_rows, hipMemcpyDeviceToHost));
-  if (out_feed)
-    *out_feed = nfeed;
+  if ((rc = sa.fetch(c.audio)) || (rc = sm.fetch(c.mpx)) || (rc = sf.fetch(c.feed)))
+    return rc;
+  if (c.mpx.out)
+    *c.mpx.out = sm.n;
+  if (c.feed.out)
+    *c.feed.out = sf.n;
   b->host_ms[2] += ms_since(tp);
   tp = clk::now();
   rc = fmd_batch_collect_rds(b, nullptr, 0, 1, nullptr);
@@ -3045,21 +3068,24 @@ static int process_host_impl(fmd_batch* b, const void* iq, IqFormat fmt, size_t 
     return rc;
   b->host_ms[3] += ms_since(tp);
   b->host_calls++;
-  if (out_floats)
-    *out_floats = nf;
+  if (c.audio.out)
+    *c.audio.out = nf;
   return take_lost_groups(b); // FMD_OK, or FMD_WARN_RDS_LOST once: audio and state are intact
+}
+
+static int process_host_checked(const char* who, fmd_batch* b, Call& c)
+{
+  if (int rc = check_call_args(who, WAY_HOST, b, c))
+    return rc;
+  return process_host_impl(b, c);
 }
 
 int fmd_batch_process_host_pcm(fmd_batch* b, const void* iq, int iq_format, size_t iq_channel_stride,
                                unsigned samples, void* audio, int pcm_format, size_t audio_channel_stride,
                                unsigned* out_samples)
 {
-  if (!iq_format_ok(iq_format))
-    return fail(FMD_ERR_ARG, "fmd_batch_process_host_pcm: iq_format must be one of FMD_IQ_F32, _U8, _S8, _S16 (0..3)");
-  if (!pcm_format_ok(pcm_format))
-    return fail(FMD_ERR_ARG, "fmd_batch_process_host_pcm: pcm_format must be FMD_PCM_F32 or FMD_PCM_S16 (0..1)");
-  return process_host_impl(b, iq, IqFormat(iq_format), iq_channel_stride, samples, audio, PcmFormat(pcm_format),
-                           audio_channel_stride, out_samples);
+  Call c = make_call(iq, iq_format, iq_channel_stride, samples, audio, pcm_format, audio_channel_stride, out_samples);
+  return process_host_checked("fmd_batch_process_host_pcm", b, c);
 }
 
 int fmd_batch_process_host_mpx(fmd_batch* b, const void* iq, int iq_format, size_t iq_channel_stride,
@@ -3067,15 +3093,9 @@ int fmd_batch_process_host_mpx(fmd_batch* b, const void* iq, int iq_format, size
                                unsigned* out_samples, void* mpx, int mpx_format, size_t mpx_channel_stride,
                                unsigned* out_mpx_samples)
 {
-  if (!mpx_format_ok(mpx_format))
-    return fail(FMD_ERR_ARG, "fmd_batch_process_host_mpx: mpx_format must be FMD_MPX_F32 or FMD_MPX_S16 (0..1)");
-  if (!iq_format_ok(iq_format))
-    return fail(FMD_ERR_ARG, "fmd_batch_process_host_mpx: iq_format must be one of FMD_IQ_F32, _U8, _S8, _S16 (0..3)");
-  if (!pcm_format_ok(pcm_format))
-    return fail(FMD_ERR_ARG, "fmd_batch_process_host_mpx: pcm_format must be FMD_PCM_F32 or FMD_PCM_S16 (0..1)");
-  return process_host_impl(b, iq, IqFormat(iq_format), iq_channel_stride, samples, audio, PcmFormat(pcm_format),
-                           audio_channel_stride, out_samples, mpx, MpxFormat(mpx_format), mpx_channel_stride,
-                           out_mpx_samples);
+  Call c = make_call(iq, iq_format, iq_channel_stride, samples, audio, pcm_format, audio_channel_stride, out_samples);
+  c.mpx = Out{FMT_MPX, mpx, mpx_format, mpx_channel_stride, out_mpx_samples};
+  return process_host_checked("fmd_batch_process_host_mpx", b, c);
 }
 
 int fmd_batch_process_host_feed(fmd_batch* b, const void* iq, int iq_format, size_t iq_channel_stride,
@@ -3084,25 +3104,16 @@ int fmd_batch_process_host_feed(fmd_batch* b, const void* iq, int iq_format, siz
                                 unsigned* out_mpx_samples, void* feed, int feed_format, size_t feed_channel_stride,
                                 unsigned* out_feed_samples)
 {
-  if (!feed_format_ok(feed_format))
-    return fail(FMD_ERR_ARG, "fmd_batch_process_host_feed: feed_format must be FMD_FEED_F32 or FMD_FEED_S16 (0..1)");
-  if (!mpx_format_ok(mpx_format))
-    return fail(FMD_ERR_ARG, "fmd_batch_process_host_feed: mpx_format must be FMD_MPX_F32 or FMD_MPX_S16 (0..1)");
-  if (!iq_format_ok(iq_format))
-    return fail(FMD_ERR_ARG, "fmd_batch_process_host_feed: iq_format must be one of FMD_IQ_F32, _U8, _S8, _S16 (0..3)");
-  if (!pcm_format_ok(pcm_format))
-    return fail(FMD_ERR_ARG, "fmd_batch_process_host_feed: pcm_format must be FMD_PCM_F32 or FMD_PCM_S16 (0..1)");
-  if (out_feed_samples)
-    *out_feed_samples = 0;
-  return process_host_impl(b, iq, IqFormat(iq_format), iq_channel_stride, samples, audio, PcmFormat(pcm_format),
-                           audio_channel_stride, out_samples, mpx, MpxFormat(mpx_format), mpx_channel_stride,
-                           out_mpx_samples, feed, FeedFormat(feed_format), feed_channel_stride, out_feed_samples);
+  Call c = make_call(iq, iq_format, iq_channel_stride, samples, audio, pcm_format, audio_channel_stride, out_samples);
+  c.mpx = Out{FMT_MPX, mpx, mpx_format, mpx_channel_stride, out_mpx_samples};
+  c.feed = Out{FMT_FEED, feed, feed_format, feed_channel_stride, out_feed_samples};
+  return process_host_checked("fmd_batch_process_host_feed", b, c);
 }
 
 int fmd_batch_process_host_fmt(fmd_batch* b, const void* iq, int format, size_t iq_channel_stride, unsigned samples,
                                float* audio, size_t audio_channel_stride, unsigned* out_floats)
 {
-  if (!iq_format_ok(format))
+  if (!format_ok(FMT_IQ, format))
     return fail(FMD_ERR_ARG, "fmd_batch_process_host_fmt: format must be one of FMD_IQ_F32, _U8, _S8, _S16 (0..3)");
   return fmd_batch_process_host_pcm(b, iq, format, iq_channel_stride, samples, audio, FMD_PCM_F32,
                                     audio_channel_stride, out_floats);
@@ -3653,59 +3664,45 @@ int fmd_reset(fmd_decoder* d)
   return d ? fmd_batch_reset(d->b) : fail(FMD_ERR_ARG, "null decoder");
 }
 
-int fmd_process_stream_pcm(fmd_decoder* d, const void* iq, int iq_format, unsigned samples, void* audio,
-                           int pcm_format)
+/* fmd_process_stream_*: the formats, the decoder, then the host call of its batch; the audio's length on success */
+static int process_stream_checked(const char* who, const char* host_who, fmd_decoder* d, Call& c)
 {
-  if (!iq_format_ok(iq_format))
-    return fail(FMD_ERR_ARG, "fmd_process_stream_pcm: iq_format must be one of FMD_IQ_F32, _U8, _S8, _S16 (0..3)");
-  if (!pcm_format_ok(pcm_format))
-    return fail(FMD_ERR_ARG, "fmd_process_stream_pcm: pcm_format must be FMD_PCM_F32 or FMD_PCM_S16 (0..1)");
+  if (int rc = check_call_args(who, WAY_FORMATS, nullptr, c))
+    return rc;
   if (!d)
     return fail(FMD_ERR_ARG, "null decoder");
   unsigned nf = 0;
-  int rc = fmd_batch_process_host_pcm(d->b, iq, iq_format, 0, samples, audio, pcm_format, 0, &nf);
+  c.audio.out = &nf;
+  const int rc = process_host_checked(host_who, d->b, c);
   return rc < 0 ? rc : int(nf); // (a groups-lost warning does not touch the audio: fmd_last_error has it)
+}
+
+int fmd_process_stream_pcm(fmd_decoder* d, const void* iq, int iq_format, unsigned samples, void* audio,
+                           int pcm_format)
+{
+  Call c = make_call(iq, iq_format, 0, samples, audio, pcm_format, 0, nullptr);
+  return process_stream_checked("fmd_process_stream_pcm", "fmd_batch_process_host_pcm", d, c);
 }
 
 int fmd_process_stream_mpx(fmd_decoder* d, const void* iq, int iq_format, unsigned samples, void* audio,
                            int pcm_format, void* mpx, int mpx_format, unsigned* mpx_samples)
 {
-  if (!mpx_format_ok(mpx_format))
-    return fail(FMD_ERR_ARG, "fmd_process_stream_mpx: mpx_format must be FMD_MPX_F32 or FMD_MPX_S16 (0..1)");
-  if (!iq_format_ok(iq_format))
-    return fail(FMD_ERR_ARG, "fmd_process_stream_mpx: iq_format must be one of FMD_IQ_F32, _U8, _S8, _S16 (0..3)");
-  if (!pcm_format_ok(pcm_format))
-    return fail(FMD_ERR_ARG, "fmd_process_stream_mpx: pcm_format must be FMD_PCM_F32 or FMD_PCM_S16 (0..1)");
-  if (!d)
-    return fail(FMD_ERR_ARG, "null decoder");
-  unsigned nf = 0;
-  int rc = fmd_batch_process_host_mpx(d->b, iq, iq_format, 0, samples, audio, pcm_format, 0, &nf, mpx, mpx_format, 0,
-                                      mpx_samples);
-  return rc < 0 ? rc : int(nf);
+  Call c = make_call(iq, iq_format, 0, samples, audio, pcm_format, 0, nullptr);
+  c.mpx = Out{FMT_MPX, mpx, mpx_format, 0, mpx_samples};
+  return process_stream_checked("fmd_process_stream_mpx", "fmd_batch_process_host_mpx", d, c);
 }
 
 int fmd_process_stream_feed(fmd_decoder* d, const void* iq, int iq_format, unsigned samples, void* audio,
                             int pcm_format, void* feed, int feed_format, unsigned* feed_samples)
 {
-  if (!feed_format_ok(feed_format))
-    return fail(FMD_ERR_ARG, "fmd_process_stream_feed: feed_format must be FMD_FEED_F32 or FMD_FEED_S16 (0..1)");
-  if (!iq_format_ok(iq_format))
-    return fail(FMD_ERR_ARG, "fmd_process_stream_feed: iq_format must be one of FMD_IQ_F32, _U8, _S8, _S16 (0..3)");
-  if (!pcm_format_ok(pcm_format))
-    return fail(FMD_ERR_ARG, "fmd_process_stream_feed: pcm_format must be FMD_PCM_F32 or FMD_PCM_S16 (0..1)");
-  if (feed_samples)
-    *feed_samples = 0;
-  if (!d)
-    return fail(FMD_ERR_ARG, "null decoder");
-  unsigned nf = 0;
-  int rc = fmd_batch_process_host_feed(d->b, iq, iq_format, 0, samples, audio, pcm_format, 0, &nf, nullptr,
-                                       FMD_MPX_F32, 0, nullptr, feed, feed_format, 0, feed_samples);
-  return rc < 0 ? rc : int(nf);
+  Call c = make_call(iq, iq_format, 0, samples, audio, pcm_format, 0, nullptr);
+  c.feed = Out{FMT_FEED, feed, feed_format, 0, feed_samples};
+  return process_stream_checked("fmd_process_stream_feed", "fmd_batch_process_host_feed", d, c);
 }
 
 int fmd_process_stream_fmt(fmd_decoder* d, const void* iq, int format, unsigned samples, float* audio)
 {
-  if (!iq_format_ok(format))
+  if (!format_ok(FMT_IQ, format))
     return fail(FMD_ERR_ARG, "fmd_process_stream_fmt: format must be one of FMD_IQ_F32, _U8, _S8, _S16 (0..3)");
   return fmd_process_stream_pcm(d, iq, format, samples, audio, FMD_PCM_F32);
 }
@@ -3917,7 +3914,7 @@ void fmd_receiver_close(fmd_receiver* r)
 
 int fmd_receiver_write_fmt(fmd_receiver* r, const void* buf, int format, unsigned samples)
 {
-  if (!iq_format_ok(format))
+  if (!format_ok(FMT_IQ, format))
     return fail(FMD_ERR_ARG, "fmd_receiver_write_fmt: format must be one of FMD_IQ_F32, _U8, _S8, _S16 (0..3)");
   if (!r || (!buf && samples))
     return fail(FMD_ERR_ARG, "fmd_receiver_write_fmt: null argument");

@@ -1,7 +1,8 @@
 /*
- * fmd_batch_process.inc.hpp -- one call of a batch: the position plan the host replays (DownConvert.cpp:112-132,
- * 203-232; FirFilter.cpp:346), the choice of kernel forms behind the IF stage, and the launches of all stages on the
- * batch's internal streams with the events that tie them (process_device_impl); the light part's launch helpers.
+ * fmd_batch_process.inc.hpp -- one call of a batch: the check in front of it (check_call, with the position plan of
+ * fmd_call_plan.hpp: DownConvert.cpp:112-132, 203-232; FirFilter.cpp:346), the choice of kernel forms behind the IF
+ * stage, and the launches of all stages on the batch's internal streams with the events that tie them
+ * (process_device_impl); the light part's launch helpers.
  * Included by fmd_batch.hip behind fmd_batch_if.inc.hpp (one translation unit: it uses that file's fmd_batch
  * struct and helpers).
  */
@@ -239,34 +240,35 @@ void sel_read_done(fmd_batch* b, fmd_batch::Selection& sel, hipStream_t st)
 void launch_feed(fmd_batch* b, const fmd_batch::LightJob& j, hipStream_t s)
 {
   const unsigned C = b->C, CP = b->CP, T = b->feed_T, D = b->feed_div, n = j.feed_n;
+  const Out& f = j.feed;
   const unsigned tiles = (n + fmd::FEED_T - 1) / fmd::FEED_T;
-  if (j.feed_deliver && n && b->sel_feed.on)
+  if (f.deliver && n && b->sel_feed.on)
   { // the selected writer (fmd_batch_select_feed): tiles of 64 entries of this batch's part of the list
     const unsigned ns = unsigned(b->sel_feed.ent.size());
     const int* tab = ns ? sel_table(b, b->sel_feed, true, s) : nullptr;
     if (tab)
     {
       const dim3 g((ns + 63) / 64, tiles);
-      if (j.feed_fmt == FMD_FEED_S16)
+      if (f.fmt == FMD_FEED_S16)
         hipLaunchKernelGGL(fmd::k_feed_out_sel<fmd::FeedS16>, g, dim3(256), 0, s, b->feed_x.p, b->feed_taps.p, T, D,
-                           j.feed_p0, n, ns, CP, reinterpret_cast<const int2*>(tab), static_cast<int16_t*>(j.d_feed),
-                           j.feed_stride);
+                           j.feed_p0, n, ns, CP, reinterpret_cast<const int2*>(tab), static_cast<int16_t*>(f.p),
+                           f.stride);
       else
         hipLaunchKernelGGL(fmd::k_feed_out_sel<fmd::FeedF32>, g, dim3(256), 0, s, b->feed_x.p, b->feed_taps.p, T, D,
-                           j.feed_p0, n, ns, CP, reinterpret_cast<const int2*>(tab), static_cast<float*>(j.d_feed),
-                           j.feed_stride);
+                           j.feed_p0, n, ns, CP, reinterpret_cast<const int2*>(tab), static_cast<float*>(f.p),
+                           f.stride);
       sel_read_done(b, b->sel_feed, s);
     }
   }
-  else if (j.feed_deliver && n)
+  else if (f.deliver && n)
   {
     const dim3 g(CP / 64, tiles);
-    if (j.feed_fmt == FMD_FEED_S16)
+    if (f.fmt == FMD_FEED_S16)
       hipLaunchKernelGGL(fmd::k_feed_out<fmd::FeedS16>, g, dim3(256), 0, s, b->feed_x.p, b->feed_taps.p, T, D,
-                         j.feed_p0, n, C, CP, static_cast<int16_t*>(j.d_feed), j.feed_stride);
+                         j.feed_p0, n, C, CP, static_cast<int16_t*>(f.p), f.stride);
     else
       hipLaunchKernelGGL(fmd::k_feed_out<fmd::FeedF32>, g, dim3(256), 0, s, b->feed_x.p, b->feed_taps.p, T, D,
-                         j.feed_p0, n, C, CP, static_cast<float*>(j.d_feed), j.feed_stride);
+                         j.feed_p0, n, C, CP, static_cast<float*>(f.p), f.stride);
   }
   if (!b->dbg_feed_skip_roll)
     hipLaunchKernelGGL(fmd::k_roll<float>, dim3((CP + 255) / 256, std::max(1u, std::min(T - 1, 64u))), dim3(256), 0, s,
@@ -303,39 +305,39 @@ void launch_light_audio(fmd_batch* b, const fmd_batch::LightJob& j, hipStream_t 
   // k_feed_out and roll in stream order -- in every layout and concurrency mode the audio halves of a batch's calls
   // share one stream (the caller's, s_post, s_rds or s_lpf) until a setup call that drains the device moves them; a
   // stream that differs from the last feed call's all the same waits for the event behind that call's roll.
-  float* const feed_rows = j.feed ? b->feed_x.p + size_t(b->feed_T - 1) * CP : nullptr;
-  if (j.feed && b->feed_used && b->feed_stream != s && hipStreamWaitEvent(s, b->feed_done, 0) != hipSuccess)
+  float* const feed_rows = j.feed.p ? b->feed_x.p + size_t(b->feed_T - 1) * CP : nullptr;
+  if (j.feed.p && b->feed_used && b->feed_stream != s && hipStreamWaitEvent(s, b->feed_done, 0) != hipSuccess)
     mark_failed(b, "hipStreamWaitEvent failed in front of the feed form of the audio tail");
   if (j.asel && !rows)
     ; // (the batch has failed: its state is void, the tail is left out)
-  else if (j.feed && j.asel && j.pcm == FMD_PCM_S16)
+  else if (j.feed.p && j.asel && j.audio.fmt == FMD_PCM_S16)
     launch(fmd::k_audio_tail_s16_sel_feed, dim3(CP / 64), dim3(64, 1), 0, s, j.tl0, j.tl1, b->alp[j.q].p, j.A, C, CP,
-           k, b->st, j.d_audio, j.audio_stride, unsigned(j.sq), j.call_index, b->pcm_clip.p, rows, feed_rows);
-  else if (j.feed && j.asel)
+           k, b->st, j.audio.p, j.audio.stride, unsigned(j.sq), j.call_index, b->pcm_clip.p, rows, feed_rows);
+  else if (j.feed.p && j.asel)
     launch(fmd::k_audio_tail_sel_feed, dim3(CP / 64), dim3(64, 1), 0, s, j.tl0, j.tl1, b->alp[j.q].p, j.A, C, CP, k,
-           b->st, j.d_audio, j.audio_stride, unsigned(j.sq), j.call_index, rows, feed_rows);
-  else if (j.feed && j.pcm == FMD_PCM_S16)
+           b->st, j.audio.p, j.audio.stride, unsigned(j.sq), j.call_index, rows, feed_rows);
+  else if (j.feed.p && j.audio.fmt == FMD_PCM_S16)
     launch(fmd::k_audio_tail_s16_feed, dim3(CP / 64), dim3(64, 1), 0, s, j.tl0, j.tl1, b->alp[j.q].p, j.A, C, CP, k,
-           b->st, j.d_audio, j.audio_stride, unsigned(j.sq), j.call_index, b->pcm_clip.p, feed_rows);
-  else if (j.feed)
+           b->st, j.audio.p, j.audio.stride, unsigned(j.sq), j.call_index, b->pcm_clip.p, feed_rows);
+  else if (j.feed.p)
     launch(fmd::k_audio_tail_feed, dim3(CP / 64), dim3(64, 1), 0, s, j.tl0, j.tl1, b->alp[j.q].p, j.A, C, CP, k,
-           b->st, j.d_audio, j.audio_stride, unsigned(j.sq), j.call_index, feed_rows);
-  else if (j.asel && j.pcm == FMD_PCM_S16)
+           b->st, j.audio.p, j.audio.stride, unsigned(j.sq), j.call_index, feed_rows);
+  else if (j.asel && j.audio.fmt == FMD_PCM_S16)
     launch(fmd::k_audio_tail_s16_sel, dim3(CP / 64), dim3(64, 1), 0, s, j.tl0, j.tl1, b->alp[j.q].p, j.A, C, CP, k,
-           b->st, j.d_audio, j.audio_stride, unsigned(j.sq), j.call_index, b->pcm_clip.p, rows);
+           b->st, j.audio.p, j.audio.stride, unsigned(j.sq), j.call_index, b->pcm_clip.p, rows);
   else if (j.asel)
     launch(fmd::k_audio_tail_sel, dim3(CP / 64), dim3(64, 1), 0, s, j.tl0, j.tl1, b->alp[j.q].p, j.A, C, CP, k, b->st,
-           j.d_audio, j.audio_stride, unsigned(j.sq), j.call_index, rows);
-  else if (j.pcm == FMD_PCM_S16)
+           j.audio.p, j.audio.stride, unsigned(j.sq), j.call_index, rows);
+  else if (j.audio.fmt == FMD_PCM_S16)
     launch(fmd::k_audio_tail_s16, dim3(CP / 64), dim3(64, 1), 0, s, j.tl0, j.tl1,
-           b->alp[j.q].p, j.A, C, CP, k, b->st, j.d_audio, j.audio_stride, unsigned(j.sq), j.call_index,
+           b->alp[j.q].p, j.A, C, CP, k, b->st, j.audio.p, j.audio.stride, unsigned(j.sq), j.call_index,
            b->pcm_clip.p);
   else
     launch(fmd::k_audio_tail, dim3(CP / 64), dim3(64, 1), 0, s, j.tl0, j.tl1, b->alp[j.q].p, j.A, C, CP,
-           k, b->st, j.d_audio, j.audio_stride, unsigned(j.sq), j.call_index);
+           k, b->st, j.audio.p, j.audio.stride, unsigned(j.sq), j.call_index);
   if (rows)
     sel_read_done(b, *j.asel, s);
-  if (j.feed)
+  if (j.feed.p)
     launch_feed(b, j, s);
   // the record's RDS state is the other half's (same stream: stream order)
   if (j.events && j.status_after_rds && hipStreamWaitEvent(s, b->cev[j.es][fmd_batch::EV_RDS], 0) != hipSuccess)
@@ -343,143 +345,6 @@ void launch_light_audio(fmd_batch* b, const fmd_batch::LightJob& j, hipStream_t 
   hipLaunchKernelGGL(fmd::k_status_publish, dim3((C + 255) / 256), dim3(256), 0, s, b->st, C, j.call_index);
   if (j.events && hipEventRecord(b->cev[j.es][fmd_batch::EV_AUD], s) != hipSuccess)
     mark_failed(b, "hipEventRecord failed behind the audio tail of a call");
-}
-
-enum IqFormat
-{
-  IQ_F32 = 0, // complex<float>, the ProcessStream argument (FmDecode.h:135)
-  IQ_U8 = 1,  // RTL-SDR byte pairs, converted like ReadAsyncCB (RTL_SDR_Source.cpp:207-211)
-  IQ_S8 = 2,  // signed 8-bit pairs, v * 2^-7 (fmd_s8_to_f32)
-  IQ_S16 = 3  // signed 16-bit pairs in host byte order, v * 2^-15 (fmd_s16_to_f32)
-};
-static_assert(IQ_F32 == FMD_IQ_F32 && IQ_U8 == FMD_IQ_U8 && IQ_S8 == FMD_IQ_S8 && IQ_S16 == FMD_IQ_S16,
-              "the plan's formats are the C ABI's");
-
-/* bytes per IQ sample */
-inline size_t iq_esz(IqFormat fmt)
-{
-  return fmt == IQ_F32 ? 8 : fmt == IQ_S16 ? 4 : 2;
-}
-
-/* the `format` argument of the _fmt entry points: 0..3, checked before anything else is touched */
-inline bool iq_format_ok(int format)
-{
-  return format >= FMD_IQ_F32 && format <= FMD_IQ_S16;
-}
-
-enum PcmFormat
-{
-  PCM_F32 = 0, // interleaved float L, R: what ProcessStream hands its caller (FmDecode.h:135)
-  PCM_S16 = 1  // interleaved int16 L, R in host byte order, fmd_f32_to_s16 of the float sample
-};
-static_assert(PCM_F32 == FMD_PCM_F32 && PCM_S16 == FMD_PCM_S16, "the plan's formats are the C ABI's");
-
-/* bytes per audio sample */
-inline size_t pcm_esz(PcmFormat fmt)
-{
-  return fmt == PCM_S16 ? 2 : 4;
-}
-
-/* the `pcm_format` argument of the _pcm entry points: 0..1, checked before anything else is touched */
-inline bool pcm_format_ok(int format)
-{
-  return format >= FMD_PCM_F32 && format <= FMD_PCM_S16;
-}
-
-enum MpxFormat
-{
-  MPX_F32 = 0, // the FM PLL's output as is (m_BufferBaseband, FmDecode.cpp:433)
-  MPX_S16 = 1  // int16 in host byte order, fmd_f32_to_mpx16 of the float sample
-};
-static_assert(MPX_F32 == FMD_MPX_F32 && MPX_S16 == FMD_MPX_S16, "the plan's formats are the C ABI's");
-
-/* bytes per multiplex sample */
-inline size_t mpx_esz(MpxFormat fmt)
-{
-  return fmt == MPX_S16 ? 2 : 4;
-}
-
-/* the `mpx_format` argument of the _mpx entry points: 0..1, checked before anything else is touched */
-inline bool mpx_format_ok(int format)
-{
-  return format >= FMD_MPX_F32 && format <= FMD_MPX_S16;
-}
-
-/* Where a call delivers its multiplex (the _mpx entry points); d == null: nowhere, the call launches what a call
- * without the argument launches. */
-struct MpxJob
-{
-  void* d = nullptr;      // rows of the format, channel c at d + c * stride elements; 16-byte aligned
-  MpxFormat fmt = MPX_F32;
-  size_t stride = 0;      // elements; a multiple of 4 (F32) / 8 (S16), >= the call's baseband length
-  unsigned* out = nullptr; // (host, optional) samples per row: the call's baseband length
-};
-
-enum FeedFormat
-{
-  FEED_F32 = 0, // the decimating filter's float sum as is
-  FEED_S16 = 1  // int16 in host byte order, fmd_f32_to_s16 of it
-};
-static_assert(FEED_F32 == FMD_FEED_F32 && FEED_S16 == FMD_FEED_S16, "the plan's formats are the C ABI's");
-
-/* bytes per feed sample */
-inline size_t feed_esz(FeedFormat fmt)
-{
-  return fmt == FEED_S16 ? 2 : 4;
-}
-
-/* the `feed_format` argument of the _feed entry points: 0..1, checked before anything else is touched */
-inline bool feed_format_ok(int format)
-{
-  return format >= FMD_FEED_F32 && format <= FMD_FEED_S16;
-}
-
-/* Where a call delivers its feed (the _feed entry points); d == null: nowhere -- the call launches what a call
- * without the argument launches, and the feed's frame count does not advance. */
-struct FeedJob
-{
-  void* d = nullptr;       // rows of the format, channel c at d + c * stride elements; 16-byte aligned
-  FeedFormat fmt = FEED_F32;
-  size_t stride = 0;       // elements; a multiple of 4 (F32) / 8 (S16), >= the call's sample count
-  unsigned* out = nullptr; // (host, optional) samples per row
-  bool deliver = true;     // false: a feed selection of no rows -- the scratch and the count advance, nothing is written
-};
-
-/* The feed samples of a call of A frames behind g0 frames: the outputs n with g0 <= n D < g0 + A; *p0 = the call's
- * first frame that has one. */
-inline unsigned feed_samples_of(uint64_t g0, unsigned A, unsigned D, unsigned* p0 = nullptr)
-{
-  const uint64_t first = (g0 + D - 1) / D;
-  if (p0)
-    *p0 = unsigned(first * D - g0);
-  return unsigned((g0 + A + D - 1) / D - first);
-}
-
-/* The baseband length M of the batch's next call of `samples` (DownConvert.cpp:112,123), 0 where the call would be
- * refused for its size: what an _mpx entry point holds the row stride against before anything is submitted. */
-inline unsigned next_baseband_length(const fmd_batch* b, unsigned samples)
-{
-  const fmd_batch* x = b->subs.empty() ? b : b->subs[0].get();
-  const unsigned D = x->des.D;
-  return x->if_pos < samples ? (samples - x->if_pos + D - 1) / D : 0;
-}
-
-/* The audio frames A of the batch's next call of `samples` (the resampler walk of process_device_impl,
- * DownConvert.cpp:203-232), 0 where the call would be refused for its size: with it an entry point knows the call's
- * feed samples before anything is submitted. */
-inline unsigned next_audio_frames(const fmd_batch* b, unsigned samples)
-{
-  const fmd_batch* x = b->subs.empty() ? b : b->subs[0].get();
-  const unsigned M = next_baseband_length(b, samples);
-  const float p = x->rs_pos, pstep = x->des.rs_step;
-  unsigned A = 0;
-  float pf = p;
-  while (unsigned(int(pf)) < M)
-  {
-    A++;
-    pf = p + float(A) * pstep;
-  }
-  return A;
 }
 
 /* launch_if_stage<IN> of the call's format */
@@ -500,109 +365,56 @@ inline int launch_if_stage_fmt(IqFormat fmt, fmd_batch* b, const void* d_iq, siz
   }
 }
 
-int process_device_impl(fmd_batch* b, const void* d_iq, IqFormat fmt, size_t iq_channel_stride,
-                        unsigned samples, void* d_audio, PcmFormat pcm, size_t audio_channel_stride,
-                        unsigned* out_floats, void* stream_, const MpxJob& mpx = MpxJob(),
-                        const FeedJob& feed = FeedJob())
+/* Everything that refuses a call, looked at before anything of it is submitted: a refused call leaves the batch as
+ * it was, its pending channel edits included.  pl: the call's plan, from the positions of the batch (a shell: of its
+ * first sub-batch -- they all have the same geometry and the same positions). */
+int check_call(fmd_batch* b, const Call& c, fmd::CallPlan& pl)
 {
-  if (!b || !d_iq || (!d_audio && audio_rows_due(b)))
+  if (!b || !c.iq || (!c.audio.p && audio_rows_due(b)))
     return fail(FMD_ERR_ARG, "fmd_batch_process_device: null argument");
-  if (samples > FMD_MAX_BLOCK || samples < b->min_samples)
+  if (c.samples > FMD_MAX_BLOCK || c.samples < b->min_samples)
     return fail(FMD_ERR_SIZE, "samples must be within [fmd_batch_min_samples(), the largest block] = [" +
                                   std::to_string(b->min_samples) + ", 65536]");
   // a lane loads two IQ samples at a time: every channel's stream has to start on a pair boundary
   {
-    const size_t pair = 2 * iq_esz(fmt);
-    if ((reinterpret_cast<uintptr_t>(d_iq) % pair) || ((iq_channel_stride * (pair / 2)) % pair))
+    const size_t pair = 2 * format_esz(FMT_IQ, c.iq_fmt);
+    if ((reinterpret_cast<uintptr_t>(c.iq) % pair) || ((c.iq_stride * (pair / 2)) % pair))
       return fail(FMD_ERR_ARG, "IQ pointer and channel stride must be multiples of two IQ samples");
   }
-  const fmd::Design& d = b->des;
-  const unsigned C = b->C, CP = b->CP, N = samples, D = d.D;
-  hipStream_t stream = static_cast<hipStream_t>(stream_);
   HIPCHK(hipSetDevice(b->device));
   if (int rc = check_device_errors(b)) // a failed batch takes no more calls (fmd_batch_reset clears it)
     return rc;
-
   /* ---- position plan (batch-uniform, mirrors the reference's bookkeeping) ---- */
-  const unsigned pos = b->if_pos;
-  const unsigned M = pos < N ? (N - pos + D - 1) / D : 0; // DownConvert.cpp:112,123
-  if (M == 0)
-    return fail(FMD_ERR_SIZE, "block shorter than the decimator phase");
-  // the reference's half-band delay lines hold 32768 samples (DownConvert.cpp:267,500); longer
-  // baseband blocks overrun its heap, so they are outside the contract here too
-  if ((N + D - 1) / D + 51 > 32768)
-    return fail(FMD_ERR_SIZE, "baseband block longer than the reference's half-band buffers (32768)");
-  // Per stage of the half-band chain: how many inputs it sees and which of the reference's regimes
-  // that is (see k_hb_pass / k_roll_hb_mixed): HB_PASS below L inputs, HB_MIXED below 2 (L - 1).
-  enum HbMode { HB_NORMAL, HB_MIXED, HB_PASS };
-  std::vector<unsigned> hb_in(d.hb.size());
-  std::vector<HbMode> hb_mode(d.hb.size(), HB_NORMAL);
-  unsigned R = M;
-  for (size_t s = 0; s < d.hb.size(); s++)
-  {
-    hb_in[s] = R;
-    const unsigned L = unsigned(d.hb[s].len);
-    if (d.hb[s].cic)
-    { // CCicN3DecimateBy2: "InLength must be an even number" (DownConvert.cpp:701) -- with an odd one the class
-      // reads one sample past its block (whatever the buffer holds): outside the contract here
-      if (R % 2u || R < 2u)
-        return fail(FMD_ERR_SIZE, "at this baseband rate the RDS decimator starts with CIC stages: the baseband length "
-                                  "of a call must be a multiple of 2 per CIC stage (the reference reads past an odd block)");
-      R = R / 2; // :726
-    }
-    else if (L == 11)
-    { // the unrolled class reads InLength - 10 .. and its first nine outputs unconditionally (:596-661)
-      if (R < 20)
-        return fail(FMD_ERR_SIZE, "block too short for the 11-tap half-band stage");
-      R = R / 2; // :688
-    }
-    else if (R < L)
-    {
-      hb_mode[s] = HB_PASS;
-      R = R / 2; // :519-520
-    }
-    else
-    { // one output per even input index (:526-543)
-      hb_mode[s] = R >= 2u * (L - 1u) ? HB_NORMAL : HB_MIXED;
-      R = (R + 1) / 2;
-    }
-  }
-  if (R == 0)
-    return fail(FMD_ERR_SIZE, "block too short: no sample reaches the RDS rate");
-  // fractional resampler walk (DownConvert.cpp:203-232), float arithmetic as written there
-  const float p = b->rs_pos;
-  const float pstep = d.rs_step;
-  unsigned A = 0;
-  float pf = p;
-  unsigned pi = unsigned(int(pf));
-  while (pi < M)
-  {
-    A++;
-    pf = p + float(A) * pstep;
-    pi = unsigned(int(pf));
-  }
-  float new_rs_pos = pf - float(M);
-  if (new_rs_pos < 0)
-    new_rs_pos = 0;
-  if (A > b->Amax || M > b->Mmax)
+  const fmd_batch* x = b->subs.empty() ? b : b->subs[0].get();
+  if (fmd::plan_call(x->des, x->if_pos, x->rs_pos, x->feed_g, b->feed_div, c.samples, pl) != FMD_OK)
+    return fail(FMD_ERR_SIZE, pl.why);
+  if (pl.A > b->Amax || pl.M > b->Mmax)
     return fail(FMD_ERR_STATE, "internal: plan exceeds buffer geometry");
-  if (A == 0)
-    return fail(FMD_ERR_SIZE, "block too short: no audio frame falls into it");
   // (the stride lies between rows: one row per channel, or the rows of the selection)
-  if (size_t(2) * A > audio_channel_stride && (b->sel_audio.on ? b->sel_audio.n_total : C) > 1)
+  if (size_t(2) * pl.A > c.audio.stride && (b->sel_audio.on ? b->sel_audio.n_total : b->C) > 1)
     return fail(FMD_ERR_ARG, "audio_channel_stride smaller than the audio produced");
-  if (mpx.d && mpx.stride < M)
+  if (c.mpx.p && c.mpx.stride < pl.M)
     return fail(FMD_ERR_ARG, "mpx_channel_stride smaller than the call's baseband length");
-  // the feed of the call: its first output and its sample count, from the frames of the feed calls so far
-  unsigned feed_p0 = 0, feed_n = 0;
-  if (feed.d)
-  {
-    if (!b->feed_div)
-      return fail(FMD_ERR_STATE, "the feed is off (fmd_batch_set_feed)");
-    feed_n = feed_samples_of(b->feed_g, A, b->feed_div, &feed_p0);
-    if (feed.stride < feed_n)
-      return fail(FMD_ERR_ARG, "feed_channel_stride smaller than the call's feed samples");
-  }
+  if (c.feed.p && !b->feed_div)
+    return fail(FMD_ERR_STATE, "the feed is off (fmd_batch_set_feed)");
+  if (c.feed.p && c.feed.stride < pl.feed_n)
+    return fail(FMD_ERR_ARG, "feed_channel_stride smaller than the call's feed samples");
+  return FMD_OK;
+}
+
+int process_device_impl(fmd_batch* b, const Call& c)
+{
+  fmd::CallPlan pl;
+  if (int rc = check_call(b, c, pl))
+    return rc;
+  const fmd::Design& d = b->des;
+  const unsigned C = b->C, CP = b->CP, N = c.samples;
+  hipStream_t stream = static_cast<hipStream_t>(c.stream);
+  const Out& mpx = c.mpx;
+  const unsigned pos = b->if_pos, M = pl.M, R = pl.R, A = pl.A;
+  const unsigned* const hb_in = pl.hb_in;
+  const fmd::HbMode* const hb_mode = pl.hb_mode;
+  const float p = b->rs_pos, pstep = d.rs_step; // (the resampler's plan kernels walk the same positions)
 
   const unsigned T_lpf = unsigned(d.rds_lpf_taps.size());
   const unsigned T_mf = unsigned(d.rds_mf_taps.size());
@@ -672,7 +484,7 @@ int process_device_impl(fmd_batch* b, const void* d_iq, IqFormat fmt, size_t iq_
   /* ---- which form the RDS decimator takes: decided here, the serial stage's form follows from it ---- */
   bool hb_all_normal = d.hb.size() <= 3;
   for (size_t s = 0; s < d.hb.size(); s++)
-    hb_all_normal = hb_all_normal && hb_mode[s] == HB_NORMAL && d.hb[s].len != 11 && !d.hb[s].cic;
+    hb_all_normal = hb_all_normal && hb_mode[s] == fmd::HB_NORMAL && d.hb[s].len != 11 && !d.hb[s].cic;
   /* Large batches in the usual geometries: the three half-band stages as one stream, intermediate rows in
    * LDS (k_halfband_chain).  Everything else -- short calls with a stage outside its normal regime, the
    * 11-tap class, chains of another length, small batches -- keeps one launch per stage. */
@@ -781,7 +593,7 @@ int process_device_impl(fmd_batch* b, const void* d_iq, IqFormat fmt, size_t iq_
     if (!(stage_mask & 1u))
       markfn(1); // (energy experiment: this call leaves the IF stage out -- see "stage_mask")
     else
-      rc = launch_if_stage_fmt(fmt, b, d_iq, iq_channel_stride, N, pos, M, q, sF, markfn,
+      rc = launch_if_stage_fmt(IqFormat(c.iq_fmt), b, c.iq, c.iq_stride, N, pos, M, q, sF, markfn,
                                evset ? evset[0].e : nullptr, evset ? evset[1].e : nullptr);
     if (rc != FMD_OK) // cannot happen: the geometry was checked when the batch was created
     {
@@ -950,14 +762,14 @@ int process_device_impl(fmd_batch* b, const void* d_iq, IqFormat fmt, size_t iq_
       for (size_t s = 0; s < d.hb.size(); s++)
       {
         const unsigned n_out =
-            (d.hb[s].cic || d.hb[s].len == 11 || hb_mode[s] == HB_PASS) ? hb_in[s] / 2 : (hb_in[s] + 1) / 2;
+            (d.hb[s].cic || d.hb[s].len == 11 || hb_mode[s] == fmd::HB_PASS) ? hb_in[s] / 2 : (hb_in[s] + 1) / 2;
         const bool last = (s + 1 == d.hb.size());
         float2* outp = last ? b->rdsraw[q].p : b->hbbuf[s].p;
         const unsigned Hout = last ? (T_lpf - 1) : unsigned(d.hb[s + 1].len - 1);
         const int hb4 = b->dbg_hb4;
         const unsigned Hs = unsigned(d.hb[s].len - 1);
         float2* const hist_dst = s == 0 ? b->mix[q ^ 1].p : b->hbbuf[s - 1].p; // where the delay line lives
-        if (hb_mode[s] == HB_PASS)
+        if (hb_mode[s] == fmd::HB_PASS)
         { // unfiltered; the delay line stays (stage 0 keeps it in the other parity's buffer: copy it over)
           hipLaunchKernelGGL(fmd::k_hb_pass, rgrid(n_out), rt, 0, sR, in, Hs, outp, Hout, n_out, CP);
           if (s == 0)
@@ -978,7 +790,7 @@ int process_device_impl(fmd_batch* b, const void* d_iq, IqFormat fmt, size_t iq_
         hipLaunchKernelGGL(fmd::k_halfband, dim3(CP / 64, (n_out + 4 * fmd::HB_R - 1) / (4 * fmd::HB_R)),
                            dim3(64, 4), 0, sR, in, outp, n_out, d.hb[s].len, b->hbcoef[s], C, CP, Hout);
         // keep the last L-1 input rows of this stage for the next call, then its input is free
-        if (hb_mode[s] == HB_MIXED)
+        if (hb_mode[s] == fmd::HB_MIXED)
           hipLaunchKernelGGL(fmd::k_roll_hb_mixed, dim3((CP + 255) / 256), rt, 0, sR, in, (const float2*)outp,
                              hist_dst, Hs, hb_in[s], n_out, Hout, CP);
         else if (s == 0)
@@ -1078,40 +890,37 @@ int process_device_impl(fmd_batch* b, const void* d_iq, IqFormat fmt, size_t iq_
      * that reads the same rows.  In front of EV_HEAVY on every path: the next writer of these rows, the serial stage
      * of the next-but-one call, runs behind that call's IF FIR, which waits for this EV_HEAVY; EV_ROLL behind it is
      * what fmd_batch_wait and the caller's stream wait for. */
-    if (mpx.d && b->sel_mpx.on)
+    const float* mpx_rows = reinterpret_cast<const float*>(b->brp(q) + size_t(Hbb) * CP);
+    // (fmd_batch_debug_mpx_ms: the kernel's own start and stop, events of the call's slot)
+    const hipEvent_t mt0 = b->dbg_mpx_timing ? b->mpx_ev[es][0].e : nullptr;
+    const hipEvent_t mt1 = b->dbg_mpx_timing ? b->mpx_ev[es][1].e : nullptr;
+    if (mpx.p && b->sel_mpx.on)
     { // the selected writer (fmd_batch_select_mpx): tiles of 64 entries of this batch's part of the list
       const unsigned n = unsigned(b->sel_mpx.ent.size());
       const int* tab = n ? sel_table(b, b->sel_mpx, true, sA) : nullptr;
       if (tab)
       {
         const dim3 g((n + 63) / 64, (M + fmd::MPX_T - 1) / fmd::MPX_T);
-        const float* rows = reinterpret_cast<const float*>(b->brp(q) + size_t(Hbb) * CP);
-        const hipEvent_t t0 = b->dbg_mpx_timing ? b->mpx_ev[es][0].e : nullptr;
-        const hipEvent_t t1 = b->dbg_mpx_timing ? b->mpx_ev[es][1].e : nullptr;
-        b->mpx_ev_used[es] = t0 != nullptr;
-        if (mpx.fmt == MPX_S16)
-          launch(fmd::k_mpx_out_sel<fmd::MpxS16>, g, dim3(256), 0, sA, t0, t1, rows, M, n, CP,
-                 reinterpret_cast<const int2*>(tab), static_cast<int16_t*>(mpx.d), mpx.stride);
+        b->mpx_ev_used[es] = mt0 != nullptr;
+        if (mpx.fmt == FMD_MPX_S16)
+          launch(fmd::k_mpx_out_sel<fmd::MpxS16>, g, dim3(256), 0, sA, mt0, mt1, mpx_rows, M, n, CP,
+                 reinterpret_cast<const int2*>(tab), static_cast<int16_t*>(mpx.p), mpx.stride);
         else
-          launch(fmd::k_mpx_out_sel<fmd::MpxF32>, g, dim3(256), 0, sA, t0, t1, rows, M, n, CP,
-                 reinterpret_cast<const int2*>(tab), static_cast<float*>(mpx.d), mpx.stride);
+          launch(fmd::k_mpx_out_sel<fmd::MpxF32>, g, dim3(256), 0, sA, mt0, mt1, mpx_rows, M, n, CP,
+                 reinterpret_cast<const int2*>(tab), static_cast<float*>(mpx.p), mpx.stride);
         sel_read_done(b, b->sel_mpx, sA);
       }
     }
-    else if (mpx.d)
+    else if (mpx.p)
     {
       const dim3 g(CP / 64, (M + fmd::MPX_T - 1) / fmd::MPX_T);
-      const float* rows = reinterpret_cast<const float*>(b->brp(q) + size_t(Hbb) * CP);
-      // (fmd_batch_debug_mpx_ms: the kernel's own start and stop, events of the call's slot)
-      const hipEvent_t t0 = b->dbg_mpx_timing ? b->mpx_ev[es][0].e : nullptr;
-      const hipEvent_t t1 = b->dbg_mpx_timing ? b->mpx_ev[es][1].e : nullptr;
-      b->mpx_ev_used[es] = t0 != nullptr;
-      if (mpx.fmt == MPX_S16)
-        launch(fmd::k_mpx_out<fmd::MpxS16>, g, dim3(256), 0, sA, t0, t1, rows, M, C, CP,
-               static_cast<int16_t*>(mpx.d), mpx.stride);
+      b->mpx_ev_used[es] = mt0 != nullptr;
+      if (mpx.fmt == FMD_MPX_S16)
+        launch(fmd::k_mpx_out<fmd::MpxS16>, g, dim3(256), 0, sA, mt0, mt1, mpx_rows, M, C, CP,
+               static_cast<int16_t*>(mpx.p), mpx.stride);
       else
-        launch(fmd::k_mpx_out<fmd::MpxF32>, g, dim3(256), 0, sA, t0, t1, rows, M, C, CP,
-               static_cast<float*>(mpx.d), mpx.stride);
+        launch(fmd::k_mpx_out<fmd::MpxF32>, g, dim3(256), 0, sA, mt0, mt1, mpx_rows, M, C, CP,
+               static_cast<float*>(mpx.p), mpx.stride);
     }
     roll_later(b->brp(q), b->brp(q ^ 1), Hbb, M); // with the low-pass's own roll, at the chain's end
     mark(6);
@@ -1145,17 +954,11 @@ int process_device_impl(fmd_batch* b, const void* d_iq, IqFormat fmt, size_t iq_
   job.sq = sq;
   job.call_index = ci;
   job.rb_mode = b->rb_mode;
-  job.d_audio = d_audio;
-  job.pcm = pcm;
-  job.audio_stride = audio_channel_stride;
+  job.audio = c.audio;
   job.asel = b->sel_audio.on ? &b->sel_audio : nullptr;
-  job.feed = feed.d != nullptr;
-  job.feed_deliver = feed.deliver;
-  job.d_feed = feed.d;
-  job.feed_fmt = feed.fmt;
-  job.feed_stride = feed.stride;
-  job.feed_p0 = feed_p0;
-  job.feed_n = feed_n;
+  job.feed = c.feed;
+  job.feed_p0 = pl.feed_p0;
+  job.feed_n = pl.feed_n;
   if (serial_mode || b->split_post)
   { // stage order of the reference (what the per-stage profile is keyed to), or two streams
     rds_heavy();
@@ -1265,9 +1068,9 @@ int process_device_impl(fmd_batch* b, const void* d_iq, IqFormat fmt, size_t iq_
     b->prof_calls++;
 
   /* ---- advance the host-tracked positions ---- */
-  b->if_pos = pos + M * D - N;                      // DownConvert.cpp:132
+  b->if_pos = pl.if_pos;                            // DownConvert.cpp:132
   b->lut_idx = (b->lut_idx + N) % d.table_size;     // FmDecode.cpp:81
-  b->rs_pos = new_rs_pos;                           // DownConvert.cpp:230-232
+  b->rs_pos = pl.rs_pos;                            // DownConvert.cpp:230-232
   b->osc_re = osc_re;                               // DownConvert.cpp:440-441 (batch-wide, see osc_on)
   b->osc_im = osc_im;
   b->osc_warm -= std::min(b->osc_warm, M);
@@ -1278,14 +1081,14 @@ int process_device_impl(fmd_batch* b, const void* d_iq, IqFormat fmt, size_t iq_
   b->lastM = M;
   b->lastA = A;
   b->lastR = R;
-  if (out_floats)
-    *out_floats = 2 * A;
+  if (c.audio.out)
+    *c.audio.out = 2 * A;
   if (mpx.out)
-    *mpx.out = mpx.d ? M : 0;
-  if (feed.d)
+    *mpx.out = mpx.p ? M : 0;
+  if (c.feed.p)
     b->feed_g += A;
-  if (feed.out)
-    *feed.out = (feed.d && feed.deliver) ? feed_n : 0;
+  if (c.feed.out)
+    *c.feed.out = (c.feed.p && c.feed.deliver) ? pl.feed_n : 0;
   return FMD_OK;
 }
 

@@ -60,7 +60,7 @@ int scan_accumulate(fmd_scan* s, const void* d_iq, IqFormat fmt, size_t stride, 
 {
   if (!s || !d_iq)
     return fail(FMD_ERR_ARG, "fmd_scan_accumulate: null scan or IQ pointer");
-  const size_t pair = 2 * iq_esz(fmt);
+  const size_t pair = 2 * format_esz(FMT_IQ, fmt);
   if (reinterpret_cast<uintptr_t>(d_iq) % pair || (s->G > 1 && stride % 2))
     return fail(FMD_ERR_ARG, "fmd_scan_accumulate: IQ pointer and capture stride must be multiples of two IQ samples");
   if (s->G > 1 && stride < samples)
@@ -250,7 +250,7 @@ int fmd_scan_slots(const fmd_scan* s, int32_t* first_shift)
 int fmd_scan_accumulate_device_fmt(fmd_scan* s, const void* d_iq, int format, size_t iq_capture_stride,
                                    unsigned samples, void* stream)
 {
-  if (!iq_format_ok(format))
+  if (!format_ok(FMT_IQ, format))
     return fail(FMD_ERR_ARG, "fmd_scan_accumulate_device_fmt: format must be one of FMD_IQ_F32, _U8, _S8, _S16 (0..3)");
   return scan_accumulate(s, d_iq, IqFormat(format), iq_capture_stride, samples, stream);
 }
@@ -274,7 +274,7 @@ int fmd_scan_accumulate_host(fmd_scan* s, const float* iq, size_t iq_capture_str
 
 int fmd_scan_accumulate_host_fmt(fmd_scan* s, const void* iq, int format, size_t iq_capture_stride, unsigned samples)
 {
-  if (!iq_format_ok(format))
+  if (!format_ok(FMT_IQ, format))
     return fail(FMD_ERR_ARG, "fmd_scan_accumulate_host_fmt: format must be one of FMD_IQ_F32, _U8, _S8, _S16 (0..3)");
   const IqFormat fmt = IqFormat(format);
   if (!s || !iq)
@@ -287,7 +287,7 @@ int fmd_scan_accumulate_host_fmt(fmd_scan* s, const void* iq, int format, size_t
     return fail(FMD_ERR_SIZE, "fmd_scan_accumulate_host: fewer samples than one segment (nfft)");
   HIPCHK(hipSetDevice(s->device));
   const size_t stride = s->G > 1 ? iq_capture_stride : 0;
-  const size_t bytes = (size_t(s->G - 1) * stride + samples) * iq_esz(fmt);
+  const size_t bytes = (size_t(s->G - 1) * stride + samples) * format_esz(FMT_IQ, fmt);
   if (bytes > s->d_stage.n)
   {
     HIPCHK(hipStreamSynchronize(nullptr)); // the old buffer may still be read by work queued on this stream
