@@ -151,6 +151,26 @@ public:
     return n > 0 ? static_cast<unsigned int>(n) : 0u;
   }
 
+  /* Not in the reference: the station's complex baseband behind tuner and IF filter beside the audio (fmd.h,
+   * FMD_CIQ_*; m_BufferIF, the samples the FM PLL demodulates), at sample_rate_if / downsample.  Writes *ciq_samples
+   * complex samples into `ciq`, a caller buffer of `samples` elements at least.  The audio is ProcessStream's. */
+  unsigned int ProcessStreamWithChannelIq(const ComplexType* samples_in, unsigned int samples, float* audio,
+                                          ComplexType* ciq, unsigned int* ciq_samples)
+  {
+    fmd_call c{};
+    c.size = sizeof(fmd_call);
+    c.iq = samples_in;
+    c.iq_format = FMD_IQ_F32;
+    c.samples = samples;
+    c.audio.p = audio;
+    c.audio.format = FMD_PCM_F32;
+    c.ciq.p = ciq;
+    c.ciq.format = FMD_CIQ_F32;
+    c.ciq.count = ciq_samples;
+    const int n = fmd_process_stream_call(m_dec, &c);
+    return n > 0 ? static_cast<unsigned int>(n) : 0u;
+  }
+
   /* Not in the reference: what its block synchroniser computes and drops (fmd.h, "Every RDS block decision").
    * SetRdsBlocks: the observation of every ProcessStream from now on (FMD_RDS_BLOCKS_*); CollectRdsBlocks: the block
    * records queued so far, in order, into `out` (returns their number; *lost: records that did not fit);

@@ -141,6 +141,30 @@ extern "C" {
 #define FMD_FEED_F32 0
 #define FMD_FEED_S16 1
 
+/* The channel IQ beside the other outputs: the `ciq.format` of a call record (fmd_call).
+ * It is every channel's complex baseband behind the tuner and the decimating IF filter (cFineTuner::Process +
+ * cDownsampleFilter::Process, m_BufferIF) -- the samples the FM PLL demodulates: for a demodulator of the caller's
+ * own, the envelope |z| the PLL discards, a station's own power, an archive at 1 / downsample of the capture's rate,
+ * or the IF stage used as a bank of digital down-converters.  One row per channel, interleaved re, im, host byte order:
+ *   FMD_CIQ_F32  float   re, im   the sample as is: the bits FMD_TAP_DEMOD returns                8 bytes a sample
+ *   FMD_CIQ_S16  int16_t re, im   fmd_f32_to_mpx16 of each part: saturate_int16(round_half_even(x * 8192.0f)),
+ *                                 NaN gives 0 -- literally the multiplex's conversion                 4
+ * Length and rate: a call delivers M complex samples per row, M = the call's multiplex count, at most
+ * fmd_batch_max_mpx_samples(b, samples), at fmd_batch_mpx_rate(b) samples per second; sample k of a row is the sample
+ * whose PLL output is multiplex sample k.
+ * Scale: the tuner's factor 2 is in the samples (full-scale float input gives |z| up to 2); FMD_CIQ_S16's full scale
+ * is +-4.0.  There is no clip counter, as with the multiplex.
+ * Units: strides and counts of this output are COMPLEX SAMPLES.
+ * The format is a property of the call, and a call that asks for the rows leaves audio, multiplex, feed, status
+ * records, meters, RDS groups, block records and channel state with the bits of the same call without them.  The rows
+ * follow the slot: behind a reset, retune, capture switch, import or load they are those of the decoder the slot now
+ * is, and under FMD_FIR_*_PARITY_WAIVED and every kernel form of the IF stage they are what that stage wrote.
+ * A format outside 0..1 is refused with FMD_ERR_ARG before anything else is looked at.
+ * fmd_debug_math has no entry of its own for the conversion: what = 9 is fmd_f32_to_mpx16, the one function both
+ * writers call. */
+#define FMD_CIQ_F32 0
+#define FMD_CIQ_S16 1
+
 /* Constructor arguments of cFmDecoder (FmDecode.h:110-116).  table_size / if_filter_order are
  * the two internal constants BASELINE configs 3 and 5 override; 0 selects the reference
  * values 64 (FmDecode.cpp:249) and 8*downsample (FmDecode.cpp:262). */
@@ -432,6 +456,57 @@ int fmd_batch_get_mpx_selection(fmd_batch* b, unsigned* out, unsigned cap);
  * has its true history.  The same errors as above. */
 int fmd_batch_select_feed(fmd_batch* b, const unsigned* channels, unsigned n);
 int fmd_batch_get_feed_selection(fmd_batch* b, unsigned* out, unsigned cap);
+
+/* A process call as one record: the input, one fmd_rows per output, the stream.  It is what
+ * the positional entry points above build internally; the channel IQ (FMD_CIQ_*) is reachable only through it.
+ *   fmd_rows   p       the output's rows (device pointer in the device call, host pointer in the others); NULL: the
+ *                      output is not delivered, and the call is the call of the entry point without that argument
+ *              format  FMD_PCM_* (audio), FMD_MPX_* (mpx), FMD_FEED_* (feed), FMD_CIQ_* (ciq)
+ *              stride  elements of the format between the rows (ciq: complex samples)
+ *              count   (host, optional) elements per row the call wrote (ciq: complex samples)
+ *   fmd_call   size    sizeof(fmd_call): anything else is FMD_ERR_ARG (a record of another version of this header)
+ *              iq, iq_format, iq_channel_stride, samples: as in fmd_batch_process_device_pcm
+ *              stream  hipStream_t of the device call, NULL = default stream; ignored by the other two
+ * A record with ciq.p == NULL is fmd_batch_process_device_feed / _host_feed / fmd_process_stream_feed with the same
+ * arguments: the same refusals in the same order, the same bits, the same launches, events and allocations.
+ * fmd_process_stream_call returns the audio's length like fmd_process_stream_pcm and ignores strides and stream; any
+ * of its outputs may be asked for together.
+ *
+ * ciq: channel c's row starts ciq.stride complex samples behind channel c - 1's and takes *ciq.count = M samples.
+ * Device call: ciq.p must be 16-byte aligned and ciq.stride a multiple of 2 samples (FMD_CIQ_F32) or 4
+ * (FMD_CIQ_S16) and >= M (fmd_batch_max_mpx_samples(b, samples), rounded up, always is), else FMD_ERR_ARG and the
+ * batch is exactly as it was; a ciq.format outside 0..1 is refused before anything else is looked at.  Nothing is
+ * written at or behind sample M of a row and nothing for channels the batch does not have.  Host call and decoder:
+ * rows of any stride >= M and any alignment, through a device staging buffer sized on first use.  The rows are written
+ * by a copying kernel right behind the call's IF stage, on that stage's stream: like d_audio's rows they are complete
+ * when the call is, and the call's input buffer counts as free behind them (see fmd_batch_process_device_mpx for what that means with concurrency 2). */
+typedef struct fmd_rows
+{
+  void* p;
+  int format;
+  size_t stride;
+  unsigned* count;
+} fmd_rows;
+typedef struct fmd_call
+{
+  size_t size;
+  const void* iq;
+  int iq_format;
+  size_t iq_channel_stride;
+  unsigned samples;
+  fmd_rows audio, mpx, feed, ciq;
+  void* stream;
+} fmd_call;
+int fmd_batch_process_device_call(fmd_batch* b, const fmd_call* call);
+int fmd_batch_process_host_call(fmd_batch* b, const fmd_call* call);
+int fmd_process_stream_call(fmd_decoder* d, const fmd_call* call);
+/* Which channels deliver channel IQ rows (ciq), with fmd_batch_select_mpx's semantics word for word: applied in front
+ * of the next call submitted, nothing waits, calls in flight keep the selection they were submitted with; global
+ * channel numbers, also above 8192 channels; channels == NULL restores one row per channel; a list with n == 0 makes
+ * the call a call with ciq.p == NULL (*ciq.count = 0); no part of a state blob; FMD_ERR_STATE on the batch behind an
+ * fmd_decoder.  The same errors as above. */
+int fmd_batch_select_ciq(fmd_batch* b, const unsigned* channels, unsigned n);
+int fmd_batch_get_ciq_selection(fmd_batch* b, unsigned* out, unsigned cap);
 
 /* out[i] = the number of audio samples of channel first_channel + i (L and R counted separately) that FMD_PCM_S16
  * calls have saturated since the batch was created: samples whose rounded value lay outside [-32768, 32767] and was

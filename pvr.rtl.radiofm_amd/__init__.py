@@ -32,6 +32,9 @@ MPX_BYTES = {FMD_MPX_F32: 4, FMD_MPX_S16: 2}  # per multiplex sample
 # mono feed formats (include/fmd.h FMD_FEED_*): the `feed_format` argument of the _feed entry points
 FMD_FEED_F32, FMD_FEED_S16 = 0, 1
 FEED_BYTES = {FMD_FEED_F32: 4, FMD_FEED_S16: 2}  # per feed sample
+# channel IQ formats (include/fmd.h FMD_CIQ_*): the `ciq.format` of a call record
+FMD_CIQ_F32, FMD_CIQ_S16 = 0, 1
+CIQ_BYTES = {FMD_CIQ_F32: 8, FMD_CIQ_S16: 4}  # per complex sample
 
 TAPS = {"demod": 0, "baseband": 1, "pilot38": 2, "mono_rs": 3, "stereo_rs": 4, "rds_lpf": 5,
         "rds_pll": 6, "rds_mf": 7, "rds_sync": 8}
@@ -139,6 +142,33 @@ SCAN_CANDIDATE_DTYPE = np.dtype([("shift", "<i4"), ("offset_hz", "<f4"), ("power
 assert SCAN_CANDIDATE_DTYPE.itemsize == C.sizeof(FmdScanCandidate)
 
 
+class FmdRows(C.Structure):
+    """fmd_rows: one output of a call record; p None: not delivered."""
+    _fields_ = [("p", C.c_void_p), ("format", C.c_int), ("stride", C.c_size_t), ("count", C.POINTER(C.c_uint))]
+
+
+class FmdCall(C.Structure):
+    """fmd_call: a process call as one record (the _call entry points)."""
+    _fields_ = [("size", C.c_size_t), ("iq", C.c_void_p), ("iq_format", C.c_int), ("iq_channel_stride", C.c_size_t),
+                ("samples", C.c_uint), ("audio", FmdRows), ("mpx", FmdRows), ("feed", FmdRows), ("ciq", FmdRows),
+                ("stream", C.c_void_p)]
+
+
+def make_rows(p=None, fmt=0, stride=0, count=None):
+    """An FmdRows; count: a ctypes c_uint that takes the elements per row the call wrote."""
+    return FmdRows(p, int(fmt), int(stride), C.pointer(count) if count is not None else None)
+
+
+def make_call(iq, iq_format, iq_stride, samples, audio=None, mpx=None, feed=None, ciq=None, stream=None):
+    """An FmdCall with its size filled in; audio / mpx / feed / ciq: FmdRows or None."""
+    call = FmdCall(size=C.sizeof(FmdCall), iq=iq, iq_format=int(iq_format), iq_channel_stride=int(iq_stride),
+                   samples=int(samples), stream=stream)
+    for name, rows in (("audio", audio), ("mpx", mpx), ("feed", feed), ("ciq", ciq)):
+        if rows is not None:
+            setattr(call, name, rows)
+    return call
+
+
 STREAM_AUDIO, STREAM_RDS, STREAM_CHANGE, STREAM_TIME_BASE = 1, 2, -11, 1000000
 
 EXPORTS = [
@@ -180,6 +210,8 @@ EXPORTS = [
     "fmd_batch_get_feed_taps", "fmd_batch_process_device_feed", "fmd_batch_process_host_feed",
     "fmd_process_stream_feed", "fmd_batch_select_feed", "fmd_batch_get_feed_selection",
     "fmd_batch_debug_feed_skip_roll",
+    "fmd_batch_process_device_call", "fmd_batch_process_host_call", "fmd_process_stream_call",
+    "fmd_batch_select_ciq", "fmd_batch_get_ciq_selection",
     "fmd_batch_select_audio", "fmd_batch_select_mpx", "fmd_batch_get_audio_selection", "fmd_batch_get_mpx_selection",
     "fmd_batch_set_rds_blocks", "fmd_batch_get_rds_blocks", "fmd_batch_collect_rds_blocks",
     "fmd_batch_read_rds_quality",
@@ -346,6 +378,11 @@ def lib():
         L.fmd_batch_select_feed.argtypes = [vp, vp, u]
         L.fmd_batch_get_feed_selection.argtypes = [vp, vp, u]
         L.fmd_batch_debug_feed_skip_roll.argtypes = [vp, i]
+        L.fmd_batch_process_device_call.argtypes = [vp, C.POINTER(FmdCall)]
+        L.fmd_batch_process_host_call.argtypes = [vp, C.POINTER(FmdCall)]
+        L.fmd_process_stream_call.argtypes = [vp, C.POINTER(FmdCall)]
+        L.fmd_batch_select_ciq.argtypes = [vp, vp, u]
+        L.fmd_batch_get_ciq_selection.argtypes = [vp, vp, u]
         L.fmd_batch_get_audio_selection.argtypes = [vp, vp, u]
         L.fmd_batch_get_mpx_selection.argtypes = [vp, vp, u]
         L.fmd_batch_set_rds_blocks.argtypes = [vp, i, u]
@@ -417,6 +454,30 @@ def feed_format_of(feed):
             return fmt
     raise FmdError(FMD_ERR_ARG_TEXT % ("no feed format for %r (float32, int16, FMD_FEED_F32, FMD_FEED_S16)"
                                        % (feed,)))
+
+
+def ciq_format_of(ciq):
+    """FMD_CIQ_* of a `ciq=` argument: np.complex64, np.int16, or the constant itself.  Anything else raises: no
+    format is guessed."""
+    if isinstance(ciq, (int, np.integer)) and not isinstance(ciq, bool):
+        if int(ciq) in CIQ_BYTES:
+            return int(ciq)
+    elif ciq is not None:
+        try:
+            fmt = {np.dtype(np.complex64): FMD_CIQ_F32, np.dtype(np.int16): FMD_CIQ_S16}.get(np.dtype(ciq))
+        except TypeError:
+            fmt = None
+        if fmt is not None:
+            return fmt
+    raise FmdError(FMD_ERR_ARG_TEXT % ("no channel IQ format for %r (complex64, int16, FMD_CIQ_F32, FMD_CIQ_S16)"
+                                       % (ciq,)))
+
+
+def _ciq_rows(fmt, rows, stride):
+    """host rows for the channel IQ: complex64 [rows, stride], or int16 [rows, stride, 2] (re, im)"""
+    if fmt == FMD_CIQ_S16:
+        return np.zeros((rows, stride, 2), dtype=np.int16)
+    return np.zeros((rows, stride), dtype=np.complex64)
 
 
 def mpx_format_of(mpx):
@@ -681,7 +742,29 @@ class Batch:
         n = _check(lib().fmd_batch_get_mpx_selection(self._h, out.ctypes.data, out.size))
         return out[:n].copy()
 
-    def _rows(self, mpx=False, feed=False):
+    def select_ciq(self, channels):
+        """The same for the channel IQ rows (fmd_batch_select_ciq); an empty list: the call without them."""
+        if channels is None:
+            _check(lib().fmd_batch_select_ciq(self._h, None, 0))
+            return
+        ch = self._selection_list(channels, "select_ciq")
+        keep = ch if ch.size else np.zeros(1, dtype=np.uint32)
+        _check(lib().fmd_batch_select_ciq(self._h, keep.ctypes.data, ch.size))
+
+    def ciq_selection(self):
+        """uint32[n]: the channels of the channel IQ rows the next call writes (fmd_batch_get_ciq_selection)."""
+        out = np.zeros(self.n_channels, dtype=np.uint32)
+        n = _check(lib().fmd_batch_get_ciq_selection(self._h, out.ctypes.data, out.size))
+        return out[:n].copy()
+
+    def process_call(self, call):
+        """One device call from a call record (make_call; fmd_batch_process_device_call): the only way to the channel
+        IQ rows (call.ciq: FMD_CIQ_*, stride and count in complex samples)."""
+        _check(lib().fmd_batch_process_device_call(self._h, C.byref(call)))
+
+    def _rows(self, mpx=False, feed=False, ciq=False):
+        if ciq:
+            return _check(lib().fmd_batch_get_ciq_selection(self._h, None, 0))
         fn = (lib().fmd_batch_get_feed_selection if feed else
               lib().fmd_batch_get_mpx_selection if mpx else lib().fmd_batch_get_audio_selection)
         return _check(fn(self._h, None, 0))
@@ -739,7 +822,7 @@ class Batch:
                                                audio.ctypes.data, a_stride, C.byref(nf)))
         return audio[:, :nf.value]
 
-    def process_host_fmt(self, iq, shared=False, pcm=None, mpx=None, feed=None):
+    def process_host_fmt(self, iq, shared=False, pcm=None, mpx=None, feed=None, ciq=None):
         """iq: [C, N] complex64, or [C, 2N] float32 / uint8 / int8 / int16 holding I, Q, I, Q, ... (rows as for
         process_host; one row when shared); the input format is the array's dtype (fmd_batch_process_host_fmt).
         Signed integers are v * 2^-7 / v * 2^-15: the same bits as process_host on the converted block.
@@ -748,7 +831,11 @@ class Batch:
         mpx=np.float32 / np.int16: returns (audio, multiplex), the multiplex as [C, M] rows of that format
         (FMD_MPX_*, fmd_batch_process_host_mpx: a deviation of f Hz reads f / 30 000, times 8192 as int16).
         feed=np.int16 / np.float32: also returns the mono feed as [C, n] rows of that format, last of the tuple
-        (FMD_FEED_*, fmd_batch_process_host_feed; set_feed turns the feed on)."""
+        (FMD_FEED_*, fmd_batch_process_host_feed; set_feed turns the feed on).
+        ciq=np.complex64 / np.int16: also returns the channel IQ, last of the tuple, as complex64 [C, M] rows or int16
+        [C, M, 2] (re, im) rows (FMD_CIQ_*, through a call record: fmd_batch_process_host_call)."""
+        if ciq is not None:
+            return self._process_host_call(iq, shared, pcm, mpx, feed, ciq)
         iq, fmt, per = iq_format_of(iq)
         pcm_fmt = pcm_format_of(pcm)
         mpx_fmt = None if mpx is None else mpx_format_of(mpx)
@@ -797,17 +884,68 @@ class Batch:
                                                     pcm_fmt, a_stride, C.byref(nf)))
         return audio[:, :nf.value]
 
+    def _process_host_call(self, iq, shared, pcm, mpx, feed, ciq):
+        """process_host_fmt with the channel IQ: the same outputs through one call record."""
+        iq, fmt, per = iq_format_of(iq)
+        pcm_fmt, ciq_fmt = pcm_format_of(pcm), ciq_format_of(ciq)
+        if shared:
+            n, stride = iq.size // per, 0
+        else:
+            iq = iq.reshape(self._input_rows(), -1)
+            n = iq.shape[1] // per
+            stride = n
+        a_stride, m_stride = self.max_audio_floats(n), self.max_mpx_samples(n)
+        audio = np.zeros((self._rows(), a_stride), dtype=np.int16 if pcm_fmt == FMD_PCM_S16 else np.float32)
+        nf, nm, nfeed, nq = C.c_uint(), C.c_uint(), C.c_uint(), C.c_uint()
+        call = make_call(iq.ctypes.data, fmt, stride, n, audio=make_rows(audio.ctypes.data, pcm_fmt, a_stride, nf))
+        out = []
+        if mpx is not None:
+            mpx_fmt = mpx_format_of(mpx)
+            rows = np.zeros((self._rows(mpx=True), m_stride), dtype=np.int16 if mpx_fmt == FMD_MPX_S16 else np.float32)
+            call.mpx = make_rows(rows.ctypes.data, mpx_fmt, m_stride, nm)
+            out.append((rows, nm, None))
+        if feed is not None:
+            feed_fmt = feed_format_of(feed)
+            f_stride = max(self.max_feed_samples(n), 1)
+            frows = np.zeros((max(self._rows(feed=True), 1), f_stride),
+                             dtype=np.int16 if feed_fmt == FMD_FEED_S16 else np.float32)
+            call.feed = make_rows(frows.ctypes.data, feed_fmt, f_stride, nfeed)
+            out.append((frows, nfeed, self._rows(feed=True)))
+        qrows = _ciq_rows(ciq_fmt, max(self._rows(ciq=True), 1), m_stride)
+        call.ciq = make_rows(qrows.ctypes.data, ciq_fmt, m_stride, nq)
+        out.append((qrows, nq, self._rows(ciq=True)))
+        _check(lib().fmd_batch_process_host_call(self._h, C.byref(call)))
+        return (audio[:, :nf.value],) + tuple(r[:r.shape[0] if k is None else k, :c.value] for r, c, k in out)
+
     def process_device(self, d_iq_ptr, iq_stride, samples, d_audio_ptr, audio_stride, stream=None,
                        u8=False, fmt=None, pcm=None, d_mpx_ptr=None, mpx_stride=0, mpx=None, d_feed_ptr=None,
-                       feed_stride=0, feed=None):
+                       feed_stride=0, feed=None, d_ciq_ptr=None, ciq_stride=0, ciq=None):
         """iq_stride in IQ samples; u8=True: d_iq_ptr holds RTL-SDR byte pairs; fmt (FMD_IQ_*): the input format,
         through fmd_batch_process_device_fmt; pcm (np.int16 / FMD_PCM_*): the output format, audio_stride and the
         returned count in its elements, through fmd_batch_process_device_pcm.
         d_mpx_ptr / mpx_stride / mpx (np.float32, np.int16 / FMD_MPX_*): the call's multiplex rows, through
         fmd_batch_process_device_mpx; returns (audio samples, multiplex samples) per channel.
         d_feed_ptr / feed_stride / feed (np.int16, np.float32 / FMD_FEED_*): the call's feed rows, through
-        fmd_batch_process_device_feed; the feed samples per channel are the last of the returned tuple."""
+        fmd_batch_process_device_feed; the feed samples per channel are the last of the returned tuple.
+        d_ciq_ptr / ciq_stride / ciq (np.complex64, np.int16 / FMD_CIQ_*): the call's channel IQ rows, stride and
+        count in complex samples, through a call record (fmd_batch_process_device_call); their count is the last of
+        the returned tuple, behind the multiplex's and the feed's where those were asked for."""
         nf = C.c_uint()
+        if d_ciq_ptr is not None or ciq is not None:
+            in_fmt = int(fmt) if fmt is not None else FMD_IQ_U8 if u8 else FMD_IQ_F32
+            nm, nfeed, nq = C.c_uint(), C.c_uint(), C.c_uint()
+            want_mpx = d_mpx_ptr is not None or mpx is not None
+            want_feed = d_feed_ptr is not None or feed is not None
+            call = make_call(d_iq_ptr, in_fmt, iq_stride, samples, stream=stream,
+                             audio=make_rows(d_audio_ptr, pcm_format_of(pcm), audio_stride, nf),
+                             mpx=make_rows(d_mpx_ptr, mpx_format_of(FMD_MPX_F32 if mpx is None else mpx), mpx_stride, nm),
+                             feed=make_rows(d_feed_ptr, feed_format_of(FMD_FEED_S16 if feed is None else feed),
+                                            feed_stride, nfeed),
+                             ciq=make_rows(d_ciq_ptr, ciq_format_of(FMD_CIQ_F32 if ciq is None else ciq), ciq_stride,
+                                           nq))
+            self.process_call(call)
+            return ((nf.value,) + ((nm.value,) if want_mpx else ()) + ((nfeed.value,) if want_feed else ())
+                    + (nq.value,))
         if d_feed_ptr is not None or feed is not None:
             in_fmt = int(fmt) if fmt is not None else FMD_IQ_U8 if u8 else FMD_IQ_F32
             nm, nfeed = C.c_uint(), C.c_uint()
@@ -1113,6 +1251,21 @@ class FmDecoder:
         n = _check(lib().fmd_process_stream_feed(self._h, iq.ctypes.data, FMD_IQ_F32, iq.size, audio.ctypes.data,
                                                  FMD_PCM_F32, rows.ctypes.data, feed_fmt, C.byref(nfeed)))
         return audio[:n], rows[:nfeed.value]
+
+    def ProcessStreamWithChannelIq(self, samples_in, ciq=np.complex64):
+        """(ProcessStream's audio, the block's IF-filtered IQ as complex64 [M] or int16 [M, 2]): FMD_CIQ_*,
+        fmd_process_stream_call."""
+        iq = np.ascontiguousarray(samples_in)
+        if iq.dtype != np.complex64:
+            iq = iq.astype(np.float32).view(np.complex64)
+        ciq_fmt = ciq_format_of(ciq)
+        audio = np.empty(2 * iq.size, dtype=np.float32)
+        rows = _ciq_rows(ciq_fmt, 1, iq.size)[0]
+        nq = C.c_uint()
+        call = make_call(iq.ctypes.data, FMD_IQ_F32, 0, iq.size, audio=make_rows(audio.ctypes.data, FMD_PCM_F32),
+                         ciq=make_rows(rows.ctypes.data, ciq_fmt, 0, nq))
+        n = _check(lib().fmd_process_stream_call(self._h, C.byref(call)))
+        return audio[:n], rows[:nq.value]
 
     def ProcessStreamU8(self, buf):
         """ReadAsyncCB + ProcessStream (RTL_SDR_Source.cpp:196-213): buf = I,Q byte pairs."""

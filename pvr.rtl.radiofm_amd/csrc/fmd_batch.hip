@@ -153,20 +153,22 @@ enum IqFormat
 static_assert(IQ_F32 == FMD_IQ_F32 && IQ_U8 == FMD_IQ_U8 && IQ_S8 == FMD_IQ_S8 && IQ_S16 == FMD_IQ_S16,
               "the plan's formats are the C ABI's");
 
-/* The format arguments of the C ABI (FMD_IQ_*, FMD_PCM_*, FMD_MPX_*, FMD_FEED_*): the values each takes (0 .. last),
- * the bytes of an element -- an IQ sample, one audio, multiplex or feed sample -- and what a refusal says. */
-enum FormatKind { FMT_IQ, FMT_PCM, FMT_MPX, FMT_FEED };
+/* The format arguments of the C ABI (FMD_IQ_*, FMD_PCM_*, FMD_MPX_*, FMD_FEED_*, FMD_CIQ_*): the values each takes
+ * (0 .. last), the bytes of an element -- an IQ sample, one audio, multiplex or feed sample, a complex sample of the
+ * channel IQ -- and what a refusal says. */
+enum FormatKind { FMT_IQ, FMT_PCM, FMT_MPX, FMT_FEED, FMT_CIQ };
 struct FormatInfo
 {
   int last;
   unsigned char esz[4];
   const char* must;
 };
-const FormatInfo kFormats[4] = {
+const FormatInfo kFormats[5] = {
     {FMD_IQ_S16, {8, 2, 2, 4}, "iq_format must be one of FMD_IQ_F32, _U8, _S8, _S16 (0..3)"},
     {FMD_PCM_S16, {4, 2}, "pcm_format must be FMD_PCM_F32 or FMD_PCM_S16 (0..1)"},
     {FMD_MPX_S16, {4, 2}, "mpx_format must be FMD_MPX_F32 or FMD_MPX_S16 (0..1)"},
-    {FMD_FEED_S16, {4, 2}, "feed_format must be FMD_FEED_F32 or FMD_FEED_S16 (0..1)"}};
+    {FMD_FEED_S16, {4, 2}, "feed_format must be FMD_FEED_F32 or FMD_FEED_S16 (0..1)"},
+    {FMD_CIQ_S16, {8, 4}, "ciq.format must be FMD_CIQ_F32 or FMD_CIQ_S16 (0..1)"}};
 
 /* a format argument, checked before anything else is touched */
 inline bool format_ok(FormatKind k, int format)
@@ -180,13 +182,13 @@ inline size_t format_esz(FormatKind k, int format)
 }
 
 /* Where a call delivers one of its outputs -- the audio, the multiplex (the _mpx entry points), the feed (the _feed
- * entry points); p == null: nowhere -- the call launches what a call without the argument launches (and the feed's
+ * entry points), the channel IQ (the _call entry points; its elements are complex samples); p == null: nowhere -- the call launches what a call without the argument launches (and the feed's
  * frame count does not advance). */
 struct Out
 {
   FormatKind kind;
   void* p = nullptr;       // rows of the format, channel c at p + c * stride elements
-  int fmt = 0;             // FMD_PCM_* / FMD_MPX_* / FMD_FEED_*
+  int fmt = 0;             // FMD_PCM_* / FMD_MPX_* / FMD_FEED_* / FMD_CIQ_*
   size_t stride = 0;       // elements
   unsigned* out = nullptr; // (host, optional) elements per row the call wrote
   bool deliver = true;     // false: a feed selection of no rows -- the scratch and the count advance, nothing is written
@@ -204,14 +206,14 @@ struct Out
   }
 };
 
-/* One call of a batch: the input rows, the three outputs, the caller's stream. */
+/* One call of a batch: the input rows, the four outputs, the caller's stream. */
 struct Call
 {
   const void* iq = nullptr;
   int iq_fmt = FMD_IQ_F32; // FMD_IQ_*
   size_t iq_stride = 0;    // IQ samples between the input rows
   unsigned samples = 0;
-  Out audio{FMT_PCM}, mpx{FMT_MPX}, feed{FMT_FEED};
+  Out audio{FMT_PCM}, mpx{FMT_MPX}, feed{FMT_FEED}, ciq{FMT_CIQ};
   void* stream = nullptr;
 };
 
@@ -417,6 +419,10 @@ struct fmd_batch
   int dbg_feed_skip_roll = 0;     // fmd_batch_debug_feed_skip_roll (mutation test): the history rows stay stale
   Selection sel_feed;             // which channels deliver feed rows (fmd_batch_select_feed): the multiplex's form
   DevBuf<float> h_feed;           // staging of the host-buffer call's feed rows (sized on first use)
+  /* The channel IQ (the _call entry points): demod[q]'s rows as an output.  It has no state
+   * of its own -- a selection of the multiplex's form and the host call's staging. */
+  Selection sel_ciq;
+  DevBuf<float> h_ciq;
   bool decoder_owned = false;     // the one-channel batch behind an fmd_decoder: it takes no selection
 
   std::vector<std::unique_ptr<fmd::GroupDecoder>> gdec;
@@ -2000,6 +2006,7 @@ static int process_shell(fmd_batch* b, const Call& c)
     sc.audio.out = &nf;
     sc.mpx = c.mpx.from_channel(ch0, b->sel_mpx.on);
     sc.feed = c.feed.from_channel(ch0, b->sel_feed.on);
+    sc.ciq = c.ciq.from_channel(ch0, b->sel_ciq.on);
     const int rc = process_device_impl(sb, sc);
     if (rc != FMD_OK)
     { // the first sub-batch refuses what every one of them would refuse (same geometry, same positions): nothing
@@ -2043,13 +2050,17 @@ static Call make_call(const void* iq, int iq_format, size_t iq_stride, unsigned 
  * formats; then WAY_DEVICE: the pointers and strides the kernels store through, WAY_HOST: what the staged copy needs
  * (no alignment; a stride only between rows), WAY_FORMATS: nothing more (fmd_process_stream_*: the decoder comes
  * next).  Checks of an output apply only when its pointer is given and, for the multiplex, its selection is not
- * empty (a feed selection of no rows still counts the feed's frames).  Clears the out-counts a refused call would
+ * empty (the channel IQ: likewise; a feed selection of no rows still counts the feed's frames).  Clears the out-counts a refused call would
  * leave behind, drops the multiplex of a selection of no rows, and says whether the feed is delivered.  No HIP call
  * in here: the refusals hold without a device. */
 enum CallWay { WAY_DEVICE, WAY_HOST, WAY_FORMATS };
 static int check_call_args(const char* who, CallWay way, fmd_batch* b, Call& c)
 {
   auto refuse = [&](int code, const char* what) { return fail(code, std::string(who) + ": " + what); };
+  if (!format_ok(FMT_CIQ, c.ciq.fmt))
+    return refuse(FMD_ERR_ARG, kFormats[FMT_CIQ].must);
+  if (c.ciq.out)
+    *c.ciq.out = 0;
   if (!format_ok(FMT_FEED, c.feed.fmt))
     return refuse(FMD_ERR_ARG, kFormats[FMT_FEED].must);
   if (c.feed.out)
@@ -2083,7 +2094,10 @@ static int check_call_args(const char* who, CallWay way, fmd_batch* b, Call& c)
   if (c.mpx.out)
     *c.mpx.out = 0;
   c.feed.deliver = f_rows != 0;
-  if (!c.mpx.p && !c.feed.p)
+  const unsigned q_rows = b->sel_ciq.on ? b->sel_ciq.n_total : b->C;
+  if (q_rows == 0) // a selection of no rows: the call without the channel IQ
+    c.ciq.p = nullptr;
+  if (!c.mpx.p && !c.feed.p && !c.ciq.p)
     return FMD_OK;
   // the rows hold the call's samples -- looked at here, in front of the pending channel edits: a refused call leaves
   // the batch as it was (a call refused for its size has no samples: check_call has the sentence)
@@ -2099,6 +2113,12 @@ static int check_call_args(const char* who, CallWay way, fmd_batch* b, Call& c)
   if (c.feed.p && (dev || f_rows > 1) && c.feed.stride < pl.feed_n)
     return refuse(FMD_ERR_ARG, "feed_channel_stride smaller than the call's feed samples "
                                "(fmd_batch_max_feed_samples is the bound)");
+  if (c.ciq.p && dev && !c.ciq.rows_aligned())
+    return refuse(FMD_ERR_ARG, "the ciq pointer must be 16-byte aligned and ciq.stride a multiple of 2 (FMD_CIQ_F32) / "
+                               "4 (FMD_CIQ_S16) complex samples");
+  if (c.ciq.p && (dev || q_rows > 1) && c.ciq.stride < pl.M)
+    return refuse(FMD_ERR_ARG, "ciq.stride smaller than the call's baseband length (fmd_batch_max_mpx_samples is the "
+                               "bound)");
   return FMD_OK;
 }
 
@@ -2140,6 +2160,34 @@ int fmd_batch_process_device_feed(fmd_batch* b, const void* d_iq, int iq_format,
   c.mpx = Out{FMT_MPX, d_mpx, mpx_format, mpx_channel_stride, out_mpx_samples};
   c.feed = Out{FMT_FEED, d_feed, feed_format, feed_channel_stride, out_feed_samples};
   return process_device_checked("fmd_batch_process_device_feed", b, c);
+}
+
+/* The call record of the C ABI as the internal one (the _call entry points): null and size first. */
+static int call_of_record(const char* who, const fmd_call* r, Call& c)
+{
+  if (!r)
+    return fail(FMD_ERR_ARG, std::string(who) + ": null call record");
+  if (r->size != sizeof(fmd_call))
+    return fail(FMD_ERR_ARG, std::string(who) + ": call->size must be sizeof(fmd_call)");
+  auto rows = [](FormatKind k, const fmd_rows& o) { return Out{k, o.p, o.format, o.stride, o.count}; };
+  c.iq = r->iq;
+  c.iq_fmt = r->iq_format;
+  c.iq_stride = r->iq_channel_stride;
+  c.samples = r->samples;
+  c.audio = rows(FMT_PCM, r->audio);
+  c.mpx = rows(FMT_MPX, r->mpx);
+  c.feed = rows(FMT_FEED, r->feed);
+  c.ciq = rows(FMT_CIQ, r->ciq);
+  c.stream = r->stream;
+  return FMD_OK;
+}
+
+int fmd_batch_process_device_call(fmd_batch* b, const fmd_call* call)
+{
+  Call c;
+  if (int rc = call_of_record("fmd_batch_process_device_call", call, c))
+    return rc;
+  return process_device_checked("fmd_batch_process_device_call", b, c);
 }
 
 int fmd_batch_process_device_fmt(fmd_batch* b, const void* d_iq, int format, size_t iq_channel_stride,
@@ -2599,9 +2647,9 @@ static int select_rows(fmd_batch* b, int which, const unsigned* channels, unsign
   }
   else
     n = 0;
-  // which: 0 audio, 1 multiplex, 2 feed
+  // which: 0 audio, 1 multiplex, 2 feed, 3 channel IQ
   auto pick = [which](fmd_batch* y) -> fmd_batch::Selection& {
-    return which == 2 ? y->sel_feed : which == 1 ? y->sel_mpx : y->sel_audio;
+    return which == 3 ? y->sel_ciq : which == 2 ? y->sel_feed : which == 1 ? y->sel_mpx : y->sel_audio;
   };
   fmd_batch::Selection& top = pick(b);
   const std::vector<fmd_batch*> xs = buffer_batches(b);
@@ -2632,7 +2680,8 @@ static int get_selection(fmd_batch* b, int which, unsigned* out, unsigned cap, c
 {
   if (!b || (cap && !out))
     return fail(FMD_ERR_ARG, std::string(who) + ": null argument");
-  const fmd_batch::Selection& sel = which == 2 ? b->sel_feed : which == 1 ? b->sel_mpx : b->sel_audio;
+  const fmd_batch::Selection& sel =
+      which == 3 ? b->sel_ciq : which == 2 ? b->sel_feed : which == 1 ? b->sel_mpx : b->sel_audio;
   const unsigned n = sel.on ? sel.n_total : b->C;
   for (unsigned i = 0; i < std::min(cap, n); i++)
     out[i] = sel.on ? sel.list[i] : i;
@@ -2667,6 +2716,16 @@ int fmd_batch_select_feed(fmd_batch* b, const unsigned* channels, unsigned n)
 int fmd_batch_get_feed_selection(fmd_batch* b, unsigned* out, unsigned cap)
 {
   return get_selection(b, 2, out, cap, "fmd_batch_get_feed_selection");
+}
+
+int fmd_batch_select_ciq(fmd_batch* b, const unsigned* channels, unsigned n)
+{
+  return select_rows(b, 3, channels, n, "fmd_batch_select_ciq");
+}
+
+int fmd_batch_get_ciq_selection(fmd_batch* b, unsigned* out, unsigned cap)
+{
+  return get_selection(b, 3, out, cap, "fmd_batch_get_ciq_selection");
 }
 
 /* fmd_batch_set_feed: a setup call.  It waits for the calls in flight (the scratch they may still write is freed or
@@ -3002,11 +3061,11 @@ static int process_host_impl(fmd_batch* b, const Call& c)
 {
   HIPCHK(hipSetDevice(b->device));
   const unsigned C = b->C, samples = c.samples;
-  // the outputs' staging -- audio; multiplex and feed where the call has them (the feed's rows one element longer
-  // than fmd_batch_max_feed_samples)
+  // the outputs' staging -- audio; multiplex, feed and channel IQ where the call has them (the feed's rows one
+  // element longer than fmd_batch_max_feed_samples)
   Call d = c;
   d.stream = nullptr;
-  StagedOut sa, sm, sf;
+  StagedOut sa, sm, sf, sc;
   if (int rc = sa.stage(b->h_audio, c.audio, b->sel_audio, C, fmd_batch_max_audio_floats(b, samples)))
     return rc;
   d.audio = sa.dev;
@@ -3021,6 +3080,12 @@ static int process_host_impl(fmd_batch* b, const Call& c)
     if (int rc = sf.stage(b->h_feed, c.feed, b->sel_feed, C, size_t(fmd_batch_max_feed_samples(b, samples)) + 1))
       return rc;
     d.feed = sf.dev;
+  }
+  if (c.ciq.p)
+  {
+    if (int rc = sc.stage(b->h_ciq, c.ciq, b->sel_ciq, C, fmd_batch_max_mpx_samples(b, samples)))
+      return rc;
+    d.ciq = sc.dev;
   }
   const size_t esz = format_esz(FMT_IQ, c.iq_fmt); // bytes per IQ sample
   // device copy: one row per channel, rows padded to a whole pair of samples
@@ -3055,12 +3120,14 @@ static int process_host_impl(fmd_batch* b, const Call& c)
   rc = wait_impl(b, 0, nullptr, false); // the groups-lost flag is this call's to report, at its end
   if (rc < 0)
     return rc;
-  if ((rc = sa.fetch(c.audio)) || (rc = sm.fetch(c.mpx)) || (rc = sf.fetch(c.feed)))
+  if ((rc = sa.fetch(c.audio)) || (rc = sm.fetch(c.mpx)) || (rc = sf.fetch(c.feed)) || (rc = sc.fetch(c.ciq)))
     return rc;
   if (c.mpx.out)
     *c.mpx.out = sm.n;
   if (c.feed.out)
     *c.feed.out = sf.n;
+  if (c.ciq.out)
+    *c.ciq.out = sc.n;
   b->host_ms[2] += ms_since(tp);
   tp = clk::now();
   rc = fmd_batch_collect_rds(b, nullptr, 0, 1, nullptr);
@@ -3108,6 +3175,14 @@ int fmd_batch_process_host_feed(fmd_batch* b, const void* iq, int iq_format, siz
   c.mpx = Out{FMT_MPX, mpx, mpx_format, mpx_channel_stride, out_mpx_samples};
   c.feed = Out{FMT_FEED, feed, feed_format, feed_channel_stride, out_feed_samples};
   return process_host_checked("fmd_batch_process_host_feed", b, c);
+}
+
+int fmd_batch_process_host_call(fmd_batch* b, const fmd_call* call)
+{
+  Call c;
+  if (int rc = call_of_record("fmd_batch_process_host_call", call, c))
+    return rc;
+  return process_host_checked("fmd_batch_process_host_call", b, c);
 }
 
 int fmd_batch_process_host_fmt(fmd_batch* b, const void* iq, int format, size_t iq_channel_stride, unsigned samples,
@@ -3698,6 +3773,17 @@ int fmd_process_stream_feed(fmd_decoder* d, const void* iq, int iq_format, unsig
   Call c = make_call(iq, iq_format, 0, samples, audio, pcm_format, 0, nullptr);
   c.feed = Out{FMT_FEED, feed, feed_format, 0, feed_samples};
   return process_stream_checked("fmd_process_stream_feed", "fmd_batch_process_host_feed", d, c);
+}
+
+int fmd_process_stream_call(fmd_decoder* d, const fmd_call* call)
+{
+  Call c;
+  if (int rc = call_of_record("fmd_process_stream_call", call, c))
+    return rc;
+  // (host pointers of one channel: strides and stream are not looked at)
+  c.iq_stride = c.audio.stride = c.mpx.stride = c.feed.stride = c.ciq.stride = 0;
+  c.stream = nullptr;
+  return process_stream_checked("fmd_process_stream_call", "fmd_batch_process_host_call", d, c);
 }
 
 int fmd_process_stream_fmt(fmd_decoder* d, const void* iq, int format, unsigned samples, float* audio)

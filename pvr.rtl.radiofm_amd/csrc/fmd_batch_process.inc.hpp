@@ -347,6 +347,45 @@ void launch_light_audio(fmd_batch* b, const fmd_batch::LightJob& j, hipStream_t 
     mark_failed(b, "hipEventRecord failed behind the audio tail of a call");
 }
 
+/* The channel IQ of a call (the _call entry points): demod[q]'s rows, which the call's IF stage wrote, into the
+ * caller's rows (k_ciq_out, or the selected writer), on the IF stage's own stream s right behind that stage (and its
+ * level meter; EV_FIR is recorded in front: the serial stage does not wait for the writer and only reads the rows).
+ * Stream order is the whole ordering argument: the rows' writer is in front on s, and their next writer -- the IF
+ * stage of the next-but-one call -- is behind on s, in every stream layout, in serial mode (s is the caller's stream)
+ * and with sub-batches and the silent twin (buffers of their own on the same s).  The call's EV_INDONE is recorded
+ * behind the writer: fmd_batch_wait[_lagged] and the caller's stream wait for it with the audio and multiplex rows.
+ * Measured against the other obvious place, the heavy stream beside the multiplex writer in front of EV_HEAVY
+ * (DESIGN.md section 9.12): there a step took 0.06-0.08 ms longer.  A call without the rows launches nothing here. */
+void launch_ciq(fmd_batch* b, const Out& o, int q, unsigned M, hipStream_t s)
+{
+  if (!o.p || !M)
+    return;
+  const bool s16 = o.fmt == FMD_CIQ_S16;
+  const unsigned per = fmd::CIQ_G * (s16 ? fmd::CiqS16::PER : fmd::CiqF32::PER); // samples of a workgroup
+  const unsigned tiles = (M + per - 1) / per;
+  if (b->sel_ciq.on)
+  { // the selected writer (fmd_batch_select_ciq): this batch's part of the list
+    const unsigned n = unsigned(b->sel_ciq.ent.size());
+    const int* tab = n ? sel_table(b, b->sel_ciq, true, s) : nullptr;
+    if (!tab)
+      return;
+    const int2* ent = reinterpret_cast<const int2*>(tab);
+    if (s16)
+      hipLaunchKernelGGL(fmd::k_ciq_out_sel<fmd::CiqS16>, dim3(n, tiles), dim3(fmd::CIQ_G), 0, s, b->demod[q].p,
+                         b->Mstride, M, ent, static_cast<int16_t*>(o.p), o.stride);
+    else
+      hipLaunchKernelGGL(fmd::k_ciq_out_sel<fmd::CiqF32>, dim3(n, tiles), dim3(fmd::CIQ_G), 0, s, b->demod[q].p,
+                         b->Mstride, M, ent, static_cast<float*>(o.p), o.stride);
+    sel_read_done(b, b->sel_ciq, s);
+  }
+  else if (s16)
+    hipLaunchKernelGGL(fmd::k_ciq_out<fmd::CiqS16>, dim3(b->C, tiles), dim3(fmd::CIQ_G), 0, s, b->demod[q].p,
+                       b->Mstride, M, static_cast<int16_t*>(o.p), o.stride);
+  else
+    hipLaunchKernelGGL(fmd::k_ciq_out<fmd::CiqF32>, dim3(b->C, tiles), dim3(fmd::CIQ_G), 0, s, b->demod[q].p,
+                       b->Mstride, M, static_cast<float*>(o.p), o.stride);
+}
+
 /* launch_if_stage<IN> of the call's format */
 inline int launch_if_stage_fmt(IqFormat fmt, fmd_batch* b, const void* d_iq, size_t iq_channel_stride, unsigned N,
                                unsigned pos, unsigned M, int q, hipStream_t sF, const std::function<void(int)>& mark,
@@ -399,6 +438,8 @@ int check_call(fmd_batch* b, const Call& c, fmd::CallPlan& pl)
     return fail(FMD_ERR_STATE, "the feed is off (fmd_batch_set_feed)");
   if (c.feed.p && c.feed.stride < pl.feed_n)
     return fail(FMD_ERR_ARG, "feed_channel_stride smaller than the call's feed samples");
+  if (c.ciq.p && c.ciq.stride < pl.M)
+    return fail(FMD_ERR_ARG, "ciq.stride smaller than the call's baseband length");
   return FMD_OK;
 }
 
@@ -601,6 +642,9 @@ int process_device_impl(fmd_batch* b, const Call& c)
       return rc;
     }
   }
+  // the call's channel IQ (the _call entry points), in front of EV_INDONE: that event, which fmd_batch_wait and the
+  // caller's stream wait for, so covers the rows too; a call without them launches nothing here
+  launch_ciq(b, c.ciq, q, M, sF);
   signal(ce[fmd_batch::EV_INDONE], sF);
 
   /* ---- K2: baseband-rate recurrences  (stream S) ---- */
@@ -1089,6 +1133,8 @@ int process_device_impl(fmd_batch* b, const Call& c)
     b->feed_g += A;
   if (c.feed.out)
     *c.feed.out = (c.feed.p && c.feed.deliver) ? pl.feed_n : 0;
+  if (c.ciq.out)
+    *c.ciq.out = c.ciq.p ? M : 0;
   return FMD_OK;
 }
 
