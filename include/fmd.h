@@ -273,6 +273,32 @@ struct fmd_batch* fmd_decoder_batch(fmd_decoder* d);
 /* ---- batch of independent channels on one GPU -------------------------------------- */
 typedef struct fmd_batch fmd_batch;
 
+/* Non-finite and denormal input.  Float IQ from a host or a damaged file may hold infinities, NaNs, values that overflow
+ * inside the IF filter's sum, and denormals.  A channel decodes such input as the reference's decoder decodes it: every
+ * output -- stage taps, audio in either format, multiplex, feed and channel IQ rows, the getters, RDS groups, block
+ * records and counters -- equals the reference's, finite values, infinities (with their sign), zeros (with theirs) and
+ * denormals bit for bit, and NaN where the reference has a NaN (sign and payload of a NaN are the processor's: an
+ * invalid operation gives 0xFFC00000 on x86 and 0x7FC00000 here).  Nothing is flushed, clamped or skipped, and no input
+ * value faults: the one address formed from a sample value, the serial stage's sine table offset, reads 0 beyond the
+ * table for a NaN phase, whose result is NaN anyway.
+ *  - Only the channels that read a capture are touched by what it holds: every other channel keeps the bits of the
+ *    same run without it, whatever lanes, waves and workgroups the two share.
+ *  - As in the reference, a decoder that has met a NaN stays poisoned: the FM PLL's state is NaN from the first
+ *    non-finite IF sample on, and with it baseband, audio and the RDS chain.  cFmDecoder::Reset does not clear all of
+ *    it, so neither do fmd_reset, fmd_batch_reset and fmd_batch_reset_channels: behind a reset the baseband is finite at
+ *    once, the resamplers and the RDS low-pass give NaN for the length of their histories, and the RDS PLL, matched
+ *    filter and bit recovery and the audio stay NaN for good (recursive state that Reset leaves behind).
+ *    fmd_batch_switch_captures carries the whole state, so a switch to a clean capture does not revive a slot either.
+ *  - What revives a slot is a new decoder: fmd_batch_retune_channels[_to] (also to the shift the slot has), or
+ *    fmd_batch_import_channels / fmd_batch_load_state of a decoder that was clean.  An exported, saved or moved
+ *    decoder is the decoder it was, NaNs included.
+ *  - FMD_PCM_S16, FMD_MPX_S16, FMD_FEED_S16 and FMD_CIQ_S16 give 0 for a NaN and saturate an infinity;
+ *    fmd_batch_read_pcm_clipped counts the latter and not the former.  The audio meter is NaN after a call with a NaN.
+ *  - The receiver (fmd_receiver_signal_status, fmd_receiver_pvr_signal_status) is outside this statement: like
+ *    cRadioReceiver::GetSignalStatus it converts a float level to int, which is undefined for NaN in the reference.
+ *  - The band scan: see fmd_scan_finish_*.
+ * tests/test_gpu_poison.py holds every one of these against the CPU oracle, lane by lane. */
+
 /* All channels share params (same geometry); tuning_shifts (optional, n_channels entries)
  * overrides the cFineTuner shift per channel (config 3: many stations from one capture),
  * NULL derives it from params->tuning_offset like FmDecode.cpp:250.  device = HIP ordinal. */
@@ -1048,7 +1074,12 @@ int fmd_scan_accumulate_host_fmt(fmd_scan* s, const void* iq, int format, size_t
                                  unsigned samples);
 /* Outputs (each optional, NULL = not written): psd [G][N], slot_db [G][T] (-inf for an ineligible slot), floor_db
  * [G] (the floor bin), cand [G][max_cand], counts [G] (the true candidate count, also when max_cand clips the
- * list).  Does not reset: accumulation may go on. */
+ * list).  Does not reset: accumulation may go on.
+ * A capture that held a NaN in any accumulated call: every bin of its psd is NaN (every bin of a segment depends on
+ * every sample, and the totals keep it), its floor_db is NaN, slot_db is NaN for
+ * every eligible slot and -inf for the others as always, and it has no candidate (counts = 0: no comparison with a NaN
+ * holds) -- until fmd_scan_reset.  The call returns as usual, and the other captures keep the bits of the same scan
+ * without that capture's poison. */
 int fmd_scan_finish_device(fmd_scan* s, float* d_psd, float* d_slot_db, float* d_floor_db, fmd_scan_candidate* d_cand,
                            unsigned max_cand, uint32_t* d_counts, void* stream);
 int fmd_scan_finish_host(fmd_scan* s, float* psd, float* slot_db, float* floor_db, fmd_scan_candidate* cand,

@@ -71,6 +71,14 @@ class Streams:
                 have = Streams._cache[(name, g, "u8")]
             self.rows.append(have)
 
+    @classmethod
+    def from_arrays(cls, rows):
+        """the streams of given captures: interleaved float32 I, Q per capture (they may hold any float at all)"""
+        s = cls.__new__(cls)
+        s.u8, s.rows = False, [np.ascontiguousarray(r, dtype=np.float32) for r in rows]
+        s.G = len(s.rows)
+        return s
+
     def row(self, g, pos, n):
         r = self.rows[g][2 * pos:2 * (pos + n)]
         assert r.size == 2 * n, "the stream is shorter than the script"
