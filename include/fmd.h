@@ -1085,6 +1085,83 @@ int fmd_scan_finish_device(fmd_scan* s, float* d_psd, float* d_slot_db, float* d
 int fmd_scan_finish_host(fmd_scan* s, float* psd, float* slot_db, float* floor_db, fmd_scan_candidate* cand,
                          unsigned max_cand, uint32_t* counts);
 
+/* ---- band splitter: wideband captures into decoder-rate bands --------------------------- */
+/* A 10-20 MS/s capture holds the whole FM band; a batch created at that rate pays the IF stage (tuner + FIR of order
+ * 8 D) per input sample and station.  The splitter is the coarse stage every SDR front end puts in front: it mixes and
+ * decimates each capture ONCE into a few overlapping bands at sample_rate_in / R, ordinary FMD_IQ_F32 captures for
+ * fmd_batch_process_device_fmt of a batch created at that rate (fmd_batch_set_capture_map lets any channel read any
+ * band).  A band is the reference's own cFineTuner followed by cDownsampleFilter (FmDecode.cpp:45-82,
+ * DownConvert.cpp:18-154) at a small integer decimation; the reference has no such stage.  Like the scan, a splitter
+ * owns no stream and touches no fmd_batch; it runs asynchronously on the caller's stream.
+ *
+ * Geometry: G = n_captures, B = n_bands, G B output rows; row r = g B + b reads capture g and has its own tuner shift
+ * shifts[r] (fmd_batch_create's tuning_shifts: the band's centre is -shift fs / T).
+ * Definition.  q counts a capture's input samples since create / reset (64 bits, the same for all captures); x[q] is
+ * the input sample converted as the decoder converts FMD_IQ_*; x[q] = 0 for q < 0.
+ *  - Taps: c[1..K] = fmd_design_lanczos(K, cutoff)[1..K];  lut = fmd_design_tuner_lut(T, shift).
+ *  - Tuner: t[q] = x[q] lut[q mod T], re = a.re*b.re - a.im*b.im, im = a.re*b.im + a.im*b.re, every operation
+ *    rounded, nothing fused.
+ *  - Filter: for every q that is a multiple of R, y = sum_{j = 1..K} t[q - j] c[j]: real and imaginary parts summed
+ *    apart, from 0.0f, j = 1..K in order, a multiply then an add per tap, each rounded (DownConvert.cpp:117-121).
+ *  - Output: the row's next sample is y * out_scale (each part).
+ * A call of `samples` >= 1 delivers to every row the outputs whose q falls inside the call -- the same count for all
+ * rows, known on the host when the call returns (*out_samples).  History and phase carry over calls of any size, also
+ * calls shorter than K or R.  Row elements beyond the count are not written.
+ * Determinism: a row's bits depend on its capture's stream, its shift and the parameters alone -- not on G, B, the
+ * row's index, the tiling, the call sizes or the stream.  Non-finite and denormal input is summed as the definition
+ * sums it (NaN where the definition has a NaN, bit for bit otherwise) and touches only the rows of its capture.
+ * The carried state is the RAW history (the last K input samples of every capture) and q, nothing per band: so
+ * fmd_split_set_shifts makes every row, from the next call submitted, bit for bit the row of a splitter that had the
+ * new shifts from the start.  It does not wait for the device.
+ * Errors: FMD_ERR_ARG (with a sentence naming the field) for null arguments, a parameter out of range, a format
+ * outside FMD_IQ_*, a stride shorter than the call with more than one capture or row, a misaligned pointer -- all
+ * before the HIP runtime is touched; FMD_ERR_DEVICE "no HIP device" without a GPU (no CPU fallback); FMD_ERR_SIZE for
+ * samples of 0 or above FMD_SPLIT_MAX_SAMPLES.  One thread at a time per splitter; the calls of one splitter go on
+ * one stream (or streams the caller orders). */
+#define FMD_SPLIT_MAX_SAMPLES 16777216u /* input samples per capture and call */
+typedef struct fmd_split_params
+{
+  double sample_rate_in; /* > 0 */
+  unsigned decimation;   /* R: 2..64 */
+  unsigned filter_order; /* K: 2..1024; 0 = 8 R, the reference's rule (FmDecode.cpp:262) */
+  double cutoff;         /* fraction of the input rate, (0, 0.5]; 0 = 0.6 / R, the reference's */
+  unsigned table_size;   /* T: 1..1024; 0 = 64 */
+  float out_scale;       /* any finite float; 0 = 0.5f: it undoes the tuner's factor 2, so the next decoder's
+                            interface_level reads what it reads for a native capture */
+} fmd_split_params;
+typedef struct fmd_split fmd_split;
+
+/* n_captures, n_bands >= 1, at most 65535 captures and 2^20 rows; shifts[n_captures * n_bands] */
+int fmd_split_create(const fmd_split_params* p, unsigned n_captures, unsigned n_bands, const int* shifts, int device,
+                     fmd_split** out);
+void fmd_split_destroy(fmd_split* s);
+/* zero history, q = 0 (asynchronously on stream) */
+int fmd_split_reset(fmd_split* s, void* stream);
+/* new shifts for all n_rows = G B rows, from the next call submitted; returns without waiting for the device */
+int fmd_split_set_shifts(fmd_split* s, const int* shifts, unsigned n_rows);
+/* G B;  fs / R;  the most outputs per row a call of `samples` can deliver: ceil(samples / R) */
+int fmd_split_rows(const fmd_split* s);
+double fmd_split_out_rate(const fmd_split* s);
+unsigned fmd_split_max_out_samples(const fmd_split* s, unsigned samples);
+/* the K taps in use (c[1..K]); returns K, nothing past cap is written */
+int fmd_split_get_taps(const fmd_split* s, float* out, unsigned cap);
+/* Testing aids, no part of the contract above (they say how this build works inside and may change with it): the
+ * input samples one workgroup's tile of outputs covers -- a whole number of R, what tests put call sizes around --
+ * and how many page-locked staging versions of the tuner tables exist (one more whenever new shifts had to be
+ * uploaded while every earlier upload was still in flight: fmd_split_set_shifts never waits). */
+unsigned fmd_split_tile_samples(const fmd_split* s);
+int fmd_split_debug_table_versions(const fmd_split* s);
+/* Capture g starts g * in_capture_stride IQ samples of iq_format behind d_in (pointer and stride: multiples of two
+ * IQ samples, as fmd_batch_process_device_fmt); row r starts r * out_row_stride complex64 samples behind d_out,
+ * which must be 16-byte aligned, out_row_stride even (the batch needs 16-byte aligned captures) and >= the call's
+ * count (fmd_split_max_out_samples always is, rounded up to even).  *out_samples (optional) = the count. */
+int fmd_split_process_device(fmd_split* s, const void* d_in, int iq_format, size_t in_capture_stride, unsigned samples,
+                             void* d_out, size_t out_row_stride, unsigned* out_samples, void* stream);
+/* The same from and to pageable host memory, any alignment; out_row_stride any value >= the count, odd ones too
+ * (rows are copied one by one through a device staging buffer).  It waits. */
+int fmd_split_process_host(fmd_split* s, const void* in, int iq_format, size_t in_capture_stride, unsigned samples,
+                           void* out, size_t out_row_stride, unsigned* out_samples);
+
 /* ---- host-only pieces (no GPU needed) ----------------------------------------------- */
 /* UECP group decoder = cRDSGroupDecoder (RDSGroupDecoder.cpp:166-1001). */
 typedef struct fmd_group_decoder fmd_group_decoder;

@@ -134,6 +134,12 @@ class FmdScanParams(C.Structure):
                 ("floor_quantile", C.c_float)]
 
 
+class FmdSplitParams(C.Structure):
+    """fmd_split_params (include/fmd.h): 0 = the field's default."""
+    _fields_ = [("sample_rate_in", C.c_double), ("decimation", C.c_uint), ("filter_order", C.c_uint),
+                ("cutoff", C.c_double), ("table_size", C.c_uint), ("out_scale", C.c_float)]
+
+
 class FmdScanCandidate(C.Structure):
     _fields_ = [("shift", C.c_int32), ("offset_hz", C.c_float), ("power_db", C.c_float), ("snr_db", C.c_float)]
 
@@ -215,6 +221,9 @@ EXPORTS = [
     "fmd_batch_select_audio", "fmd_batch_select_mpx", "fmd_batch_get_audio_selection", "fmd_batch_get_mpx_selection",
     "fmd_batch_set_rds_blocks", "fmd_batch_get_rds_blocks", "fmd_batch_collect_rds_blocks",
     "fmd_batch_read_rds_quality",
+    "fmd_split_create", "fmd_split_destroy", "fmd_split_reset", "fmd_split_set_shifts", "fmd_split_rows",
+    "fmd_split_out_rate", "fmd_split_max_out_samples", "fmd_split_get_taps", "fmd_split_tile_samples",
+    "fmd_split_debug_table_versions", "fmd_split_process_device", "fmd_split_process_host",
 ]
 
 
@@ -389,6 +398,22 @@ def lib():
         L.fmd_batch_get_rds_blocks.argtypes = [vp]
         L.fmd_batch_collect_rds_blocks.argtypes = [vp, vp, u, i, vp, C.POINTER(u)]
         L.fmd_batch_read_rds_quality.argtypes = [vp, u, u, vp]
+        L.fmd_split_create.argtypes = [C.POINTER(FmdSplitParams), u, u, vp, i, C.POINTER(vp)]
+        L.fmd_split_destroy.argtypes = [vp]
+        L.fmd_split_destroy.restype = None
+        L.fmd_split_reset.argtypes = [vp, vp]
+        L.fmd_split_set_shifts.argtypes = [vp, vp, u]
+        L.fmd_split_rows.argtypes = [vp]
+        L.fmd_split_out_rate.restype = C.c_double
+        L.fmd_split_out_rate.argtypes = [vp]
+        L.fmd_split_max_out_samples.restype = u
+        L.fmd_split_max_out_samples.argtypes = [vp, u]
+        L.fmd_split_get_taps.argtypes = [vp, vp, u]
+        L.fmd_split_tile_samples.restype = u
+        L.fmd_split_tile_samples.argtypes = [vp]
+        L.fmd_split_debug_table_versions.argtypes = [vp]
+        L.fmd_split_process_device.argtypes = [vp, vp, i, C.c_size_t, u, vp, C.c_size_t, C.POINTER(u), vp]
+        L.fmd_split_process_host.argtypes = [vp, vp, i, C.c_size_t, u, vp, C.c_size_t, C.POINTER(u)]
         _LIB = L
     return _LIB
 

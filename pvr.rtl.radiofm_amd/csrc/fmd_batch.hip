@@ -1566,6 +1566,7 @@ void build_walk(const fmd_batch* b, uint2* out)
 #include "fmd_batch_if.inc.hpp"      // launch_if_stage: the IF stage's kernel forms
 #include "fmd_batch_process.inc.hpp" // process_device_impl: one call on the batch's streams
 #include "fmd_scan.inc.hpp"          // fmd_scan_*: the band scan (its own object, the caller's stream)
+#include "fmd_split.inc.hpp"         // fmd_split_*: the band splitter (its own object, the caller's stream)
 
 namespace
 {

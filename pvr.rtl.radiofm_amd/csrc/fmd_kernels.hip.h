@@ -31,3 +31,4 @@
 #include "fmd_k_restart.hip.h"
 #include "fmd_k_state.hip.h"
 #include "fmd_k_scan.hip.h"
+#include "fmd_k_split.hip.h"
