@@ -1024,8 +1024,10 @@ fmd_decoder* fmd_receiver_decoder(fmd_receiver* r);
  *    N) / (N/2) + 1 whole segments; the samples behind the last one are not used and nothing carries over.
  *  - Slots: shift k in [-floor(T/2), -floor(T/2) + T - 1] (fmd_batch_create's tuning_shifts), centred at f(k) =
  *    -k fs / T.  Slot power = sum of P[i] over the bins within +-half_width_hz of f(k); eligible when |f(k)| +
- *    half_width_hz <= fs/2 (no wrap-around).  Floor bin = the floor(q (N-1))-th smallest P[i], q = floor_quantile;
- *    a slot's floor = floor bin x its bin count; snr_db = 10 log10(slot power / slot floor).
+ *    half_width_hz <= fs/2 (no wrap-around) and at least one bin lies within +-half_width_hz of f(k) (a slot
+ *    narrower than a bin, 2 half_width_hz < fs / N, may hold none: it is ineligible like one at the band's edge:
+ *    slot_db -inf, never a candidate, never compared with).  Floor bin = the floor(q (N-1))-th smallest P[i], q =
+ *    floor_quantile; a slot's floor = floor bin x its bin count; snr_db = 10 log10(slot power / slot floor).
  *  - Candidate: an eligible slot with snr_db >= threshold_db whose power is >= that of every eligible slot within
  *    +-min_separation_hz and > that of those among them with a smaller shift.  Listed by increasing frequency.
  * Determinism: the order of every sum depends on (nfft, samples) alone and the totals (double, on the device) add
@@ -1074,7 +1076,12 @@ int fmd_scan_accumulate_host_fmt(fmd_scan* s, const void* iq, int format, size_t
                                  unsigned samples);
 /* Outputs (each optional, NULL = not written): psd [G][N], slot_db [G][T] (-inf for an ineligible slot), floor_db
  * [G] (the floor bin), cand [G][max_cand], counts [G] (the true candidate count, also when max_cand clips the
- * list).  Does not reset: accumulation may go on.
+ * list).  Does not reset: accumulation may go on, and a finish changes nothing a later finish reports.
+ * Any subset of the outputs may be asked for (cand without counts, counts alone with max_cand 0, ...); the two entry
+ * points give the same bits.  Capture g's list is cand[g][0 .. min(counts[g], max_cand) - 1], by increasing
+ * frequency: a clipped list holds the lowest-frequency candidates.  Nothing else is written: the entries of cand
+ * behind a capture's list (all of them with max_cand 0) and every byte behind an output's [G][..] extent keep what
+ * the caller put there.  fmd_scan_finish_device writes asynchronously on stream.
  * A capture that held a NaN in any accumulated call: every bin of its psd is NaN (every bin of a segment depends on
  * every sample, and the totals keep it), its floor_db is NaN, slot_db is NaN for
  * every eligible slot and -inf for the others as always, and it has no candidate (counts = 0: no comparison with a NaN

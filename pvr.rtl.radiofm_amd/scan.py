@@ -88,6 +88,12 @@ class Scan:
     def shifts(self):
         return np.arange(self.table_size, dtype=np.int32) + self.first_shift
 
+    def finish_device(self, psd=None, slot_db=None, floor_db=None, cand=None, max_cand=0, counts=None, stream=None):
+        """fmd_scan_finish_device: device pointers (None: not written) of psd [G, N], slot_db [G, T], floor_db [G]
+        (float32), cand [G, max_cand] (SCAN_CANDIDATE_DTYPE) and counts [G] (uint32), written asynchronously on
+        stream.  Nothing is reset."""
+        _check(lib().fmd_scan_finish_device(self._h, psd, slot_db, floor_db, cand, int(max_cand), counts, stream))
+
     def result(self, max_cand=None):
         """The scan so far (nothing is reset): psd [G, N] (bin i at (i - N/2) fs / N), freqs [N], shifts [T],
         slot_hz [T], slot_db [G, T] (-inf: ineligible), floor_db [G], candidates (per capture a list of dicts with
