@@ -108,12 +108,17 @@ using DevBuf = Buf<T, false>;
 template <typename T>
 using HostBuf = Buf<T, true>;
 
-/* An owning, move-only HIP event; converts to hipEvent_t (null until created). */
+/* An owning, move-only HIP event; converts to hipEvent_t (null until created).  `in_use` is for the events that
+ * guard a staging slot or a table used in rotation, and for nothing else (the events of a call's slot and the
+ * profiling events are recorded with hipEventRecord and never look at it): record_use() behind the copy or kernel
+ * that reads what the event guards, sync_if_in_use() in front of the host's next write -- a guard that was never
+ * set has nothing to wait for. */
 struct Event
 {
   hipEvent_t e = nullptr;
+  bool in_use = false;
   Event() = default;
-  Event(Event&& o) noexcept : e(std::exchange(o.e, nullptr)) {}
+  Event(Event&& o) noexcept : e(std::exchange(o.e, nullptr)), in_use(std::exchange(o.in_use, false)) {}
   ~Event() { release(); }
   hipError_t create(unsigned flags = hipEventDisableTiming)
   {
@@ -125,7 +130,14 @@ struct Event
     if (e)
       (void)hipEventDestroy(e);
     e = nullptr;
+    in_use = false;
   }
+  hipError_t record_use(hipStream_t s)
+  {
+    in_use = true;
+    return hipEventRecord(e, s);
+  }
+  hipError_t sync_if_in_use() const { return in_use ? hipEventSynchronize(e) : hipSuccess; }
   operator hipEvent_t() const { return e; }
 };
 
@@ -229,6 +241,8 @@ struct fmd_batch
   void* user = nullptr;
   std::vector<int> shifts;
 
+  static constexpr int NSLOT = 8; // event sets, RDS queues and staging slots in rotation (call_index % NSLOT)
+
   // host-tracked, batch-uniform positions
   unsigned if_pos = 0;     // cDownsampleFilter::m_pos_int
   unsigned lut_idx = 0;    // cFineTuner::m_index
@@ -291,8 +305,7 @@ struct fmd_batch
   static constexpr unsigned kOscH = 64;
   DevBuf<fmd::HbOsc> osc_tab[4]; // (+ HBF_SLACK entries that are read but never used, see k_halfband_chain)
   HostBuf<fmd::HbOsc> h_osc;     // [NSLOT][kOscH + Mmax + 8]
-  Event osc_ev[8];           // [NSLOT] behind the copy out of a staging slot
-  bool osc_ev_used[8] = {};
+  Event osc_ev[NSLOT];           // behind the copy out of a staging slot
   size_t h_osc_stride = 0;
   float osc_re = 1.0f, osc_im = 0.0f; // CRDSDownConvert: m_Osc1 = (1, 0) (DownConvert.cpp:284)
   bool osc_on = false;
@@ -305,7 +318,7 @@ struct fmd_batch
                                // (2: 288 600 MS/s and the FIR 0.975 ms inside the pipeline; 3: 287 500 and 1.00)
   bool dbg_fir_interior = true; // k_if_fir_mt3<.., 2>: tiles inside a call take the interior body ("fir_ro" -2: none
                                // does; the sign of that key and not a key of its own: the key table is held to 14)
-  int dbg_lpf_late = -1;       // stream layout of an overlapped call (process_device_impl): -1 the library decides,
+  int dbg_lpf_late = -1;       // stream layout of an overlapped call (submit_overlapped): -1 the library decides,
                                // 0 low-pass filters on the heavy stream, 1 on a stream of their own, 2 at the
                                // heads of the light part's two streams
   // where a host-buffer call's time goes (fmd_batch_debug_host_ms): copy in, submission, wait + copy
@@ -317,8 +330,6 @@ struct fmd_batch
   DevBuf<float> fstate; // all float state arrays, CP each
   DevBuf<int> istate;
   DevBuf<uint16_t> r_data;
-  static constexpr int NSLOT = 8; // event sets / RDS queues in rotation (call_index % NSLOT)
-  static_assert(NSLOT == 8, "osc_ev / osc_ev_used above");
   DevBuf<fmd::RdsGroupRec> queue[NSLOT]; // never drained while a call that appends to it is in flight
   DevBuf<unsigned> queue_counts; // [NSLOT], contiguous: one copy reads them all
   unsigned* qcount(int q) const { return queue_counts.p + q; }
@@ -331,7 +342,7 @@ struct fmd_batch
   HostBuf<fmd::RdsGroupRec> h_recs;
   unsigned queue_cap = 0;
   /* The block observation (fmd_batch_set_rds_blocks).  The mode is the caller-facing batch's
-   * and every sub-batch's next call's; a call takes it along in its LightJob.  Nothing of this exists on the device
+   * and every sub-batch's next call's; a call reads it when it is submitted.  Nothing of this exists on the device
    * until the first call of fmd_batch_set_rds_blocks that enables a mode: then the counters ([RQ_N][CP], zero, and
    * from there on touched by nothing but the observing kernels), and with the first mode 2 the block queues -- one
    * per event slot like the group queues, with counts, staging and drained bookkeeping of their own: the two drains
@@ -367,8 +378,7 @@ struct fmd_batch
   // fmd_batch_debug_mpx_ms (its first query switches this on): the multiplex writer's own start and stop of the last
   // NSLOT calls that asked for the multiplex (events of their own, no slot of the stage list or the timeline)
   int dbg_mpx_timing = 0;
-  Event mpx_ev[8][2]; // [NSLOT]
-  bool mpx_ev_used[8] = {};
+  Event mpx_ev[NSLOT][2]; // (in_use of [slot][0]: a timed launch of the writer has recorded the pair)
   // per channel: audio samples that FMD_PCM_S16 calls saturated since the batch was created (k_audio_tail<OutS16>;
   // fmd_batch_read_pcm_clipped).  It belongs to the output like the audio meter: nothing resets it.
   DevBuf<unsigned long long> pcm_clip; // [CP]
@@ -387,7 +397,6 @@ struct fmd_batch
     HostBuf<int> h;     // what the upload reads: the version's own, rewritten only with the version
     Event read;         // behind the last kernel that reads d (and so behind the upload)
     hipStream_t stream = nullptr; // where `read` was last recorded
-    bool used = false;
   };
   struct Selection
   {
@@ -415,7 +424,6 @@ struct fmd_batch
   DevBuf<float> feed_taps, feed_x;
   Event feed_done;
   hipStream_t feed_stream = nullptr;
-  bool feed_used = false;
   int dbg_feed_skip_roll = 0;     // fmd_batch_debug_feed_skip_roll (mutation test): the history rows stay stale
   Selection sel_feed;             // which channels deliver feed rows (fmd_batch_select_feed): the multiplex's form
   DevBuf<float> h_feed;           // staging of the host-buffer call's feed rows (sized on first use)
@@ -434,7 +442,7 @@ struct fmd_batch
 
   // Internal streams: the IF FIR of the next calls (s_fir), the serial stage of this call (s_ser), the heavy part of
   // the post chain behind it (s_post: half-band chain, resampler) and its light part (s_rds, s_lpf: see the stream
-  // layouts in process_device_impl; a batch of one or two wavefronts runs its RDS chain and its audio chain side by
+  // layouts in front of submit_overlapped; a batch of one or two wavefronts runs its RDS chain and its audio chain side by
   // side on s_rds / s_post) are independent chains tied together, and to the caller's stream, with events.  Streams
   // of their own on purpose, and picked by measurement (pick_independent_streams): HIP multiplexes streams onto a
   // few hardware queues and two chains sharing a queue block each other.  demod, br, mix and the filters' inputs
@@ -445,28 +453,6 @@ struct fmd_batch
   //                  fmd_batch_collect_rds; lets call k+1's FIR overlap call k's serial stages
   int concurrency = 1;
   hipStream_t s_fir = nullptr, s_ser = nullptr, s_post = nullptr, s_rds = nullptr, s_lpf = nullptr;
-  // What the light part of a call's post chain (RDS PLL, matched filter, bit recovery, audio tail) needs to know
-  // about its call: see launch_light_rds / launch_light_audio.
-  struct LightJob
-  {
-    unsigned R = 0, A = 0, mf_g = 0, alpf_g = 0;
-    unsigned rds_lpf_g = 0;            // ring phase of the RDS low-pass at this call
-    const unsigned* org = nullptr;     // ring origins of the RDS low-pass / matched filter, or null (fmd_batch::org)
-    int q = 0, es = 0, sq = 0;
-    bool events = true;                // false: everything on the caller's stream, no event is recorded or waited for
-    bool lpf_here = false;             // the two complex low-pass filters are part of the light part (layout 2)
-    int audio_after = -1;              // event of the call the audio half waits for on its stream (-1: stream order)
-    bool status_after_rds = false;     // the two halves are on different streams: the status record waits for EV_RDS
-    hipEvent_t prev_aud = nullptr;     // ... and the bit recovery for the previous call's status record
-    uint32_t call_index = 0;
-    int rb_mode = 0;                   // FMD_RDS_BLOCKS_*: which form of the bit recovery the call launches
-    Out audio{FMT_PCM};                // the call's audio rows
-    hipEvent_t tl0 = nullptr, tl1 = nullptr; // profiling level 1: the audio tail's own start / stop
-    Selection* asel = nullptr;         // the call's audio selection, or null: one row per channel
-    // the feed of a call that asked for it (feed.p: the tail's feed form, the roll; feed.deliver: k_feed_out as well)
-    Out feed{FMT_FEED};
-    unsigned feed_p0 = 0, feed_n = 0;  // the call's first frame with an output, outputs of the call
-  };
   /* More channels than the whole-CU pipeline is built for (kSubBatchChannels = 64 CUs' worth of serial stage): the
    * batch the caller holds is a SHELL over ceil(C / 8192) sub-batches of equal size, each a complete batch of its own
    * (buffers, channel state, RDS queues, status snapshot), all on the shell's five streams.  A call is submitted
@@ -479,7 +465,7 @@ struct fmd_batch
   bool owns_streams = true;        // false: a sub-batch, the streams are its shell's
   hipEvent_t vheavy[2] = {nullptr, nullptr}; // shell: EV_HEAVY of the last two sub-batch calls of the common sequence
   // sub-batch: EV_HEAVY of the sub-batch call two back in the common sequence -- this call's IF FIR stays behind it
-  // (process_device_impl); else null
+  // (submit_front); else null
   hipEvent_t sched_prev2 = nullptr;
   bool split_post = false;
   bool serial_exclusive = false; // serial stage owns whole CUs (small batches, see the launch)
@@ -539,7 +525,6 @@ struct fmd_batch
   DevBuf<int2> d_edits;
   DevBuf<float2> d_rows;
   Event edit_ev[NSLOT];                // behind the copy out of a staging slot
-  bool edit_ev_used[NSLOT] = {};
   Event edit_done;                     // behind the restart (the twin's next call waits where streams differ)
   unsigned restart_seq = 0;
   /* Resetting single channels (fmd_batch_reset_channels): the ring phase of a channel's RDS
@@ -564,7 +549,6 @@ struct fmd_batch
   DevBuf<uint2> d_walk;                // [C]
   HostBuf<uint2> h_walk;               // [NSLOT][C]
   Event walk_ev[NSLOT];                // behind the copy out of a staging slot
-  bool walk_ev_used[NSLOT] = {};
 
   /* Saving, loading and moving channel state (fmd_batch_save_state and its kin).  A batch
    * with buffers of its own holds the table of its carried regions (state_tab, built on first use: the restart's
@@ -588,7 +572,6 @@ struct fmd_batch
   HostBuf<char> h_imp[NSLOT];
   DevBuf<char> d_imp[NSLOT];
   Event imp_ev[NSLOT];                 // behind the copy out of a staging slot
-  bool imp_ev_used[NSLOT] = {};
   unsigned imp_seq = 0;
   struct GdecImport
   {
@@ -1059,7 +1042,7 @@ int create_streams(fmd_batch* b)
   HIPCHK(hipDeviceGetStreamPriorityRange(&lo, &hi)); // lo = least, hi = greatest priority
   // (the two heavy chains side by side on a fifth stream: measured slower in rounds 1-3, removed.)  The
   // fifth stream carries the post chain's two low-pass filters or the light part's audio half: see the stream
-  // layouts in process_device_impl
+  // layouts in front of submit_overlapped
   const int nstreams = 5;
   // (the light chain's stream at the high priority too: measured twice, no difference; the heavy part's,
   // which since round 4 is on the loop that closes the period: 279 100 against 279 200 MS/s; with the
@@ -1112,7 +1095,7 @@ int create_one(const fmd_params* params, unsigned n_channels, const int* tuning_
   const fmd::Design& d = b->des;
   { // Smallest call.  Short blocks are decoded like the reference decodes them (a half-band stage
     // below L inputs passes its input on unfiltered, below 2 (L - 1) it refills its delay line from
-    // outputs, a block shorter than a filter keeps part of the old history: process_device_impl);
+    // outputs, a block shorter than a filter keeps part of the old history: stage_decimator_stages);
     // what is refused are only blocks so short that a stage would be left with NO sample -- there the
     // reference divides by zero in its level meters (FmDecode.cpp:522-539, RadioReceiver.cpp:584-598)
     // -- and blocks that give the unrolled 11-tap class fewer inputs than it reads unconditionally.
@@ -1127,7 +1110,7 @@ int create_one(const fmd_params* params, unsigned n_channels, const int* tuning_
       for (const auto& h : d.hb)
       {
         if (h.cic)
-        { // (an even number of inputs: process_device_impl)
+        { // (an even number of inputs: stage_decimator_stages)
           ok = ok && n >= 2 && n % 2 == 0;
           n = n / 2;
         }
@@ -1564,7 +1547,7 @@ void build_walk(const fmd_batch* b, uint2* out)
 } // namespace
 
 #include "fmd_batch_if.inc.hpp"      // launch_if_stage: the IF stage's kernel forms
-#include "fmd_batch_process.inc.hpp" // process_device_impl: one call on the batch's streams
+#include "fmd_batch_process.inc.hpp" // submit_call: one call on the batch's streams, stage by stage
 #include "fmd_scan.inc.hpp"          // fmd_scan_*: the band scan (its own object, the caller's stream)
 #include "fmd_split.inc.hpp"         // fmd_split_*: the band splitter (its own object, the caller's stream)
 
@@ -1703,8 +1686,7 @@ int submit_edits(fmd_batch* x, fmd_batch* tw, hipStream_t stream)
     if (f.imp >= 0)
       import_of[ch] = f.imp;
   const int slot = int(x->restart_seq++ % fmd_batch::NSLOT);
-  if (x->edit_ev_used[slot]) // the copy of NSLOT edits ago (long done unless the caller never waits)
-    HIPCHK(hipEventSynchronize(x->edit_ev[slot]));
+  HIPCHK(x->edit_ev[slot].sync_if_in_use()); // the copy of NSLOT edits ago (long done unless the caller never waits)
   int2* he = x->h_edits.p + size_t(slot) * 2 * x->C;
   float2* hr = x->h_rows.p ? x->h_rows.p + size_t(slot) * x->restart_rows_cap * T : nullptr;
   std::map<int, int> row_of; // shift % T -> row of the staging table
@@ -1740,8 +1722,7 @@ int submit_edits(fmd_batch* x, fmd_batch* tw, hipStream_t stream)
     dr = x->d_rows.p + size_t(slot) * x->restart_rows_cap * T;
     HIPCHK(hipMemcpyAsync(dr, hr, row_of.size() * T * sizeof(float2), hipMemcpyHostToDevice, sF));
   }
-  HIPCHK(hipEventRecord(x->edit_ev[slot], sF));
-  x->edit_ev_used[slot] = true;
+  HIPCHK(x->edit_ev[slot].record_use(sF));
   if (n_rs)
   {
     fmd::RestartTable tab{};
@@ -1979,7 +1960,7 @@ static int process_any(fmd_batch* b, const Call& c)
   t.audio.p = b->twin_audio.p;
   t.audio.stride = b->twin_audio.n;
   t.stream = c.stream;
-  const int trc = process_device_impl(tw, t);
+  const int trc = submit_call(tw, t);
   if (trc != FMD_OK)
     mark_failed(b, "the silent twin refused a call the batch took");
   return trc;
@@ -1988,7 +1969,7 @@ static int process_any(fmd_batch* b, const Call& c)
 static int process_shell(fmd_batch* b, const Call& c)
 {
   if (!b || b->subs.empty())
-    return process_device_impl(b, c);
+    return submit_call(b, c);
   fmd::CallPlan pl;
   if (int rc = check_call(b, c, pl))
     return rc;
@@ -2008,7 +1989,7 @@ static int process_shell(fmd_batch* b, const Call& c)
     sc.mpx = c.mpx.from_channel(ch0, b->sel_mpx.on);
     sc.feed = c.feed.from_channel(ch0, b->sel_feed.on);
     sc.ciq = c.ciq.from_channel(ch0, b->sel_ciq.on);
-    const int rc = process_device_impl(sb, sc);
+    const int rc = submit_call(sb, sc);
     if (rc != FMD_OK)
     { // the first sub-batch refuses what every one of them would refuse (same geometry, same positions): nothing
       // has been submitted.  Later: part of the call is on the device -- the batch is unusable until reset.
@@ -2756,7 +2737,7 @@ int fmd_batch_set_feed(fmd_batch* b, int divisor)
     x->feed_div = 0; // (off until everything below is in place)
     x->feed_T = 0;
     x->feed_g = 0;
-    x->feed_used = false;
+    x->feed_done.in_use = false;
     x->feed_x.release();
     x->feed_taps.release();
     if (!divisor)
@@ -3878,7 +3859,7 @@ int fmd_batch_debug_mpx_ms(fmd_batch* b, float* out, unsigned cap)
   for (int i = 0; i < fmd_batch::NSLOT && n < cap; i++)
   {
     float ms = 0.0f;
-    if (b->mpx_ev_used[i] && hipEventElapsedTime(&ms, b->mpx_ev[i][0], b->mpx_ev[i][1]) == hipSuccess)
+    if (b->mpx_ev[i][0].in_use && hipEventElapsedTime(&ms, b->mpx_ev[i][0], b->mpx_ev[i][1]) == hipSuccess)
       out[n++] = ms;
   }
   (void)hipGetLastError();

@@ -300,7 +300,7 @@ void write_host_part(fmd_batch* b, const unsigned* channels, unsigned n, uint32_
     origins = origins || x->origins_live;
   h.flags = flags | (origins ? SF_ORIGINS : 0u) | (x0->osc_on ? SF_OSC : 0u) | (b->map_on ? SF_MAP : 0u);
   char* p = blob + sizeof(StateHeader);
-  if (x0->osc_on && x0->h_osc.p) // what the next call copies in front of its own entries (process_device_impl)
+  if (x0->osc_on && x0->h_osc.p) // what the next call copies in front of its own entries (upload_oscillator)
     std::memcpy(p, x0->h_osc.p + size_t(x0->call_index % fmd_batch::NSLOT) * x0->h_osc_stride + x0->lastM, kOscBytes);
   p += kOscBytes;
   for (unsigned i = 0; i < n; i++, p += host_rec_bytes())
@@ -783,8 +783,7 @@ int import_impl(fmd_batch* b, const unsigned* channels, unsigned n, const void* 
   {
     fmd_batch* x = pl.x;
     const int slot = int(x->imp_seq++ % fmd_batch::NSLOT);
-    if (x->imp_ev_used[slot]) // the copy of eight imports ago
-      HIPCHK(hipEventSynchronize(x->imp_ev[slot]));
+    HIPCHK(x->imp_ev[slot].sync_if_in_use()); // the copy of eight imports ago
     if (x->h_imp[slot].n < pl.p.bytes || x->d_imp[slot].n < pl.p.bytes)
     { // (growing a slot frees the old one: the runtime waits for whatever still reads it)
       const size_t want = std::max(pl.p.bytes, size_t(1) << 16);
@@ -863,8 +862,7 @@ int submit_imports(fmd_batch* x, hipStream_t sF, const std::map<unsigned, int>& 
       continue;
     char* d = x->d_imp[p.slot].p;
     HIPCHK(hipMemcpyAsync(d, x->h_imp[p.slot].p, p.bytes, hipMemcpyHostToDevice, sF));
-    HIPCHK(hipEventRecord(x->imp_ev[p.slot], sF));
-    x->imp_ev_used[p.slot] = true;
+    HIPCHK(x->imp_ev[p.slot].record_use(sF));
     const fmd::StateTable tab = table_without(x, x->state_skip);
     hipLaunchKernelGGL(fmd::k_channel_import, dim3(state_blocks(m), tab.n + 1), dim3(256), 0, sF, tab,
                        (const fmd::StateEdit*)d, m, (const void*)(d + p.payload_at), p.n_cols, 0u,
