@@ -72,6 +72,16 @@ extern "C" {
 #define FMD_IQ_U8 1
 #define FMD_IQ_S8 2
 #define FMD_IQ_S16 3
+/* Real-sampled input, for a real band splitter only (fmd_split_create_real, below): one element per sample,
+ * 16 | the FMD_IQ_* of the same element type, converted like its I part (exact for the integers):
+ *   FMD_REAL_F32  float    as is              4 bytes per sample
+ *   FMD_REAL_S8   int8_t   (float)v * 2^-7    1
+ *   FMD_REAL_S16  int16_t  (float)v * 2^-15   2    (Airspy raw mode, direct-sampling ADC boards)
+ * 17 is not a format (no unsigned real samples).  Every entry point but fmd_split_process_* of a real splitter
+ * refuses these values like any other value outside 0..3. */
+#define FMD_REAL_F32 16
+#define FMD_REAL_S8 18
+#define FMD_REAL_S16 19
 
 /* Audio output formats: the `pcm_format` argument of the _pcm entry points.  L and R interleaved, host byte order.
  *   FMD_PCM_F32  float L, R     what cFmDecoder::ProcessStream hands its caller; the default everywhere   4 bytes
@@ -1124,7 +1134,28 @@ int fmd_scan_finish_host(fmd_scan* s, float* psd, float* slot_db, float* floor_d
  * outside FMD_IQ_*, a stride shorter than the call with more than one capture or row, a misaligned pointer -- all
  * before the HIP runtime is touched; FMD_ERR_DEVICE "no HIP device" without a GPU (no CPU fallback); FMD_ERR_SIZE for
  * samples of 0 or above FMD_SPLIT_MAX_SAMPLES.  One thread at a time per splitter; the calls of one splitter go on
- * one stream (or streams the caller orders). */
+ * one stream (or streams the caller orders).
+ *
+ * Real-sampled captures (fmd_split_create_real).  Wideband samplers also run in real mode: an Airspy in raw mode, a
+ * direct-sampling ADC board with the FM band in its first or second Nyquist zone.  A real splitter takes such a
+ * capture as it is, one element per sample (FMD_REAL_F32 / _S8 / _S16), instead of a zero Q interleaved by the host:
+ *  - Definition: x[q] = (convert(v[q]), +0.0f), then everything above as it stands -- taps, tuner, filter, output,
+ *    count, history, phase, fmd_split_set_shifts, reset, determinism and the non-finite rule ("touches only the rows
+ *    of its capture" included).  The rows are those of a complex splitter of the same parameters fed (v, +0) pairs.
+ *  - The implementation may leave out the tuner's two products with the zero part, t = (v lut.re, v lut.im).  The bits
+ *    do not change: a product with +0 is a zero, and adding or subtracting a zero changes nothing but, where the
+ *    other product is a zero too, that zero's sign; the zero times a tap stays a zero, and the tap sum, which starts
+ *    at +0.0f and therefore never is -0, is the same with either sign added to it.  (inf and NaN: lut is finite, so
+ *    the zero products are zeros there too.)
+ *  - sample_rate_in is the real sample rate; a band's centre is still -shift fs / T and the output rate fs / R.  A
+ *    real capture holds the station at RF f, un-inverted, at f - round(f / fs) fs in [-fs / 2, fs / 2), whatever the
+ *    Nyquist zone -- and its mirror at minus that: the band filter's stopband is what removes it.
+ *  - A splitter is real or complex for life: a real one takes only FMD_REAL_*, a complex one only FMD_IQ_*.  The
+ *    other kind is FMD_ERR_ARG with a sentence that says which kind the splitter is (behind the null checks; the
+ *    splitter stays as it was); a value that is neither is refused before anything else, as above.
+ *  - Output rows are complex64 as above: FMD_IQ_F32 captures for a batch.
+ * Not offered: real input anywhere but here (batch, decoder, receiver and scan refuse FMD_REAL_*; the band rows are
+ * ordinary captures, and the scan takes those), unsigned 8- or 16-bit real samples, saving a splitter's state. */
 #define FMD_SPLIT_MAX_SAMPLES 16777216u /* input samples per capture and call */
 typedef struct fmd_split_params
 {
@@ -1141,6 +1172,9 @@ typedef struct fmd_split fmd_split;
 /* n_captures, n_bands >= 1, at most 65535 captures and 2^20 rows; shifts[n_captures * n_bands] */
 int fmd_split_create(const fmd_split_params* p, unsigned n_captures, unsigned n_bands, const int* shifts, int device,
                      fmd_split** out);
+/* the same parameters, ranges and defaults, for real-sampled captures (FMD_REAL_*) */
+int fmd_split_create_real(const fmd_split_params* p, unsigned n_captures, unsigned n_bands, const int* shifts,
+                          int device, fmd_split** out);
 void fmd_split_destroy(fmd_split* s);
 /* zero history, q = 0 (asynchronously on stream) */
 int fmd_split_reset(fmd_split* s, void* stream);
@@ -1161,7 +1195,9 @@ int fmd_split_debug_table_versions(const fmd_split* s);
 /* Capture g starts g * in_capture_stride IQ samples of iq_format behind d_in (pointer and stride: multiples of two
  * IQ samples, as fmd_batch_process_device_fmt); row r starts r * out_row_stride complex64 samples behind d_out,
  * which must be 16-byte aligned, out_row_stride even (the batch needs 16-byte aligned captures) and >= the call's
- * count (fmd_split_max_out_samples always is, rounded up to even).  *out_samples (optional) = the count. */
+ * count (fmd_split_max_out_samples always is, rounded up to even).  *out_samples (optional) = the count.
+ * A real splitter: in_capture_stride and samples count real samples of iq_format (FMD_REAL_*); d_in and
+ * in_capture_stride must be multiples of FOUR real samples -- 16 bytes of F32, 4 of S8, 8 of S16. */
 int fmd_split_process_device(fmd_split* s, const void* d_in, int iq_format, size_t in_capture_stride, unsigned samples,
                              void* d_out, size_t out_row_stride, unsigned* out_samples, void* stream);
 /* The same from and to pageable host memory, any alignment; out_row_stride any value >= the count, odd ones too

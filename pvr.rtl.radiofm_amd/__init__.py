@@ -23,6 +23,7 @@ FMD_WARN_RDS_LOST = 1
 # IQ input formats (include/fmd.h FMD_IQ_*): the `format` argument of the _fmt entry points
 FMD_IQ_F32, FMD_IQ_U8, FMD_IQ_S8, FMD_IQ_S16 = 0, 1, 2, 3
 IQ_BYTES = {FMD_IQ_F32: 8, FMD_IQ_U8: 2, FMD_IQ_S8: 2, FMD_IQ_S16: 4}  # per IQ sample
+FMD_REAL_F32, FMD_REAL_S8, FMD_REAL_S16 = 16, 18, 19  # real samples, a real band splitter's input only (split.py)
 # audio output formats (include/fmd.h FMD_PCM_*): the `pcm_format` argument of the _pcm entry points
 FMD_PCM_F32, FMD_PCM_S16 = 0, 1
 PCM_BYTES = {FMD_PCM_F32: 4, FMD_PCM_S16: 2}  # per audio sample
@@ -224,6 +225,7 @@ EXPORTS = [
     "fmd_split_create", "fmd_split_destroy", "fmd_split_reset", "fmd_split_set_shifts", "fmd_split_rows",
     "fmd_split_out_rate", "fmd_split_max_out_samples", "fmd_split_get_taps", "fmd_split_tile_samples",
     "fmd_split_debug_table_versions", "fmd_split_process_device", "fmd_split_process_host",
+    "fmd_split_create_real",
 ]
 
 
@@ -399,6 +401,7 @@ def lib():
         L.fmd_batch_collect_rds_blocks.argtypes = [vp, vp, u, i, vp, C.POINTER(u)]
         L.fmd_batch_read_rds_quality.argtypes = [vp, u, u, vp]
         L.fmd_split_create.argtypes = [C.POINTER(FmdSplitParams), u, u, vp, i, C.POINTER(vp)]
+        L.fmd_split_create_real.argtypes = [C.POINTER(FmdSplitParams), u, u, vp, i, C.POINTER(vp)]
         L.fmd_split_destroy.argtypes = [vp]
         L.fmd_split_destroy.restype = None
         L.fmd_split_reset.argtypes = [vp, vp]

@@ -2,7 +2,8 @@
  * fmd_batch.hip -- C ABI (include/fmd.h) of the MI355X FM decoder: device memory, the
  * per-call position plan (host) and the kernel sequence.  gfx950 only, no CPU fallback.
  *
- * Build: hipcc --offload-arch=gfx950 -O3 -ffp-contract=off -fPIC -shared fmd_batch.hip -o libfmd_hip.so
+ * Build (the Makefile): hipcc --offload-arch=gfx950 -O3 -ffp-contract=off -fPIC -shared fmd_batch.hip
+ *                       fmd_split_real.hip -o libfmd_hip.so
  */
 #include "../../include/fmd.h"
 
@@ -191,6 +192,20 @@ inline bool format_ok(FormatKind k, int format)
 inline size_t format_esz(FormatKind k, int format)
 {
   return kFormats[k].esz[format];
+}
+
+/* FMD_REAL_* (16 | FMD_IQ_F32, _S8, _S16; no unsigned bytes): real samples, one element each.  Only a real band
+ * splitter takes them -- format_ok(FMT_IQ, ..) keeps refusing them everywhere else. */
+static_assert(FMD_REAL_F32 == (16 | FMD_IQ_F32) && FMD_REAL_S8 == (16 | FMD_IQ_S8) && FMD_REAL_S16 == (16 | FMD_IQ_S16),
+              "a real format is its IQ format with bit 4 set");
+inline bool real_format_ok(int format)
+{
+  return format == FMD_REAL_F32 || format == FMD_REAL_S8 || format == FMD_REAL_S16;
+}
+
+inline size_t real_format_esz(int format)
+{
+  return kFormats[FMT_IQ].esz[format & 3] / 2;
 }
 
 /* Where a call delivers one of its outputs -- the audio, the multiplex (the _mpx entry points), the feed (the _feed

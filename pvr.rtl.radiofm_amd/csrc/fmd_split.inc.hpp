@@ -7,6 +7,7 @@ struct fmd_split
 {
   int device = 0;
   unsigned G = 0, B = 0;
+  bool real = false;                // fmd_split_create_real: FMD_REAL_* input, one float a sample in window and history
   double fs = 0.0;
   float scale = 0.5f;
   fmd::SplitGeom geom{};            // the generic form's tile
@@ -18,6 +19,7 @@ struct fmd_split
   bool shifts_dirty = true;         // the device tables are not those of `shifts`
   DevBuf<float> d_coeff;
   DevBuf<float2> d_hist[2];         // [G][K] raw (converted) history, by call parity
+  DevBuf<float> d_rhist[2];         // ... of a real splitter
   DevBuf<float2> d_luts;            // [G B][T]: written by an upload on the calls' stream, behind its last reader
   /* Page-locked staging of one version of the tables: the upload in front of a call reads it when the stream gets
    * there, so it is written again only once `done`, recorded behind that upload, has completed.  A set_shifts never
@@ -41,6 +43,12 @@ namespace
 inline bool split_compiled(unsigned R, unsigned K)
 {
   return (R == 4 && K == 32) || (R == 8 && K == 64);
+}
+
+/* the geometry of a tile of TO outputs, for this splitter's kind */
+inline fmd::SplitGeom split_geom_of(const fmd_split* s, unsigned TO)
+{
+  return fmd::split_geom(s->geom.R, s->geom.K, s->geom.T, TO, s->real);
 }
 
 template <class In>
@@ -77,10 +85,17 @@ int split_check(const char* fn, fmd_split* s, const void* in, int format, size_t
                 const void* out, size_t out_stride, bool device_call)
 {
   const std::string f(fn);
-  if (!format_ok(FMT_IQ, format))
+  const bool real = real_format_ok(format);
+  if (!real && !format_ok(FMT_IQ, format))
     return fail(FMD_ERR_ARG, f + ": iq_format must be one of FMD_IQ_F32, _U8, _S8, _S16 (0..3)");
   if (!s || !in || !out)
     return fail(FMD_ERR_ARG, f + ": null splitter, input or output pointer");
+  if (real != s->real)
+    return fail(FMD_ERR_ARG,
+                f + (s->real ? ": this is a real splitter (fmd_split_create_real), iq_format must be one of "
+                               "FMD_REAL_F32, _S8, _S16 (16, 18, 19)"
+                             : ": this is a complex splitter (fmd_split_create), iq_format must be one of "
+                               "FMD_IQ_F32, _U8, _S8, _S16 (0..3)"));
   if (samples == 0 || samples > FMD_SPLIT_MAX_SAMPLES)
     return fail(FMD_ERR_SIZE, f + ": samples must be 1 .. FMD_SPLIT_MAX_SAMPLES (16777216)");
   if (s->G > 1 && in_stride < samples)
@@ -90,9 +105,17 @@ int split_check(const char* fn, fmd_split* s, const void* in, int format, size_t
     return fail(FMD_ERR_ARG, f + ": out_row_stride is shorter than the call's output count");
   if (device_call)
   {
-    const size_t pair = 2 * format_esz(FMT_IQ, format);
-    if (reinterpret_cast<uintptr_t>(in) % pair || (s->G > 1 && in_stride % 2))
-      return fail(FMD_ERR_ARG, f + ": d_in and in_capture_stride must be multiples of two IQ samples");
+    if (real)
+    {
+      if (reinterpret_cast<uintptr_t>(in) % (4 * real_format_esz(format)) || (s->G > 1 && in_stride % 4))
+        return fail(FMD_ERR_ARG, f + ": d_in and in_capture_stride must be multiples of four real samples");
+    }
+    else
+    {
+      const size_t pair = 2 * format_esz(FMT_IQ, format);
+      if (reinterpret_cast<uintptr_t>(in) % pair || (s->G > 1 && in_stride % 2))
+        return fail(FMD_ERR_ARG, f + ": d_in and in_capture_stride must be multiples of two IQ samples");
+    }
     if (reinterpret_cast<uintptr_t>(out) % 16 || out_stride % 2)
       return fail(FMD_ERR_ARG, f + ": d_out must be 16-byte aligned and out_row_stride even");
     if (out_stride < M)
@@ -136,7 +159,7 @@ int split_upload_tables(fmd_split* s, hipStream_t stream)
   return FMD_OK;
 }
 
-int split_process(fmd_split* s, const void* d_in, IqFormat fmt, size_t in_stride, unsigned samples, float2* d_out,
+int split_process(fmd_split* s, const void* d_in, int fmt, size_t in_stride, unsigned samples, float2* d_out,
                   size_t out_stride, unsigned* out_samples, hipStream_t stream)
 {
   HIPCHK(hipSetDevice(s->device));
@@ -147,7 +170,7 @@ int split_process(fmd_split* s, const void* d_in, IqFormat fmt, size_t in_stride
   fmd::SplitArgs a{};
   a.in = d_in;
   a.in_stride = s->G > 1 ? in_stride : 0;
-  a.hist = s->d_hist[s->parity].p;
+  a.hist = s->real ? static_cast<const void*>(s->d_rhist[s->parity].p) : s->d_hist[s->parity].p;
   a.luts = s->d_luts.p;
   a.coeff = s->d_coeff.p;
   a.out = d_out;
@@ -158,13 +181,18 @@ int split_process(fmd_split* s, const void* d_in, IqFormat fmt, size_t in_stride
   a.lut_k = unsigned((s->q % g.T + size_t(g.T) * ((g.K + g.T - 1) / g.T) - g.K) % g.T);
   a.lut_step = unsigned(fmd::kSplitThreads) % g.T;
   a.scale = s->scale;
-  a.g = s->compiled ? fmd::split_geom(g.R, g.K, g.T, fmd::kSplitThreads) : g;
+  a.g = s->compiled ? split_geom_of(s, fmd::kSplitThreads) : g;
   if (a.M)
   {
     const unsigned ntiles = (a.M + a.g.TO - 1) / a.g.TO;
     const unsigned lds = a.g.total * unsigned(sizeof(float2));
     switch (fmt)
     {
+    case FMD_REAL_F32:
+    case FMD_REAL_S8:
+    case FMD_REAL_S16: // (the real forms: fmd_split_real.hip)
+      fmd::split_real_launch(fmt, s->compiled ? int(g.R) : 0, ntiles, s->G, lds, stream, a);
+      break;
     case IQ_U8: split_launch<fmd::InU8>(s, a, ntiles, lds, stream); break;
     case IQ_S8: split_launch<fmd::InS8>(s, a, ntiles, lds, stream); break;
     case IQ_S16: split_launch<fmd::InS16>(s, a, ntiles, lds, stream); break;
@@ -173,6 +201,12 @@ int split_process(fmd_split* s, const void* d_in, IqFormat fmt, size_t in_stride
   }
   switch (fmt)
   {
+  case FMD_REAL_F32:
+  case FMD_REAL_S8:
+  case FMD_REAL_S16:
+    fmd::split_real_roll(fmt, s->G, g.K, d_in, a.in_stride, samples, s->d_rhist[s->parity].p,
+                         s->d_rhist[s->parity ^ 1u].p, stream);
+    break;
   case IQ_U8: split_roll<fmd::InU8>(s, d_in, a.in_stride, samples, stream); break;
   case IQ_S8: split_roll<fmd::InS8>(s, d_in, a.in_stride, samples, stream); break;
   case IQ_S16: split_roll<fmd::InS16>(s, d_in, a.in_stride, samples, stream); break;
@@ -186,6 +220,75 @@ int split_process(fmd_split* s, const void* d_in, IqFormat fmt, size_t in_stride
   return FMD_OK;
 }
 
+/* fmd_split_create / fmd_split_create_real: the same parameters, ranges and defaults */
+int split_create(const char* fn, bool real, const fmd_split_params* p, unsigned n_captures, unsigned n_bands,
+                 const int* shifts, int device, fmd_split** out)
+{
+  const std::string f(fn);
+  if (!p || !out || !shifts)
+    return fail(FMD_ERR_ARG, f + ": null argument (params, shifts or out)");
+  *out = nullptr;
+  if (n_captures == 0 || n_captures > 65535u)
+    return fail(FMD_ERR_ARG, f + ": n_captures must be 1 .. 65535");
+  if (n_bands == 0 || size_t(n_captures) * n_bands > (size_t(1) << 20))
+    return fail(FMD_ERR_ARG, f + ": n_bands must be at least 1 and n_captures * n_bands at most 2^20");
+  const double fs = p->sample_rate_in;
+  if (!(fs > 0.0) || !std::isfinite(fs))
+    return fail(FMD_ERR_ARG, f + ": sample_rate_in must be a positive rate");
+  const unsigned R = p->decimation;
+  if (R < 2 || R > 64)
+    return fail(FMD_ERR_ARG, f + ": decimation must be 2 .. 64");
+  const unsigned K = p->filter_order ? p->filter_order : 8 * R;
+  if (K < 2 || K > 1024)
+    return fail(FMD_ERR_ARG, f + ": filter_order must be 2 .. 1024 (0 = 8 * decimation)");
+  const double cutoff = p->cutoff != 0.0 ? p->cutoff : 0.6 / double(R);
+  if (!(cutoff > 0.0 && cutoff <= 0.5))
+    return fail(FMD_ERR_ARG, f + ": cutoff must lie in (0, 0.5] of the input rate (0 = 0.6 / decimation)");
+  const unsigned T = p->table_size ? p->table_size : 64u;
+  if (T > 1024)
+    return fail(FMD_ERR_ARG, f + ": table_size must be 1 .. 1024 (0 = 64)");
+  if (!std::isfinite(p->out_scale))
+    return fail(FMD_ERR_ARG, f + ": out_scale must be a finite float (0 = 0.5)");
+  // the largest tile of outputs whose windows fit the LDS of a workgroup
+  unsigned TO = fmd::kSplitThreads;
+  while (TO > 1 && fmd::split_geom(R, K, T, TO, real).total * sizeof(float2) > fmd::kSplitLdsBytes)
+    TO--;
+  const fmd::SplitGeom geom = fmd::split_geom(R, K, T, TO, real);
+  if (geom.total * sizeof(float2) > fmd::kSplitLdsBytes)
+    return fail(FMD_ERR_ARG, f + ": filter_order and table_size do not fit a workgroup's LDS");
+
+  int ndev = 0;
+  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
+    return fail(FMD_ERR_DEVICE, "no HIP device available (this library has no CPU fallback)");
+  if (device < 0 || device >= ndev)
+    return fail(FMD_ERR_ARG, f + ": device ordinal out of range");
+  if (real && (!fmd::split_real_launch || !fmd::split_real_roll)) // (never in the library: fmd_k_split.hip.h)
+    return fail(FMD_ERR_DEVICE, f + ": the real forms' kernels (fmd_split_real.o) are not linked into this program");
+  HIPCHK(hipSetDevice(device));
+  std::unique_ptr<fmd_split> s(new fmd_split);
+  s->device = device;
+  s->real = real;
+  s->G = n_captures;
+  s->B = n_bands;
+  s->fs = fs;
+  s->scale = p->out_scale != 0.0f ? p->out_scale : 0.5f;
+  s->geom = geom;
+  s->compiled = split_compiled(R, K) &&
+                fmd::split_geom(R, K, T, fmd::kSplitThreads, real).total * sizeof(float2) <= fmd::kSplitLdsBytes;
+  s->taps = fmd::make_lanczos(K, cutoff);
+  s->shifts.assign(shifts, shifts + size_t(n_captures) * n_bands);
+  const size_t rows = size_t(n_captures) * n_bands;
+  // (zero-filled: no sample in front of q = 0)
+  const size_t nh = size_t(n_captures) * K;
+  if (s->d_coeff.alloc(s->taps.size()) || s->d_luts.alloc(rows * T) ||
+      (real ? s->d_rhist[0].alloc(nh) || s->d_rhist[1].alloc(nh) : s->d_hist[0].alloc(nh) || s->d_hist[1].alloc(nh)))
+    return fail(FMD_ERR_DEVICE, f + ": device allocation failed");
+  HIPCHK(hipMemcpy(s->d_coeff.p, s->taps.data(), s->taps.size() * sizeof(float), hipMemcpyHostToDevice));
+  HIPCHK(hipDeviceSynchronize());
+  *out = s.release();
+  return FMD_OK;
+}
+
 } // namespace
 
 extern "C" {
@@ -193,64 +296,13 @@ extern "C" {
 int fmd_split_create(const fmd_split_params* p, unsigned n_captures, unsigned n_bands, const int* shifts, int device,
                      fmd_split** out)
 {
-  if (!p || !out || !shifts)
-    return fail(FMD_ERR_ARG, "fmd_split_create: null argument (params, shifts or out)");
-  *out = nullptr;
-  if (n_captures == 0 || n_captures > 65535u)
-    return fail(FMD_ERR_ARG, "fmd_split_create: n_captures must be 1 .. 65535");
-  if (n_bands == 0 || size_t(n_captures) * n_bands > (size_t(1) << 20))
-    return fail(FMD_ERR_ARG, "fmd_split_create: n_bands must be at least 1 and n_captures * n_bands at most 2^20");
-  const double fs = p->sample_rate_in;
-  if (!(fs > 0.0) || !std::isfinite(fs))
-    return fail(FMD_ERR_ARG, "fmd_split_create: sample_rate_in must be a positive rate");
-  const unsigned R = p->decimation;
-  if (R < 2 || R > 64)
-    return fail(FMD_ERR_ARG, "fmd_split_create: decimation must be 2 .. 64");
-  const unsigned K = p->filter_order ? p->filter_order : 8 * R;
-  if (K < 2 || K > 1024)
-    return fail(FMD_ERR_ARG, "fmd_split_create: filter_order must be 2 .. 1024 (0 = 8 * decimation)");
-  const double cutoff = p->cutoff != 0.0 ? p->cutoff : 0.6 / double(R);
-  if (!(cutoff > 0.0 && cutoff <= 0.5))
-    return fail(FMD_ERR_ARG, "fmd_split_create: cutoff must lie in (0, 0.5] of the input rate (0 = 0.6 / decimation)");
-  const unsigned T = p->table_size ? p->table_size : 64u;
-  if (T > 1024)
-    return fail(FMD_ERR_ARG, "fmd_split_create: table_size must be 1 .. 1024 (0 = 64)");
-  if (!std::isfinite(p->out_scale))
-    return fail(FMD_ERR_ARG, "fmd_split_create: out_scale must be a finite float (0 = 0.5)");
-  // the largest tile of outputs whose windows fit the LDS of a workgroup
-  unsigned TO = fmd::kSplitThreads;
-  while (TO > 1 && fmd::split_geom(R, K, T, TO).total * sizeof(float2) > fmd::kSplitLdsBytes)
-    TO--;
-  const fmd::SplitGeom geom = fmd::split_geom(R, K, T, TO);
-  if (geom.total * sizeof(float2) > fmd::kSplitLdsBytes)
-    return fail(FMD_ERR_ARG, "fmd_split_create: filter_order and table_size do not fit a workgroup's LDS");
+  return split_create("fmd_split_create", false, p, n_captures, n_bands, shifts, device, out);
+}
 
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
-    return fail(FMD_ERR_DEVICE, "no HIP device available (this library has no CPU fallback)");
-  if (device < 0 || device >= ndev)
-    return fail(FMD_ERR_ARG, "fmd_split_create: device ordinal out of range");
-  HIPCHK(hipSetDevice(device));
-  std::unique_ptr<fmd_split> s(new fmd_split);
-  s->device = device;
-  s->G = n_captures;
-  s->B = n_bands;
-  s->fs = fs;
-  s->scale = p->out_scale != 0.0f ? p->out_scale : 0.5f;
-  s->geom = geom;
-  s->compiled = split_compiled(R, K) &&
-                fmd::split_geom(R, K, T, fmd::kSplitThreads).total * sizeof(float2) <= fmd::kSplitLdsBytes;
-  s->taps = fmd::make_lanczos(K, cutoff);
-  s->shifts.assign(shifts, shifts + size_t(n_captures) * n_bands);
-  const size_t rows = size_t(n_captures) * n_bands;
-  // (zero-filled: no sample in front of q = 0)
-  if (s->d_coeff.alloc(s->taps.size()) || s->d_hist[0].alloc(size_t(n_captures) * K) ||
-      s->d_hist[1].alloc(size_t(n_captures) * K) || s->d_luts.alloc(rows * T))
-    return fail(FMD_ERR_DEVICE, "fmd_split_create: device allocation failed");
-  HIPCHK(hipMemcpy(s->d_coeff.p, s->taps.data(), s->taps.size() * sizeof(float), hipMemcpyHostToDevice));
-  HIPCHK(hipDeviceSynchronize());
-  *out = s.release();
-  return FMD_OK;
+int fmd_split_create_real(const fmd_split_params* p, unsigned n_captures, unsigned n_bands, const int* shifts,
+                          int device, fmd_split** out)
+{
+  return split_create("fmd_split_create_real", true, p, n_captures, n_bands, shifts, device, out);
 }
 
 void fmd_split_destroy(fmd_split* s)
@@ -269,8 +321,12 @@ int fmd_split_reset(fmd_split* s, void* stream)
     return fail(FMD_ERR_ARG, "fmd_split_reset: null splitter");
   HIPCHK(hipSetDevice(s->device));
   // (the buffer the next call reads; the other one is written whole before it is read)
-  HIPCHK(hipMemsetAsync(s->d_hist[s->parity].p, 0, size_t(s->G) * s->geom.K * sizeof(float2),
-                        static_cast<hipStream_t>(stream)));
+  if (s->real)
+    HIPCHK(hipMemsetAsync(s->d_rhist[s->parity].p, 0, size_t(s->G) * s->geom.K * sizeof(float),
+                          static_cast<hipStream_t>(stream)));
+  else
+    HIPCHK(hipMemsetAsync(s->d_hist[s->parity].p, 0, size_t(s->G) * s->geom.K * sizeof(float2),
+                          static_cast<hipStream_t>(stream)));
   s->q = 0;
   return FMD_OK;
 }
@@ -346,7 +402,7 @@ int fmd_split_process_device(fmd_split* s, const void* d_in, int iq_format, size
   if (int rc = split_check("fmd_split_process_device", s, d_in, iq_format, in_capture_stride, samples, d_out,
                            out_row_stride, true))
     return rc;
-  return split_process(s, d_in, IqFormat(iq_format), in_capture_stride, samples, static_cast<float2*>(d_out),
+  return split_process(s, d_in, iq_format, in_capture_stride, samples, static_cast<float2*>(d_out),
                        out_row_stride, out_samples, static_cast<hipStream_t>(stream));
 }
 
@@ -357,10 +413,11 @@ int fmd_split_process_host(fmd_split* s, const void* in, int iq_format, size_t i
                            out_row_stride, false))
     return rc;
   HIPCHK(hipSetDevice(s->device));
-  const size_t esz = format_esz(FMT_IQ, iq_format);
+  const size_t esz = s->real ? real_format_esz(iq_format) : format_esz(FMT_IQ, iq_format);
   const size_t rows = size_t(s->G) * s->B;
-  // device rows: captures one behind the other at an even stride, rows at the even stride the kernel needs
-  const size_t d_in_stride = (size_t(samples) + 1) & ~size_t(1);
+  // device rows: captures one behind the other at an even stride (real samples: a multiple of four), rows at the
+  // even stride the kernel needs
+  const size_t d_in_stride = s->real ? (size_t(samples) + 3) & ~size_t(3) : (size_t(samples) + 1) & ~size_t(1);
   const size_t d_out_stride = (size_t(fmd_split_max_out_samples(s, samples)) + 1) & ~size_t(1);
   const size_t in_bytes = s->G * d_in_stride * esz, out_bytes = rows * d_out_stride * sizeof(float2);
   if (in_bytes > s->d_stage_in.n || out_bytes > s->d_stage_out.n)
@@ -373,7 +430,7 @@ int fmd_split_process_host(fmd_split* s, const void* in, int iq_format, size_t i
   HIPCHK(hipMemcpy2D(s->d_stage_in.p, d_in_stride * esz, in, (s->G > 1 ? in_capture_stride : samples) * esz,
                      size_t(samples) * esz, s->G, hipMemcpyHostToDevice));
   unsigned M = 0;
-  if (int rc = split_process(s, s->d_stage_in.p, IqFormat(iq_format), d_in_stride, samples,
+  if (int rc = split_process(s, s->d_stage_in.p, iq_format, d_in_stride, samples,
                              reinterpret_cast<float2*>(s->d_stage_out.p), d_out_stride, &M, nullptr))
     return rc;
   HIPCHK(hipStreamSynchronize(nullptr));

@@ -14,6 +14,14 @@ ones; the formats of (a) and the two ways of (b) alternate `--visits` times and 
 the better visit.  Prints one JSON line and writes it to --out.
 
     python tools/split_bench.py --steps 20 --warmup 3 --out profiles/split.json
+
+--real: a real-sampled capture two ways at the same two geometries -- the real splitter on
+FMD_REAL_S16 / _F32 input, and what a host had to do without it, the complex splitter on the same samples with a zero Q
+interleaved (FMD_IQ_S16 / _F32, twice the bytes), same G, samples, R, B and shifts; the four alternate `--visits`
+times, every visit is reported.  Plus one direct-sampling geometry, reported and compared with nothing: 4 captures x
+4 194 304 samples at 122.88 MS/s, R 48, K 384, T 1024, 12 bands.
+
+    python tools/split_bench.py --real --out profiles/split_real.json
 """
 import argparse
 import json
@@ -62,6 +70,65 @@ def inputs(G, n):
     return {"f32": (f32, 8), "s16": (s16, 4), "s8": (s8, 2)}
 
 
+DIRECT_SAMPLING = {"fs": 122.88e6, "R": 48, "K": 384, "T": 1024, "captures": 4, "samples": 4194304, "bands": 12}
+
+
+def real_inputs(G, n):
+    """noise as real samples, and the same samples with a zero Q interleaved"""
+    torch.manual_seed(1)
+    f32 = (0.1 * torch.randn((G, n), dtype=torch.float32, device="cuda")).contiguous()
+    s16 = torch.clamp(f32 * 32767.0, -32768, 32767).to(torch.int16).contiguous()
+    zq = lambda t: torch.stack([t, torch.zeros_like(t)], dim=2).reshape(G, 2 * n).contiguous()
+    return {"real_s16": (s16, 2), "zero_q_s16": (zq(s16), 4), "real_f32": (f32, 4), "zero_q_f32": (zq(f32), 8)}
+
+
+def main_real(args, split):
+    stream = torch.cuda.current_stream().cuda_stream
+    res = {"alone_steps": args.alone_steps, "warmup": args.warmup, "visits": args.visits,
+           "device": torch.cuda.get_device_name(0), "compare": [], "direct_sampling": []}
+    for R, G, n, B in GEOMETRIES:
+        G = max(1, G // args.scale)
+        fs = FS_BAND * R
+        T, shifts = band_shifts(R, B)
+        x = real_inputs(G, n)
+        sp = {True: split.Splitter(fs, R, G, [shifts] * G, table_size=T, real=True),
+              False: split.Splitter(fs, R, G, [shifts] * G, table_size=T)}
+        out = torch.empty((G * B, sp[True].out_stride(n)), dtype=torch.complex64, device="cuda")
+        ms = {name: [] for name in x}
+        for _ in range(args.visits):
+            for name, (t, esz) in x.items():
+                s_ = sp[name.startswith("real")]
+                ms[name].append(timed(lambda: s_.process(t, n, out=out, stream=stream), args.alone_steps, args.warmup))
+        entry = {"R": R, "captures": G, "samples": n, "bands": B, "table_size": T,
+                 "ms_per_call": {k: [round(v, 4) for v in vs] for k, vs in ms.items()}}
+        for fmt in ("s16", "f32"):
+            r, z = ms["real_" + fmt], ms["zero_q_" + fmt]
+            entry["real_over_zero_q_" + fmt] = round(min(r) / min(z), 4)
+            entry["zero_q_spread_" + fmt] = round((max(z) - min(z)) / min(z), 4)
+            entry["real_slower_than_every_zero_q_visit_" + fmt] = bool(min(r) > max(z))
+        res["compare"].append(entry)
+        for s_ in sp.values():
+            s_.close()
+    d = DIRECT_SAMPLING
+    G, n, B = max(1, d["captures"] // args.scale), d["samples"], d["bands"]
+    span = d["T"] // 2 - 40
+    shifts = [int(round(-span + 2 * span * b / (B - 1))) for b in range(B)]
+    sp = split.Splitter(d["fs"], d["R"], G, [shifts] * G, filter_order=d["K"], table_size=d["T"], real=True)
+    out = torch.empty((G * B, sp.out_stride(n)), dtype=torch.complex64, device="cuda")
+    x = real_inputs(G, n)
+    for name in ("real_s16", "real_f32"):
+        t, esz = x[name]
+        v = [timed(lambda: sp.process(t, n, out=out, stream=stream), max(1, args.alone_steps // 20), args.warmup)
+             for _ in range(args.visits)]
+        floor = G * n * (esz + 8.0 * B / d["R"])
+        res["direct_sampling"].append(dict(d, captures=G, input=name, tile_samples=sp.tile_samples,
+                                           ms_per_call=[round(a, 4) for a in v], floor_bytes=int(floor),
+                                           GBps_of_floor_bytes=round(floor / min(v) / 1e6, 1),
+                                           signal_ms_per_call=round(n / d["fs"] * 1e3, 3)))
+    sp.close()
+    return res
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--steps", type=int, default=20)
@@ -69,12 +136,20 @@ def main():
     ap.add_argument("--alone-steps", type=int, default=1000, help="calls of the splitter alone per timed window")
     ap.add_argument("--visits", type=int, default=2)
     ap.add_argument("--scale", type=int, default=1, help="divide captures by this (a rehearsal at a small size)")
+    ap.add_argument("--real", action="store_true", help="real-sampled input against zero-Q complex input")
     ap.add_argument("--out", default="")
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("split_bench: no GPU (nothing here is measured on a CPU)")
     pkg = load_package()
     split = import_module(pkg.__name__ + ".split")
+    if args.real:
+        line = json.dumps(main_real(args, split))
+        print(line)
+        if args.out:
+            with open(args.out, "w") as f:
+                f.write(line + "\n")
+        return
     stream = torch.cuda.current_stream().cuda_stream
     res = {"steps": args.steps, "alone_steps": args.alone_steps, "warmup": args.warmup, "device": torch.cuda.get_device_name(0), "alone": [],
            "decode": []}
