@@ -171,6 +171,26 @@ public:
     return n > 0 ? static_cast<unsigned int>(n) : 0u;
   }
 
+  /* Not in the reference: the way back in -- one call from the station's complex baseband behind tuner and IF filter
+   * (fmd.h, FMD_IN_CIQ_*), `m` complex samples (re, im floats) at sample_rate_if / downsample: what
+   * ProcessStreamWithChannelIq delivered, from an archive, or a channeliser's of the caller's own.  The IF stage does
+   * not run and keeps its state; everything behind it takes the samples as its output.  The audio as ProcessStream
+   * writes it; returns the floats written.  ProcessChannelIqToPcm16 / ProcessChannelIqWithMpx: the record form with
+   * the audio as int16 (FMD_PCM_S16) / with the multiplex beside it (`mpx`: a buffer of m floats). */
+  unsigned int ProcessChannelIq(const float* ciq, unsigned int m, float* audio)
+  {
+    return ChannelIqCall(ciq, m, audio, FMD_PCM_F32, nullptr, nullptr);
+  }
+  unsigned int ProcessChannelIqToPcm16(const float* ciq, unsigned int m, int16_t* audio)
+  {
+    return ChannelIqCall(ciq, m, audio, FMD_PCM_S16, nullptr, nullptr);
+  }
+  unsigned int ProcessChannelIqWithMpx(const float* ciq, unsigned int m, float* audio, float* mpx,
+                                       unsigned int* mpx_samples)
+  {
+    return ChannelIqCall(ciq, m, audio, FMD_PCM_F32, mpx, mpx_samples);
+  }
+
   /* Not in the reference: what its block synchroniser computes and drops (fmd.h, "Every RDS block decision").
    * SetRdsBlocks: the observation of every ProcessStream from now on (FMD_RDS_BLOCKS_*); CollectRdsBlocks: the block
    * records queued so far, in order, into `out` (returns their number; *lost: records that did not fit);
@@ -190,6 +210,22 @@ public:
   }
 
 private:
+  unsigned int ChannelIqCall(const float* ciq, unsigned int m, void* audio, int pcm_format, float* mpx,
+                             unsigned int* mpx_samples)
+  {
+    fmd_call c{};
+    c.size = sizeof(fmd_call);
+    c.iq = ciq;
+    c.iq_format = FMD_IN_CIQ_F32;
+    c.samples = m;
+    c.audio.p = audio;
+    c.audio.format = pcm_format;
+    c.mpx.p = mpx;
+    c.mpx.format = FMD_MPX_F32;
+    c.mpx.count = mpx_samples;
+    const int n = fmd_process_stream_call(m_dec, &c);
+    return n > 0 ? static_cast<unsigned int>(n) : 0u;
+  }
   fmd_status Status() const
   {
     fmd_status st{};

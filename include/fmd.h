@@ -175,6 +175,40 @@ extern "C" {
 #define FMD_CIQ_F32 0
 #define FMD_CIQ_S16 1
 
+/* The way back in: channel IQ rows as the INPUT of a call -- an archive made through `ciq`
+ * decoded again, or the rows of a channeliser of the caller's own (a polyphase filter bank, an FPGA front end, a DDC in
+ * the receiver).  Two more values of fmd_call.iq_format, taken by the three _call entry points only
+ * (fmd_batch_process_device_call, fmd_batch_process_host_call, fmd_process_stream_call); every positional entry point,
+ * the receiver, the scan and the splitter refuse them with FMD_ERR_ARG and a sentence, before anything else is touched:
+ *   FMD_IN_CIQ_F32  float   re, im   as is: the bits FMD_CIQ_F32 and FMD_TAP_DEMOD deliver
+ *   FMD_IN_CIQ_S16  int16_t re, im   (float)v * 2^-13 of each part (fmd_ciq16_to_f32): exact in float and the inverse
+ *                                    scale of FMD_CIQ_S16 -- a call with S16 rows has the bits of the F32 call on the
+ *                                    same rows converted by the host
+ * Field meanings with these formats: `iq` is one row per channel, channel c reads row c, no capture map is consulted
+ * and channels-per-capture does not apply; `iq_channel_stride` is in COMPLEX SAMPLES; `samples` is M, the baseband
+ * length of the call (what fmd_batch_max_mpx_samples counts for an IQ call).
+ * Device call: the pointer 16-byte aligned, the stride a multiple of 2 complex samples (F32) / 4 (S16), and >= M when
+ * the batch has more than one channel -- the rules of the `ciq` output's rows.  Host call and single decoder: any
+ * stride >= M and any alignment, through the input's staging buffer.
+ * Which M: exactly those an IQ call producing that M would be accepted with, and the plan's sentences
+ * (FMD_ERR_SIZE): too short for the RDS chain or for an audio frame, M + 51 > 32768, an odd M in front of CIC stages,
+ * M above the batch's largest.  fmd_batch_baseband_limits has the numbers: *min = fmd_batch_min_samples / downsample,
+ * *max = the decimator's outputs of the largest block, *multiple = 2 per CIC stage of the RDS decimator (else 1).
+ * What such a call does: the IF stage does not run -- no tuner, no FIR, no level meter -- and its carried state (the
+ * filter's history, the tuner's phase, the decimator's phase) is untouched: the next IQ call continues as if the
+ * channel-IQ calls between had not happened.  Everything behind the IF stage takes the rows as that stage's output of
+ * a call of baseband length M: audio in both PCM formats, multiplex, feed and `ciq` out (a copy of the input, F32
+ * bits), status, audio meter and clip counters, RDS groups, block records and counters, UECP frames, selections and
+ * debug taps (FMD_TAP_DEMOD returns the row).  interface_level, the one status field that reads raw IQ, keeps the
+ * value the last IQ call left.  The kind belongs to the call like the formats: consecutive calls may differ, with calls
+ * in flight.  Edits (resets, retunes, switches, imports, loads) are applied in front of the next call submitted as
+ * ever; what they change in the IF stage is seen by the next IQ call.  State blobs are unchanged.  Non-finite rows
+ * are decoded as the definition says, NaN for NaN, confined to their channel.  The input buffer is free when the
+ * copying kernel (k_ciq_in, in the IF stage's place on its stream) has run: the rule of IQ input, also with
+ * concurrency 2.  The tuner's factor 2 is in such rows (see FMD_CIQ_*): an external channeliser scales by 2. */
+#define FMD_IN_CIQ_F32 32
+#define FMD_IN_CIQ_S16 33
+
 /* Constructor arguments of cFmDecoder (FmDecode.h:110-116).  table_size / if_filter_order are
  * the two internal constants BASELINE configs 3 and 5 override; 0 selects the reference
  * values 64 (FmDecode.cpp:249) and 8*downsample (FmDecode.cpp:262). */
@@ -327,6 +361,9 @@ unsigned fmd_batch_channels(const fmd_batch* b);
 int fmd_batch_streams_sharing_queue(const fmd_batch* b);
 /* smallest `samples` a process call of this batch accepts (see FMD_MIN_BLOCK) */
 unsigned fmd_batch_min_samples(const fmd_batch* b);
+/* The baseband lengths M a call with channel IQ rows as input (FMD_IN_CIQ_*) may have: [*min, *max], multiples of
+ * *multiple (any pointer may be NULL).  FMD_ERR_ARG for a null batch. */
+int fmd_batch_baseband_limits(const fmd_batch* b, unsigned* min, unsigned* max, unsigned* multiple);
 unsigned fmd_batch_max_audio_floats(const fmd_batch* b, unsigned samples);
 /* multiplex samples per channel a call of `samples` delivers at most (see FMD_MPX_*): the bound for sizing rows */
 unsigned fmd_batch_max_mpx_samples(const fmd_batch* b, unsigned samples);
@@ -501,7 +538,8 @@ int fmd_batch_get_feed_selection(fmd_batch* b, unsigned* out, unsigned cap);
  *              stride  elements of the format between the rows (ciq: complex samples)
  *              count   (host, optional) elements per row the call wrote (ciq: complex samples)
  *   fmd_call   size    sizeof(fmd_call): anything else is FMD_ERR_ARG (a record of another version of this header)
- *              iq, iq_format, iq_channel_stride, samples: as in fmd_batch_process_device_pcm
+ *              iq, iq_format, iq_channel_stride, samples: as in fmd_batch_process_device_pcm; or channel IQ rows
+ *                      as the input, FMD_IN_CIQ_* (see there: stride in complex samples, samples = M)
  *              stream  hipStream_t of the device call, NULL = default stream; ignored by the other two
  * A record with ciq.p == NULL is fmd_batch_process_device_feed / _host_feed / fmd_process_stream_feed with the same
  * arguments: the same refusals in the same order, the same bits, the same launches, events and allocations.
@@ -957,6 +995,10 @@ int fmd_batch_debug_reset_keep_ring_phase(fmd_batch* b, int on);
  * in front of a call's frames stay what they were -- the first feed sample that reaches back over a call boundary is
  * then wrong.  An entry point of its own: the fmd_batch_debug_set key table is held to 14 keys. */
 int fmd_batch_debug_feed_skip_roll(fmd_batch* b, int on);
+/* Test aid (mutation test of FMD_IN_CIQ_*): the input copy leaves out every row's last tile. */
+int fmd_batch_debug_ciq_in_skip_tile(fmd_batch* b, int on);
+/* Test aid: out[i] = the host build of FMD_IN_CIQ_S16's conversion of in[i], (float)v * 2^-13; no device is touched. */
+int fmd_debug_ciq16_to_f32(const int16_t* in, unsigned n, float* out);
 
 const char* fmd_last_error(void);
 const char* fmd_version(void);

@@ -36,6 +36,9 @@ FEED_BYTES = {FMD_FEED_F32: 4, FMD_FEED_S16: 2}  # per feed sample
 # channel IQ formats (include/fmd.h FMD_CIQ_*): the `ciq.format` of a call record
 FMD_CIQ_F32, FMD_CIQ_S16 = 0, 1
 CIQ_BYTES = {FMD_CIQ_F32: 8, FMD_CIQ_S16: 4}  # per complex sample
+# channel IQ rows as a call's INPUT (include/fmd.h FMD_IN_CIQ_*): two more values of a call record's iq_format
+FMD_IN_CIQ_F32, FMD_IN_CIQ_S16 = 32, 33
+IN_CIQ_BYTES = {FMD_IN_CIQ_F32: 8, FMD_IN_CIQ_S16: 4}  # per complex sample
 
 TAPS = {"demod": 0, "baseband": 1, "pilot38": 2, "mono_rs": 3, "stereo_rs": 4, "rds_lpf": 5,
         "rds_pll": 6, "rds_mf": 7, "rds_sync": 8}
@@ -166,8 +169,40 @@ def make_rows(p=None, fmt=0, stride=0, count=None):
     return FmdRows(p, int(fmt), int(stride), C.pointer(count) if count is not None else None)
 
 
-def make_call(iq, iq_format, iq_stride, samples, audio=None, mpx=None, feed=None, ciq=None, stream=None):
-    """An FmdCall with its size filled in; audio / mpx / feed / ciq: FmdRows or None."""
+def ciq_in_of(rows):
+    """(pointer, FMD_IN_CIQ_* format, stride in complex samples, M) of channel IQ rows given as a call's input: a torch
+    tensor or numpy array of complex64 [C, M] / [M] (FMD_IN_CIQ_F32) or int16 [C, M, 2] / [M, 2] (re, im;
+    FMD_IN_CIQ_S16), the samples of a row contiguous.  The format is the dtype's; any other dtype or layout raises:
+    nothing is converted or copied silently."""
+    name = str(rows.dtype).replace("torch.", "")
+    fmt = {"complex64": FMD_IN_CIQ_F32, "int16": FMD_IN_CIQ_S16}.get(name)
+    if fmt is None:
+        raise FmdError(FMD_ERR_ARG_TEXT % ("no channel IQ input format for dtype %s (complex64, int16)" % name))
+    shape = tuple(int(v) for v in rows.shape)
+    nd = len(shape) - (1 if fmt == FMD_IN_CIQ_S16 else 0)
+    if nd not in (1, 2) or (fmt == FMD_IN_CIQ_S16 and shape[-1] != 2):
+        raise FmdError(FMD_ERR_ARG_TEXT % "channel IQ input rows are complex64 [C, M] or int16 [C, M, 2]")
+    if hasattr(rows, "data_ptr"):  # torch: strides in elements
+        ptr, strides = rows.data_ptr(), tuple(int(v) for v in rows.stride())
+    else:
+        ptr, strides = rows.ctypes.data, tuple(int(v) // rows.dtype.itemsize for v in rows.strides)
+    per = 2 if fmt == FMD_IN_CIQ_S16 else 1  # array elements per complex sample
+    if (fmt == FMD_IN_CIQ_S16 and strides[-1] != 1) or strides[nd - 1] != per or (nd == 2 and strides[0] % per):
+        raise FmdError(FMD_ERR_ARG_TEXT % "the samples of a channel IQ input row must be contiguous")
+    return ptr, fmt, (strides[0] // per if nd == 2 else 0), shape[nd - 1]
+
+
+def make_call(iq=None, iq_format=None, iq_stride=None, samples=None, audio=None, mpx=None, feed=None, ciq=None,
+              stream=None, ciq_in=None):
+    """An FmdCall with its size filled in; audio / mpx / feed / ciq: FmdRows or None.
+    ciq_in: channel IQ rows as the call's input (ciq_in_of: complex64 or int16 by dtype) in place of iq / iq_format /
+    iq_stride / samples -- a stride or a length given beside it wins.  The caller keeps the rows alive."""
+    if ciq_in is not None:
+        if iq is not None or iq_format is not None:
+            raise FmdError(FMD_ERR_ARG_TEXT % "a call takes iq or ciq_in, not both")
+        iq, iq_format, stride, m = ciq_in_of(ciq_in)
+        iq_stride = stride if iq_stride is None else iq_stride
+        samples = m if samples is None else samples
     call = FmdCall(size=C.sizeof(FmdCall), iq=iq, iq_format=int(iq_format), iq_channel_stride=int(iq_stride),
                    samples=int(samples), stream=stream)
     for name, rows in (("audio", audio), ("mpx", mpx), ("feed", feed), ("ciq", ciq)):
@@ -216,7 +251,8 @@ EXPORTS = [
     "fmd_batch_set_feed", "fmd_batch_get_feed", "fmd_batch_feed_rate", "fmd_batch_max_feed_samples",
     "fmd_batch_get_feed_taps", "fmd_batch_process_device_feed", "fmd_batch_process_host_feed",
     "fmd_process_stream_feed", "fmd_batch_select_feed", "fmd_batch_get_feed_selection",
-    "fmd_batch_debug_feed_skip_roll",
+    "fmd_batch_debug_feed_skip_roll", "fmd_batch_baseband_limits", "fmd_batch_debug_ciq_in_skip_tile",
+    "fmd_debug_ciq16_to_f32",
     "fmd_batch_process_device_call", "fmd_batch_process_host_call", "fmd_process_stream_call",
     "fmd_batch_select_ciq", "fmd_batch_get_ciq_selection",
     "fmd_batch_select_audio", "fmd_batch_select_mpx", "fmd_batch_get_audio_selection", "fmd_batch_get_mpx_selection",
@@ -389,6 +425,9 @@ def lib():
         L.fmd_batch_select_feed.argtypes = [vp, vp, u]
         L.fmd_batch_get_feed_selection.argtypes = [vp, vp, u]
         L.fmd_batch_debug_feed_skip_roll.argtypes = [vp, i]
+        L.fmd_batch_baseband_limits.argtypes = [vp, vp, vp, vp]
+        L.fmd_batch_debug_ciq_in_skip_tile.argtypes = [vp, i]
+        L.fmd_debug_ciq16_to_f32.argtypes = [vp, u, vp]
         L.fmd_batch_process_device_call.argtypes = [vp, C.POINTER(FmdCall)]
         L.fmd_batch_process_host_call.argtypes = [vp, C.POINTER(FmdCall)]
         L.fmd_process_stream_call.argtypes = [vp, C.POINTER(FmdCall)]
@@ -785,10 +824,62 @@ class Batch:
         n = _check(lib().fmd_batch_get_ciq_selection(self._h, out.ctypes.data, out.size))
         return out[:n].copy()
 
-    def process_call(self, call):
+    def process_call(self, call=None, ciq_in=None, **rows):
         """One device call from a call record (make_call; fmd_batch_process_device_call): the only way to the channel
-        IQ rows (call.ciq: FMD_CIQ_*, stride and count in complex samples)."""
+        IQ rows (call.ciq: FMD_CIQ_*, stride and count in complex samples) and to channel IQ rows as the input.
+        ciq_in: a device tensor of such rows (complex64 [C, M] or int16 [C, M, 2]: make_call's ciq_in) -- into the
+        record given, or into a new one of the keyword arguments (audio=, mpx=, feed=, ciq=, stream=)."""
+        if ciq_in is not None:
+            ptr, fmt, stride, m = ciq_in_of(ciq_in)
+            if call is None:
+                call = make_call(ciq_in=ciq_in, **rows)
+            else:
+                call.iq, call.iq_format, call.iq_channel_stride, call.samples = ptr, fmt, stride, m
         _check(lib().fmd_batch_process_device_call(self._h, C.byref(call)))
+
+    def baseband_limits(self):
+        """(min, max, multiple) of the baseband length M of a call with channel IQ rows as input
+        (fmd_batch_baseband_limits)."""
+        lo, hi, mult = C.c_uint(), C.c_uint(), C.c_uint()
+        _check(lib().fmd_batch_baseband_limits(self._h, C.byref(lo), C.byref(hi), C.byref(mult)))
+        return lo.value, hi.value, mult.value
+
+    def debug_ciq_in_skip_tile(self, on=True):
+        """Test aid: the input copy of FMD_IN_CIQ_* leaves out a tile (fmd_batch_debug_ciq_in_skip_tile)."""
+        _check(lib().fmd_batch_debug_ciq_in_skip_tile(self._h, int(on)))
+
+    def process_host_ciq_in(self, ciq_in, pcm=None, mpx=None, feed=None, ciq=None):
+        """One host call with channel IQ rows as the input (fmd_batch_process_host_call, FMD_IN_CIQ_*): ciq_in is
+        complex64 [C, M] or int16 [C, M, 2], any row stride.  Returns the audio, or a tuple of it and the multiplex,
+        feed and channel IQ rows asked for, as process_host_fmt does."""
+        ptr, fmt, stride, m = ciq_in_of(ciq_in)
+        pcm_fmt = pcm_format_of(pcm)
+        n = 65536  # (the largest block: its bounds hold for every baseband length a call may have)
+        a_stride, m_stride = self.max_audio_floats(n), max(m, 1)
+        audio = np.zeros((self._rows(), a_stride), dtype=np.int16 if pcm_fmt == FMD_PCM_S16 else np.float32)
+        nf, nm, nfeed, nq = C.c_uint(), C.c_uint(), C.c_uint(), C.c_uint()
+        call = make_call(ptr, fmt, stride, m, audio=make_rows(audio.ctypes.data, pcm_fmt, a_stride, nf))
+        out = []
+        if mpx is not None:
+            mpx_fmt = mpx_format_of(mpx)
+            rows = np.zeros((self._rows(mpx=True), m_stride), dtype=np.int16 if mpx_fmt == FMD_MPX_S16 else np.float32)
+            call.mpx = make_rows(rows.ctypes.data, mpx_fmt, m_stride, nm)
+            out.append((rows, nm, None))
+        if feed is not None:
+            feed_fmt = feed_format_of(feed)
+            f_stride = max(self.max_feed_samples(n), 1)
+            frows = np.zeros((max(self._rows(feed=True), 1), f_stride),
+                             dtype=np.int16 if feed_fmt == FMD_FEED_S16 else np.float32)
+            call.feed = make_rows(frows.ctypes.data, feed_fmt, f_stride, nfeed)
+            out.append((frows, nfeed, self._rows(feed=True)))
+        if ciq is not None:
+            ciq_fmt = ciq_format_of(ciq)
+            qrows = _ciq_rows(ciq_fmt, max(self._rows(ciq=True), 1), m_stride)
+            call.ciq = make_rows(qrows.ctypes.data, ciq_fmt, m_stride, nq)
+            out.append((qrows, nq, self._rows(ciq=True)))
+        _check(lib().fmd_batch_process_host_call(self._h, C.byref(call)))
+        res = (audio[:, :nf.value],) + tuple(r[:r.shape[0] if k is None else k, :c.value] for r, c, k in out)
+        return res[0] if len(res) == 1 else res
 
     def _rows(self, mpx=False, feed=False, ciq=False):
         if ciq:
@@ -1294,6 +1385,24 @@ class FmDecoder:
                          ciq=make_rows(rows.ctypes.data, ciq_fmt, 0, nq))
         n = _check(lib().fmd_process_stream_call(self._h, C.byref(call)))
         return audio[:n], rows[:nq.value]
+
+    def ProcessChannelIq(self, ciq_in, pcm=None, mpx=None):
+        """One call from the block's channel IQ, the samples behind the IF stage (FMD_IN_CIQ_*, fmd_process_stream_call):
+        ciq_in is complex64 [M] or int16 [M, 2] by dtype.  The audio (pcm=np.int16: FMD_PCM_S16); with mpx=np.float32 /
+        np.int16 also the multiplex, as ProcessStreamWithMpx returns it."""
+        ptr, fmt, _, m = ciq_in_of(ciq_in)
+        pcm_fmt = pcm_format_of(pcm)
+        # (the largest block's bound: it holds for every baseband length a call may have)
+        audio = np.empty(lib().fmd_batch_max_audio_floats(lib().fmd_decoder_batch(self._h), 65536),
+                         dtype=np.int16 if pcm_fmt == FMD_PCM_S16 else np.float32)
+        call = make_call(ptr, fmt, 0, m, audio=make_rows(audio.ctypes.data, pcm_fmt))
+        nm = C.c_uint()
+        if mpx is not None:
+            mpx_fmt = mpx_format_of(mpx)
+            rows = np.empty(max(m, 1), dtype=np.int16 if mpx_fmt == FMD_MPX_S16 else np.float32)
+            call.mpx = make_rows(rows.ctypes.data, mpx_fmt, 0, nm)
+        n = _check(lib().fmd_process_stream_call(self._h, C.byref(call)))
+        return audio[:n] if mpx is None else (audio[:n], rows[:nm.value])
 
     def ProcessStreamU8(self, buf):
         """ReadAsyncCB + ProcessStream (RTL_SDR_Source.cpp:196-213): buf = I,Q byte pairs."""

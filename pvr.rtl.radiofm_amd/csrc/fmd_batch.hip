@@ -3,7 +3,7 @@
  * per-call position plan (host) and the kernel sequence.  gfx950 only, no CPU fallback.
  *
  * Build (the Makefile): hipcc --offload-arch=gfx950 -O3 -ffp-contract=off -fPIC -shared fmd_batch.hip
- *                       fmd_split_real.hip -o libfmd_hip.so
+ *                       fmd_split_real.hip fmd_ciq_in.hip -o libfmd_hip.so
  */
 #include "../../include/fmd.h"
 
@@ -208,6 +208,18 @@ inline size_t real_format_esz(int format)
   return kFormats[FMT_IQ].esz[format & 3] / 2;
 }
 
+/* FMD_IN_CIQ_* (32 | FMD_CIQ_F32, _S16): channel IQ rows as a call's input, the samples behind the IF stage.  Only the
+ * _call entry points take them -- format_ok(FMT_IQ, ..) keeps refusing them everywhere else. */
+static_assert(FMD_IN_CIQ_F32 == (32 | FMD_CIQ_F32) && FMD_IN_CIQ_S16 == (32 | FMD_CIQ_S16),
+              "a channel-IQ input format is its output format with bit 5 set");
+inline bool ciq_in_format(int format)
+{
+  return format == FMD_IN_CIQ_F32 || format == FMD_IN_CIQ_S16;
+}
+const char* const kCiqInOnlyCall =
+    "FMD_IN_CIQ_F32 / _S16 (channel IQ rows as input) are taken by the _call entry points only "
+    "(fmd_batch_process_device_call, fmd_batch_process_host_call, fmd_process_stream_call)";
+
 /* Where a call delivers one of its outputs -- the audio, the multiplex (the _mpx entry points), the feed (the _feed
  * entry points), the channel IQ (the _call entry points; its elements are complex samples); p == null: nowhere -- the call launches what a call without the argument launches (and the feed's
  * frame count does not advance). */
@@ -237,9 +249,13 @@ struct Out
 struct Call
 {
   const void* iq = nullptr;
-  int iq_fmt = FMD_IQ_F32; // FMD_IQ_*
+  int iq_fmt = FMD_IQ_F32; // FMD_IQ_*; from a call record also FMD_IN_CIQ_*
   size_t iq_stride = 0;    // IQ samples between the input rows
-  unsigned samples = 0;
+  unsigned samples = 0;    // (FMD_IN_CIQ_*: the call's baseband length M)
+  bool from_record = false; // a _call entry point's: the only ones that take FMD_IN_CIQ_*
+  bool ciq_in() const { return ciq_in_format(iq_fmt); }
+  // bytes of an input sample
+  size_t in_esz() const { return ciq_in() ? format_esz(FMT_CIQ, iq_fmt & 1) : format_esz(FMT_IQ, iq_fmt); }
   Out audio{FMT_PCM}, mpx{FMT_MPX}, feed{FMT_FEED}, ciq{FMT_CIQ};
   void* stream = nullptr;
 };
@@ -440,6 +456,7 @@ struct fmd_batch
   Event feed_done;
   hipStream_t feed_stream = nullptr;
   int dbg_feed_skip_roll = 0;     // fmd_batch_debug_feed_skip_roll (mutation test): the history rows stay stale
+  int dbg_ciq_in_skip = 0;        // fmd_batch_debug_ciq_in_skip_tile (mutation test): the input copy's last tile is left out
   Selection sel_feed;             // which channels deliver feed rows (fmd_batch_select_feed): the multiplex's form
   DevBuf<float> h_feed;           // staging of the host-buffer call's feed rows (sized on first use)
   /* The channel IQ (the _call entry points): demod[q]'s rows as an output.  It has no state
@@ -630,6 +647,18 @@ inline bool is_shell(const fmd_batch* b)
 inline bool audio_rows_due(const fmd_batch* b)
 {
   return !(b->sel_audio.on && b->sel_audio.n_total == 0);
+}
+
+/* The baseband lengths a call with channel IQ rows as input may have (fmd_batch_baseband_limits): those an IQ call
+ * can produce -- from the smallest call's (fmd_batch_min_samples / D, in every decimator phase) to the largest
+ * block's, D samples apart each. */
+inline unsigned baseband_min(const fmd_batch* b)
+{
+  return b->min_samples / b->des.D;
+}
+inline unsigned baseband_max(const fmd_batch* b)
+{
+  return b->Mmax - 1; // (Mmax: one more than the decimator's outputs of the largest block, fmd_batch_create)
 }
 
 /* the sub-batch that owns a channel, and the channel's index there (a plain batch: itself) */
@@ -1518,6 +1547,25 @@ unsigned fmd_batch_min_samples(const fmd_batch* b)
   return b ? b->min_samples : 0;
 }
 
+int fmd_batch_baseband_limits(const fmd_batch* b, unsigned* min, unsigned* max, unsigned* multiple)
+{
+  if (!b)
+    return fail(FMD_ERR_ARG, "fmd_batch_baseband_limits: null batch");
+  if (min)
+    *min = baseband_min(b);
+  if (max)
+    *max = baseband_max(b);
+  if (multiple)
+  { // every CIC stage of the RDS decimator halves an even block (plan_call: the reference reads past an odd one)
+    unsigned m = 1;
+    for (const auto& h : b->des.hb)
+      if (h.cic)
+        m *= 2;
+    *multiple = m;
+  }
+  return FMD_OK;
+}
+
 unsigned fmd_batch_max_mpx_samples(const fmd_batch* b, unsigned samples)
 {
   // the decimator's outputs of a block, with its phase at 0 (DownConvert.cpp:112,123)
@@ -1972,6 +2020,8 @@ static int process_any(fmd_batch* b, const Call& c)
   Call t;
   t.iq = b->twin_iq.p;
   t.samples = c.samples;
+  if (c.ciq_in()) // (the twin takes the call's kind: M float pairs of the same zeros, every channel the one row)
+    t.iq_fmt = FMD_IN_CIQ_F32;
   t.audio.p = b->twin_audio.p;
   t.audio.stride = b->twin_audio.n;
   t.stream = c.stream;
@@ -1996,8 +2046,9 @@ static int process_shell(fmd_batch* b, const Call& c)
     sb->sched_prev2 = b->vheavy[1];
     Call sc = c;
     // (a capture map: every sub-batch takes the first row, its walk names the rows it reads)
-    const size_t row0 = b->map_on ? 0 : ch0 / b->cpc;
-    sc.iq = static_cast<const char*>(c.iq) + row0 * c.iq_stride * format_esz(FMT_IQ, c.iq_fmt);
+    // (channel IQ rows: one per channel whatever the map)
+    const size_t row0 = c.ciq_in() ? ch0 : b->map_on ? 0 : ch0 / b->cpc;
+    sc.iq = static_cast<const char*>(c.iq) + row0 * c.iq_stride * c.in_esz();
     // (the sub-batch's first row of every output; every sub-batch counts the feed's frames for itself)
     sc.audio = c.audio.from_channel(ch0, b->sel_audio.on);
     sc.audio.out = &nf;
@@ -2064,8 +2115,12 @@ static int check_call_args(const char* who, CallWay way, fmd_batch* b, Call& c)
     *c.feed.out = 0;
   if (!format_ok(FMT_MPX, c.mpx.fmt))
     return refuse(FMD_ERR_ARG, kFormats[FMT_MPX].must);
-  if (!format_ok(FMT_IQ, c.iq_fmt))
-    return refuse(FMD_ERR_ARG, kFormats[FMT_IQ].must);
+  if (ciq_in_format(c.iq_fmt) && !c.from_record)
+    return refuse(FMD_ERR_ARG, kCiqInOnlyCall);
+  if (!format_ok(FMT_IQ, c.iq_fmt) && !c.ciq_in())
+    return refuse(FMD_ERR_ARG, c.from_record ? "iq_format must be one of FMD_IQ_F32, _U8, _S8, _S16 (0..3) or "
+                                               "FMD_IN_CIQ_F32, _S16 (32, 33)"
+                                             : kFormats[FMT_IQ].must);
   if (!format_ok(FMT_PCM, c.audio.fmt))
     return refuse(FMD_ERR_ARG, kFormats[FMT_PCM].must);
   if (way == WAY_FORMATS)
@@ -2075,11 +2130,19 @@ static int check_call_args(const char* who, CallWay way, fmd_batch* b, Call& c)
   if (dev && c.feed.p && !c.feed.rows_aligned())
     return refuse(FMD_ERR_ARG, "the feed pointer must be 16-byte aligned and feed_channel_stride a multiple of 4 "
                                "(FMD_FEED_F32) / 8 (FMD_FEED_S16) elements");
+  // channel IQ rows as input: a lane loads 16 bytes of a row at a time, the rule of the ciq output's rows
+  if (dev && c.ciq_in() && c.iq && ((reinterpret_cast<uintptr_t>(c.iq) % 16) || (c.iq_stride * c.in_esz()) % 16))
+    return refuse(FMD_ERR_ARG, "with FMD_IN_CIQ_* the iq pointer must be 16-byte aligned and iq_channel_stride a "
+                               "multiple of 2 (FMD_IN_CIQ_F32) / 4 (FMD_IN_CIQ_S16) complex samples");
   // (a device call's other null arguments get their own sentence further down)
   if (!b || (!dev && (!c.iq || (!c.audio.p && audio_rows_due(b)))))
     return refuse(FMD_ERR_ARG, "null argument");
   if (c.feed.p && !b->feed_div)
     return refuse(FMD_ERR_STATE, "a feed pointer while the feed is off (fmd_batch_set_feed turns it on)");
+  // ... one row per channel, `samples` = M complex samples each
+  if (c.ciq_in() && b->C > 1 && c.iq_stride < c.samples)
+    return refuse(FMD_ERR_ARG, "with FMD_IN_CIQ_* iq_channel_stride must be at least samples, the call's baseband "
+                               "length: one row per channel");
   // four 16-bit frames go out as one 16-byte store: every row has to start on a 16-byte boundary
   if (dev && c.audio.fmt == FMD_PCM_S16 && c.iq && c.audio.p && !c.audio.rows_aligned())
     return refuse(FMD_ERR_ARG, "for FMD_PCM_S16 the audio pointer must be 16-byte aligned and audio_channel_stride a "
@@ -2098,9 +2161,8 @@ static int check_call_args(const char* who, CallWay way, fmd_batch* b, Call& c)
     return FMD_OK;
   // the rows hold the call's samples -- looked at here, in front of the pending channel edits: a refused call leaves
   // the batch as it was (a call refused for its size has no samples: check_call has the sentence)
-  const fmd_batch* x = b->subs.empty() ? b : b->subs[0].get();
   fmd::CallPlan pl;
-  (void)fmd::plan_call(x->des, x->if_pos, x->rs_pos, x->feed_g, b->feed_div, c.samples, pl);
+  (void)plan_of_call(b, c, pl);
   if (c.mpx.p && dev && !c.mpx.rows_aligned())
     return refuse(FMD_ERR_ARG, "the multiplex pointer must be 16-byte aligned and mpx_channel_stride a multiple of 4 "
                                "(FMD_MPX_F32) / 8 (FMD_MPX_S16) elements");
@@ -2176,6 +2238,7 @@ static int call_of_record(const char* who, const fmd_call* r, Call& c)
   c.feed = rows(FMT_FEED, r->feed);
   c.ciq = rows(FMT_CIQ, r->ciq);
   c.stream = r->stream;
+  c.from_record = true;
   return FMD_OK;
 }
 
@@ -2800,6 +2863,15 @@ int fmd_batch_get_feed_taps(const fmd_batch* b, float* out, unsigned cap)
   return int(b->feed_taps_h.size());
 }
 
+int fmd_batch_debug_ciq_in_skip_tile(fmd_batch* b, int on)
+{
+  if (!b)
+    return fail(FMD_ERR_ARG, "null batch");
+  for (fmd_batch* x : buffer_batches(b))
+    x->dbg_ciq_in_skip = on != 0;
+  return FMD_OK;
+}
+
 int fmd_batch_debug_feed_skip_roll(fmd_batch* b, int on)
 {
   if (!b)
@@ -3057,7 +3129,9 @@ struct StagedOut
 static int process_host_impl(fmd_batch* b, const Call& c)
 {
   HIPCHK(hipSetDevice(b->device));
-  const unsigned C = b->C, samples = c.samples;
+  const unsigned C = b->C;
+  // (channel IQ rows as input: the capture samples whose bounds hold for a call of this baseband length)
+  const unsigned samples = c.ciq_in() ? std::min(c.samples, baseband_max(b)) * b->des.D : c.samples;
   // the outputs' staging -- audio; multiplex, feed and channel IQ where the call has them (the feed's rows one
   // element longer than fmd_batch_max_feed_samples)
   Call d = c;
@@ -3084,12 +3158,13 @@ static int process_host_impl(fmd_batch* b, const Call& c)
       return rc;
     d.ciq = sc.dev;
   }
-  const size_t esz = format_esz(FMT_IQ, c.iq_fmt); // bytes per IQ sample
-  // device copy: one row per channel, rows padded to a whole pair of samples
-  const size_t dev_row = (size_t(samples) + 1) / 2 * 2 * esz;
+  const size_t esz = c.in_esz(); // bytes per input sample
+  const unsigned n_in = c.samples;
+  // device copy: one row per channel, rows padded to a whole pair of samples (channel IQ rows: to 16 bytes)
+  const size_t dev_row = c.ciq_in() ? (size_t(n_in) * esz + 15) / 16 * 16 : (size_t(n_in) + 1) / 2 * 2 * esz;
   d.iq_stride = c.iq_stride ? dev_row / esz : 0;
   // input rows: one per capture of the map, per channel, per cpc channels, or one
-  const unsigned streams = !c.iq_stride ? 1u : b->map_on ? b->n_cap : C / b->cpc;
+  const unsigned streams = !c.iq_stride ? 1u : c.ciq_in() ? C : b->map_on ? b->n_cap : C / b->cpc;
   const size_t iq_floats = (dev_row * streams + 3) / 4;
   if (iq_floats > b->h_iq.n && b->h_iq.alloc(iq_floats))
     return fail(FMD_ERR_DEVICE, "staging allocation failed");
@@ -3098,10 +3173,10 @@ static int process_host_impl(fmd_batch* b, const Call& c)
   auto ms_since = [](clk::time_point t) { return std::chrono::duration<double, std::milli>(clk::now() - t).count(); };
   clk::time_point tp = clk::now();
   if (c.iq_stride)
-    HIPCHK(hipMemcpy2D(b->h_iq.p, dev_row, c.iq, c.iq_stride * esz, size_t(samples) * esz, streams,
+    HIPCHK(hipMemcpy2D(b->h_iq.p, dev_row, c.iq, c.iq_stride * esz, size_t(n_in) * esz, streams,
                        hipMemcpyHostToDevice));
   else
-    HIPCHK(hipMemcpy(b->h_iq.p, c.iq, size_t(samples) * esz, hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(b->h_iq.p, c.iq, size_t(n_in) * esz, hipMemcpyHostToDevice));
   b->host_ms[0] += ms_since(tp);
   tp = clk::now();
   int rc = process_any(b, d);
@@ -3808,6 +3883,16 @@ fmd_batch* fmd_decoder_batch(fmd_decoder* d)
 int fmd_get_status(fmd_decoder* d, fmd_status* st)
 {
   return d ? fmd_batch_get_status(d->b, 0, st) : fail(FMD_ERR_ARG, "null decoder");
+}
+
+/* Test aid: the host build of fmd_ciq16_to_f32 (FMD_IN_CIQ_S16) on an array; no device is touched. */
+int fmd_debug_ciq16_to_f32(const int16_t* in, unsigned n, float* out)
+{
+  if (!in || !out)
+    return fail(FMD_ERR_ARG, "fmd_debug_ciq16_to_f32: null argument");
+  for (unsigned i = 0; i < n; i++)
+    out[i] = fmd_ciq16_to_f32(in[i]);
+  return FMD_OK;
 }
 
 /* Test aid, see k_debug_math.  Host arrays in and out; b may be NULL for one-argument functions. */

@@ -496,6 +496,16 @@ void launch_ciq(fmd_batch* b, const Out& o, int q, unsigned M, hipStream_t s)
       });
 }
 
+/* The position plan of call c from the positions of the batch (a shell: of its first sub-batch -- they all have the
+ * same geometry and the same positions): of its samples, or, with channel IQ rows as input, of its baseband length. */
+int plan_of_call(const fmd_batch* b, const Call& c, fmd::CallPlan& pl)
+{
+  const fmd_batch* x = b->subs.empty() ? b : b->subs[0].get();
+  if (c.ciq_in())
+    return fmd::plan_call_baseband(x->des, x->rs_pos, x->feed_g, b->feed_div, c.samples, pl);
+  return fmd::plan_call(x->des, x->if_pos, x->rs_pos, x->feed_g, b->feed_div, c.samples, pl);
+}
+
 /* Everything that refuses a call, looked at before anything of it is submitted: a refused call leaves the batch as
  * it was, its pending channel edits included.  pl: the call's plan, from the positions of the batch (a shell: of its
  * first sub-batch -- they all have the same geometry and the same positions). */
@@ -503,10 +513,29 @@ int check_call(fmd_batch* b, const Call& c, fmd::CallPlan& pl)
 {
   if (!b || !c.iq || (!c.audio.p && audio_rows_due(b)))
     return fail(FMD_ERR_ARG, "fmd_batch_process_device: null argument");
-  if (c.samples > FMD_MAX_BLOCK || c.samples < b->min_samples)
+  if (c.ciq_in() && !fmd::ciq_in_launch) // (never in the library: fmd_k_ciq_in.hip.h)
+    return fail(FMD_ERR_DEVICE, "the channel IQ input's kernels (fmd_ciq_in.o) are not linked into this program");
+  if (c.ciq_in())
+  { // (the plan's own refusals first: they are the sentences of an IQ call that would produce this length)
+    if (c.samples > baseband_max(b))
+      return fail(FMD_ERR_SIZE, "samples (the baseband length of a call with channel IQ rows as input) above the "
+                                "batch's largest, fmd_batch_baseband_limits: " + std::to_string(baseband_max(b)));
+    if (plan_of_call(b, c, pl) != FMD_OK)
+      return fail(FMD_ERR_SIZE, pl.why);
+    if (c.samples < baseband_min(b))
+      return fail(FMD_ERR_SIZE, "samples (the baseband length of a call with channel IQ rows as input) must be within "
+                                "fmd_batch_baseband_limits = [" + std::to_string(baseband_min(b)) + ", " +
+                                    std::to_string(baseband_max(b)) + "]");
+    // a lane loads 16 bytes of a row at a time: every row has to start on a 16-byte boundary
+    if ((reinterpret_cast<uintptr_t>(c.iq) % 16) || (c.iq_stride * c.in_esz()) % 16)
+      return fail(FMD_ERR_ARG, "with FMD_IN_CIQ_* the iq pointer must be 16-byte aligned and iq_channel_stride a "
+                               "multiple of 2 (FMD_IN_CIQ_F32) / 4 (FMD_IN_CIQ_S16) complex samples");
+  }
+  else if (c.samples > FMD_MAX_BLOCK || c.samples < b->min_samples)
     return fail(FMD_ERR_SIZE, "samples must be within [fmd_batch_min_samples(), the largest block] = [" +
                                   std::to_string(b->min_samples) + ", 65536]");
   // a lane loads two IQ samples at a time: every channel's stream has to start on a pair boundary
+  if (!c.ciq_in())
   {
     const size_t pair = 2 * format_esz(FMT_IQ, c.iq_fmt);
     if ((reinterpret_cast<uintptr_t>(c.iq) % pair) || ((c.iq_stride * (pair / 2)) % pair))
@@ -516,8 +545,7 @@ int check_call(fmd_batch* b, const Call& c, fmd::CallPlan& pl)
   if (int rc = check_device_errors(b)) // a failed batch takes no more calls (fmd_batch_reset clears it)
     return rc;
   /* ---- position plan (batch-uniform, mirrors the reference's bookkeeping) ---- */
-  const fmd_batch* x = b->subs.empty() ? b : b->subs[0].get();
-  if (fmd::plan_call(x->des, x->if_pos, x->rs_pos, x->feed_g, b->feed_div, c.samples, pl) != FMD_OK)
+  if (plan_of_call(b, c, pl) != FMD_OK)
     return fail(FMD_ERR_SIZE, pl.why);
   if (pl.A > b->Amax || pl.M > b->Mmax)
     return fail(FMD_ERR_STATE, "internal: plan exceeds buffer geometry");
@@ -658,6 +686,21 @@ int stage_if(Submit& x)
   };
   if (!(x.stage_mask & 1u))
   { // (energy experiment: this call leaves the IF stage out -- see "stage_mask")
+    markfn(1);
+    return FMD_OK;
+  }
+  if (x.c.ciq_in())
+  { // channel IQ rows as input: the copy into demod[q] is the whole stage -- no tuner, no FIR, no level meter, and the
+    // stage's carried state (history, tuner phase, decimator phase) is not touched (commit_call).  The profiling
+    // events of the FIR kernel take the copy's start and stop: the stage-time getter reports it in the IF stage's slot.
+    const bool s16 = x.c.iq_fmt == FMD_IN_CIQ_S16;
+    const unsigned per = fmd::CIQ_G * (s16 ? fmd::InCiqS16::PER : fmd::InCiqF32::PER); // samples of a workgroup
+    // (fmd_batch_debug_ciq_in_skip_tile, a mutation test's: every row's last tile is left out)
+    const unsigned tiles = (x.M + per - 1) / per - (x.b->dbg_ciq_in_skip ? 1u : 0u);
+    const hipEvent_t t0 = x.evset ? x.evset[0].e : nullptr, t1 = x.evset ? x.evset[1].e : nullptr;
+    markfn(0);
+    if (tiles) // (the kernels' own object: fmd_ciq_in.hip)
+      fmd::ciq_in_launch(s16, x.C, tiles, x.sF, t0, t1, x.c.iq, x.c.iq_stride, x.M, x.b->demod[x.q].p, x.b->Mstride);
     markfn(1);
     return FMD_OK;
   }
@@ -1171,8 +1214,12 @@ void commit_call(Submit& x)
   b->slot_call[x.es] = x.ci;
   if (x.evset)
     b->prof_calls++;
-  b->if_pos = pl.if_pos;                                      // DownConvert.cpp:132
-  b->lut_idx = (b->lut_idx + c.samples) % x.d.table_size;     // FmDecode.cpp:81
+  if (!c.ciq_in())
+  { // (channel IQ rows as input: the IF stage did not run -- its decimator phase, tuner phase and history stay)
+    b->if_pos = pl.if_pos;                                    // DownConvert.cpp:132
+    b->lut_idx = (b->lut_idx + c.samples) % x.d.table_size;   // FmDecode.cpp:81
+    b->hist_sel ^= 1;
+  }
   b->rs_pos = pl.rs_pos;                                      // DownConvert.cpp:230-232
   b->osc_re = x.osc_re;                                       // DownConvert.cpp:440-441 (batch-wide, see osc_on)
   b->osc_im = x.osc_im;
@@ -1180,7 +1227,6 @@ void commit_call(Submit& x)
   b->rds_lpf_g = (b->rds_lpf_g + x.R) % x.T_lpf;
   b->mf_g = (b->mf_g + x.R) % x.T_mf;
   b->alpf_g = (b->alpf_g + x.A) % x.T_alp;
-  b->hist_sel ^= 1;
   b->lastM = x.M;
   b->lastA = x.A;
   b->lastR = x.R;

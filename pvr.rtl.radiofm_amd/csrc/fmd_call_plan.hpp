@@ -43,20 +43,17 @@ inline unsigned feed_samples_of(uint64_t g0, unsigned A, unsigned D, unsigned* p
   return unsigned((g0 + A + D - 1) / D - first);
 }
 
-/* The plan of a call of `samples` at decimator phase if_pos and resampler position rs_pos; feed_div != 0: behind
- * feed_g frames of feed calls.  FMD_OK, or FMD_ERR_SIZE with the sentence in pl.why.  M, A and the feed's counts are
- * the call's whether or not it is refused (0 where no sample gets that far): a stride check in front of the refusal
- * reads them. */
-inline int plan_call(const Design& d, unsigned if_pos, float rs_pos, uint64_t feed_g, unsigned feed_div,
-                     unsigned samples, CallPlan& pl)
+/* What both kinds of call share: the plan of a call of baseband length M at resampler position rs_pos -- everything
+ * behind the IF stage depends on the input through M alone.  m_long: the length the reference's half-band buffers are
+ * tested against; m0_why: the refusal of M == 0.  if_pos is the caller's to set behind FMD_OK. */
+inline int plan_baseband_body(const Design& d, float rs_pos, uint64_t feed_g, unsigned feed_div, unsigned M,
+                              unsigned m_long, const char* m0_why, CallPlan& pl)
 {
-  const unsigned N = samples, D = d.D;
   auto refuse = [&](const char* why) {
     pl.why = why;
     return int(FMD_ERR_SIZE);
   };
   pl = CallPlan();
-  const unsigned M = if_pos < N ? (N - if_pos + D - 1) / D : 0; // DownConvert.cpp:112,123
   pl.M = M;
   // fractional resampler walk (DownConvert.cpp:203-232), float arithmetic as written there
   const float p = rs_pos;
@@ -79,10 +76,10 @@ inline int plan_call(const Design& d, unsigned if_pos, float rs_pos, uint64_t fe
     pl.feed_n = feed_samples_of(feed_g, A, feed_div, &pl.feed_p0);
 
   if (M == 0)
-    return refuse("block shorter than the decimator phase");
+    return refuse(m0_why);
   // the reference's half-band delay lines hold 32768 samples (DownConvert.cpp:267,500); longer
   // baseband blocks overrun its heap, so they are outside the contract here too
-  if ((N + D - 1) / D + 51 > 32768)
+  if (m_long + 51 > 32768)
     return refuse("baseband block longer than the reference's half-band buffers (32768)");
   unsigned R = M;
   for (size_t s = 0; s < d.hb.size() && s < kMaxHbStages; s++)
@@ -119,8 +116,33 @@ inline int plan_call(const Design& d, unsigned if_pos, float rs_pos, uint64_t fe
     return refuse("block too short: no sample reaches the RDS rate");
   if (A == 0)
     return refuse("block too short: no audio frame falls into it");
-  pl.if_pos = if_pos + M * D - N; // DownConvert.cpp:132
   return FMD_OK;
+}
+
+/* The plan of a call of `samples` at decimator phase if_pos and resampler position rs_pos; feed_div != 0: behind
+ * feed_g frames of feed calls.  FMD_OK, or FMD_ERR_SIZE with the sentence in pl.why.  M, A and the feed's counts are
+ * the call's whether or not it is refused (0 where no sample gets that far): a stride check in front of the refusal
+ * reads them. */
+inline int plan_call(const Design& d, unsigned if_pos, float rs_pos, uint64_t feed_g, unsigned feed_div,
+                     unsigned samples, CallPlan& pl)
+{
+  const unsigned N = samples, D = d.D;
+  const unsigned M = if_pos < N ? (N - if_pos + D - 1) / D : 0; // DownConvert.cpp:112,123
+  const int rc = plan_baseband_body(d, rs_pos, feed_g, feed_div, M, (N + D - 1) / D,
+                                    "block shorter than the decimator phase", pl);
+  if (rc == FMD_OK)
+    pl.if_pos = if_pos + M * D - N; // DownConvert.cpp:132
+  return rc;
+}
+
+/* The plan of a call that brings its baseband itself (FMD_IN_CIQ_*: M complex samples per channel, the IF stage does
+ * not run): M, R, A, the half-band regimes, rs_pos and the feed's counts are those of an IQ call that produces M
+ * baseband samples, with the same refusal sentences; the decimator phase is not the call's (pl.if_pos stays 0: the
+ * caller keeps its own). */
+inline int plan_call_baseband(const Design& d, float rs_pos, uint64_t feed_g, unsigned feed_div, unsigned M,
+                              CallPlan& pl)
+{
+  return plan_baseband_body(d, rs_pos, feed_g, feed_div, M, M, "a call of no baseband samples", pl);
 }
 
 } // namespace fmd

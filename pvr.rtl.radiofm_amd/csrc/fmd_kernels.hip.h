@@ -28,6 +28,7 @@
 #include "fmd_k_mpx.hip.h"
 #include "fmd_k_feed.hip.h"
 #include "fmd_k_ciq.hip.h"
+#include "fmd_k_ciq_in.hip.h"
 #include "fmd_k_restart.hip.h"
 #include "fmd_k_state.hip.h"
 #include "fmd_k_scan.hip.h"

@@ -136,6 +136,13 @@ FMD_HD float fmd_s16_to_f32(int v)
   return (float)v * 0x1p-15f;
 }
 
+/* Channel IQ rows of 16-bit integers as an input (FMD_IN_CIQ_S16): v * 2^-13, the inverse scale of FMD_CIQ_S16
+ * (fmd_f32_to_mpx16 multiplies by 8192); full scale is [-4, 4).  Exact, like the two above. */
+FMD_HD float fmd_ciq16_to_f32(int v)
+{
+  return (float)v * 0x1p-13f;
+}
+
 /* Audio sample -> signed 16-bit PCM (FMD_PCM_S16): saturate(round_half_even(x * 2^15)), NaN gives 0.  x * 2^15 is
  * exact short of overflow (then +-inf, which saturates), rintf rounds to nearest even in the default rounding mode on
  * the host and is v_rndne_f32 on the device, and the clamp is done on the rounded FLOAT: the cast sees an integer in
