@@ -16,7 +16,6 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
-#include <deque>
 #include <functional>
 #include <map>
 #include <memory>
@@ -142,6 +141,80 @@ struct Event
   operator hipEvent_t() const { return e; }
 };
 
+/* The record queues of a batch with buffers of its own, one per event slot (a call appends to queue[call_index %
+ * kSlots] and to nothing else), as the group queues and the block queues both are: the device queues of `cap` records
+ * (PER elements of T each), their counts -- contiguous, one copy reads them all --, and the page-locked staging a
+ * drain reads them into: the counts and the records arrive by DMA, no staging kernel.  A drain (drain_queues) names
+ * the slots it visits in todo[], then takes the two steps between which the caller synchronises the stream. */
+constexpr int kSlots = 8;
+template <typename T, unsigned PER>
+struct SlotQueues
+{
+  DevBuf<T> queue[kSlots]; // never drained while a call that appends to it is in flight
+  DevBuf<unsigned> counts;
+  HostBuf<unsigned> h_counts;
+  HostBuf<T> h_recs;
+  unsigned cap = 0;
+  // one drain's: the slots it visits, what it takes from each, their sum, and what the queues could not hold
+  int todo[kSlots] = {}, ntodo = 0;
+  unsigned cnt[kSlots] = {};
+  size_t total = 0;
+  uint64_t over = 0;
+
+  unsigned* count(int slot) const { return counts.p + slot; }
+  // (two steps, each family in the order it always allocated in: the trace test sees the memsets)
+  int alloc_counts() { return counts.alloc(kSlots) | h_counts.alloc(kSlots); }
+  int alloc_queues(unsigned records)
+  {
+    int bad = 0;
+    for (int q = 0; q < kSlots && !bad; q++)
+      bad |= queue[q].alloc(size_t(PER) * records);
+    cap = bad ? 0 : records;
+    return bad;
+  }
+  void release()
+  {
+    for (auto& q : queue)
+      q.release();
+    counts.release();
+    h_counts.release();
+    cap = 0;
+  }
+  // step 1: the counts on their way to the host (todo[] is the caller's: it knows which slots are due)
+  hipError_t fetch_counts(hipStream_t stream)
+  {
+    return ntodo ? hipMemcpyAsync(h_counts.p, counts.p, kSlots * sizeof(unsigned), hipMemcpyDeviceToHost, stream)
+                 : hipSuccess;
+  }
+  // step 2 (the counts have arrived): the non-empty queues' first `cap` records back to back into h_recs -- grown to
+  // hold at least `grow` records --, their counts cleared.  -1: the staging could not grow.
+  int fetch_records(size_t grow, hipStream_t stream)
+  {
+    total = 0;
+    over = 0;
+    for (int i = 0; i < ntodo; i++)
+    {
+      const unsigned n = h_counts.p[todo[i]];
+      cnt[i] = std::min(n, cap);
+      over += n - cnt[i];
+      total += cnt[i];
+    }
+    if (PER * total > h_recs.n && h_recs.alloc(PER * std::max(total, grow)))
+      return -1;
+    size_t at = 0;
+    for (int i = 0; i < ntodo; i++)
+      if (cnt[i])
+      {
+        if (hipMemcpyAsync(h_recs.p + PER * at, queue[todo[i]].p, size_t(cnt[i]) * PER * sizeof(T), hipMemcpyDeviceToHost,
+                           stream) != hipSuccess ||
+            hipMemsetAsync(count(todo[i]), 0, sizeof(unsigned), stream) != hipSuccess)
+          return -2;
+        at += cnt[i];
+      }
+    return 0;
+  }
+};
+
 /* One launch of a kernel the profiler can time: with ev_start, hipExtLaunchKernelGGL records ev_start / ev_stop at
  * the kernel's own start and stop (a recorded event would also count the dispatch gap behind it); without, a plain
  * launch.  Every argument is converted to the kernel's parameter type. */
@@ -169,7 +242,9 @@ static_assert(IQ_F32 == FMD_IQ_F32 && IQ_U8 == FMD_IQ_U8 && IQ_S8 == FMD_IQ_S8 &
 /* The format arguments of the C ABI (FMD_IQ_*, FMD_PCM_*, FMD_MPX_*, FMD_FEED_*, FMD_CIQ_*): the values each takes
  * (0 .. last), the bytes of an element -- an IQ sample, one audio, multiplex or feed sample, a complex sample of the
  * channel IQ -- and what a refusal says. */
-enum FormatKind { FMT_IQ, FMT_PCM, FMT_MPX, FMT_FEED, FMT_CIQ };
+enum FormatKind { FMT_IQ, FMT_PCM, FMT_MPX, FMT_FEED, FMT_CIQ, FMT_KINDS };
+/* a call's four outputs (what fmd_batch::sel and Call::kOut are indexed by) */
+constexpr FormatKind kOutKinds[4] = {FMT_PCM, FMT_MPX, FMT_FEED, FMT_CIQ};
 struct FormatInfo
 {
   int last;
@@ -258,6 +333,9 @@ struct Call
   size_t in_esz() const { return ciq_in() ? format_esz(FMT_CIQ, iq_fmt & 1) : format_esz(FMT_IQ, iq_fmt); }
   Out audio{FMT_PCM}, mpx{FMT_MPX}, feed{FMT_FEED}, ciq{FMT_CIQ};
   void* stream = nullptr;
+  static constexpr Out Call::* kOut[FMT_KINDS] = {nullptr, &Call::audio, &Call::mpx, &Call::feed, &Call::ciq};
+  Out& out(FormatKind k) { return this->*kOut[k]; }
+  const Out& out(FormatKind k) const { return this->*kOut[k]; }
 };
 
 } // namespace
@@ -272,7 +350,7 @@ struct fmd_batch
   void* user = nullptr;
   std::vector<int> shifts;
 
-  static constexpr int NSLOT = 8; // event sets, RDS queues and staging slots in rotation (call_index % NSLOT)
+  static constexpr int NSLOT = kSlots; // event sets, RDS queues and staging slots in rotation (call_index % NSLOT)
 
   // host-tracked, batch-uniform positions
   unsigned if_pos = 0;     // cDownsampleFilter::m_pos_int
@@ -361,35 +439,23 @@ struct fmd_batch
   DevBuf<float> fstate; // all float state arrays, CP each
   DevBuf<int> istate;
   DevBuf<uint16_t> r_data;
-  DevBuf<fmd::RdsGroupRec> queue[NSLOT]; // never drained while a call that appends to it is in flight
-  DevBuf<unsigned> queue_counts; // [NSLOT], contiguous: one copy reads them all
-  unsigned* qcount(int q) const { return queue_counts.p + q; }
+  SlotQueues<fmd::RdsGroupRec, 1> groups; // the RDS groups of the calls (fmd_batch_collect_rds / _export_rds_device)
   // call whose groups were last taken out of the slot's queue (collect / export): a slot is not
   // visited again before a newer call has used it
   uint32_t drained_call[NSLOT] = {};
-  // page-locked staging of fmd_batch_collect_rds: the counts and the records arrive by DMA, no
-  // staging kernel, two synchronisations per collect
-  HostBuf<unsigned> h_counts;
-  HostBuf<fmd::RdsGroupRec> h_recs;
-  unsigned queue_cap = 0;
   /* The block observation (fmd_batch_set_rds_blocks).  The mode is the caller-facing batch's
    * and every sub-batch's next call's; a call reads it when it is submitted.  Nothing of this exists on the device
    * until the first call of fmd_batch_set_rds_blocks that enables a mode: then the counters ([RQ_N][CP], zero, and
    * from there on touched by nothing but the observing kernels), and with the first mode 2 the block queues -- one
-   * per event slot like the group queues, with counts, staging and drained bookkeeping of their own: the two drains
-   * are independent. */
+   * per event slot like the group queues, with drained bookkeeping of their own: the two drains are independent. */
   int rb_mode = 0;
-  unsigned rb_cap = 0;                 // records per block queue, fixed by the first mode 2
   DevBuf<unsigned> rb_quality;         // [RQ_N][CP]
-  DevBuf<uint4> rb_queue[NSLOT];       // two uint4 per record
-  DevBuf<unsigned> rb_counts;          // [NSLOT]
+  SlotQueues<uint4, 2> blocks;         // two uint4 per record; blocks.cap is fixed by the first mode 2
   // A mode-2 call has used the slot's queue since it was last drained.  A slot's age is its NEWEST call's
   // (slot_call), whatever that call's mode: records left in a queue for NSLOT calls or more are delivered once the
   // call that has since reused the slot is `lag` calls old -- later than their own call's age would allow, never
   // earlier than a call that may still append.  Collecting at least every NSLOT calls never meets this.
   bool rb_dirty[NSLOT] = {};
-  HostBuf<unsigned> rb_h_counts;
-  HostBuf<uint4> rb_h_recs;
   // fmd_batch_export_rds_device drains a queue asynchronously on the caller's stream: the event tells
   // the next call that appends to the same queue (NSLOT calls later) when it is empty
   Event ev_drained[NSLOT];
@@ -403,9 +469,9 @@ struct fmd_batch
   std::vector<fmd::HbCoef> hbcoef;
   fmd::HbChainTaps hb_taps{}; // the same taps as k_halfband_chain takes them (three-stage chains)
 
-  // host staging for the host-buffer entry point (h_audio: sized in bytes of the call's output format)
-  DevBuf<float> h_iq, h_audio;
-  DevBuf<float> h_mpx; // ... and of its multiplex rows (fmd_batch_process_host_mpx: sized on first use)
+  // device staging of the host-buffer entry points, by kind: the input rows ([FMT_IQ]) and every output's rows (sized
+  // on first use, in bytes of the call's format)
+  DevBuf<float> h_stage[FMT_KINDS];
   // fmd_batch_debug_mpx_ms (its first query switches this on): the multiplex writer's own start and stop of the last
   // NSLOT calls that asked for the multiplex (events of their own, no slot of the stage list or the timeline)
   int dbg_mpx_timing = 0;
@@ -439,7 +505,7 @@ struct fmd_batch
     std::vector<std::unique_ptr<SelTable>> pool;
     int cur = -1;
   };
-  Selection sel_audio, sel_mpx;
+  Selection sel[FMT_KINDS]; // by output kind (kOutKinds; [FMT_IQ] is never used); feed and channel IQ: the multiplex's form
   /* The mono feed at sample_rate_pcm / feed_div (fmd_batch_set_feed).  Every batch knows the
    * divisor; the caller-facing one keeps the taps for fmd_batch_get_feed_taps.  A batch with buffers of its own holds
    * the taps on the device, the time-major scratch of mono frames -- [feed_T - 1 + Amax][CP] floats: the history rows
@@ -457,12 +523,8 @@ struct fmd_batch
   hipStream_t feed_stream = nullptr;
   int dbg_feed_skip_roll = 0;     // fmd_batch_debug_feed_skip_roll (mutation test): the history rows stay stale
   int dbg_ciq_in_skip = 0;        // fmd_batch_debug_ciq_in_skip_tile (mutation test): the input copy's last tile is left out
-  Selection sel_feed;             // which channels deliver feed rows (fmd_batch_select_feed): the multiplex's form
-  DevBuf<float> h_feed;           // staging of the host-buffer call's feed rows (sized on first use)
   /* The channel IQ (the _call entry points): demod[q]'s rows as an output.  It has no state
-   * of its own -- a selection of the multiplex's form and the host call's staging. */
-  Selection sel_ciq;
-  DevBuf<float> h_ciq;
+   * of its own -- a selection of the multiplex's form (sel[FMT_CIQ]) and the host call's staging. */
   bool decoder_owned = false;     // the one-channel batch behind an fmd_decoder: it takes no selection
 
   std::vector<std::unique_ptr<fmd::GroupDecoder>> gdec;
@@ -643,10 +705,41 @@ inline bool is_shell(const fmd_batch* b)
   return !b->subs.empty();
 }
 
+/* A caller-facing batch and the batches with buffers of their own behind it: a shell's sub-batches with their first
+ * channels, or the plain batch itself.  THE walk over "every part": whatever is done per batch with buffers goes
+ * through it (what recurses through a sub-batch as a whole batch -- waits, resets, error words -- does not). */
+struct Part
+{
+  fmd_batch* x;
+  unsigned ch0;
+};
+std::vector<Part> parts(fmd_batch* b)
+{
+  std::vector<Part> v;
+  for (size_t k = 0; k < b->subs.size(); k++)
+    v.push_back(Part{b->subs[k].get(), b->sub_ch0[k]});
+  if (v.empty())
+    v.push_back(Part{b, 0u});
+  return v;
+}
+inline fmd_batch* first_part(fmd_batch* b)
+{
+  return is_shell(b) ? b->subs[0].get() : b;
+}
+
+/* a batch-wide setting that every sub-batch mirrors: the batch's own copy and theirs */
+template <typename T, typename V>
+void set_all(fmd_batch* b, T fmd_batch::*member, const V& value)
+{
+  b->*member = value;
+  for (auto& sb : b->subs)
+    sb.get()->*member = value;
+}
+
 /* whether the batch's next call writes any audio row (a selection of no rows: the audio pointer may be null) */
 inline bool audio_rows_due(const fmd_batch* b)
 {
-  return !(b->sel_audio.on && b->sel_audio.n_total == 0);
+  return !(b->sel[FMT_PCM].on && b->sel[FMT_PCM].n_total == 0);
 }
 
 /* The baseband lengths a call with channel IQ rows as input may have (fmd_batch_baseband_limits): those an IQ call
@@ -669,9 +762,8 @@ inline fmd_batch* owner_of(fmd_batch* b, unsigned channel, unsigned* local)
     *local = channel;
     return b;
   }
-  size_t s = 0;
-  while (s + 1 < b->subs.size() && channel >= b->sub_ch0[s + 1])
-    s++;
+  // (sub_ch0 ends with C: the last first channel that is not above `channel`)
+  const size_t s = size_t(std::upper_bound(b->sub_ch0.begin(), b->sub_ch0.end() - 1, channel) - b->sub_ch0.begin()) - 1;
   *local = channel - b->sub_ch0[s];
   return b->subs[s].get();
 }
@@ -1320,11 +1412,8 @@ int create_one(const fmd_params* params, unsigned n_channels, const int* tuning_
   bad |= b->pcm_clip.alloc(CP);
   bad |= b->istate.alloc(size_t(fmd::I_SLOTS) * CP);
   bad |= b->r_data.alloc(size_t(4) * CP);
-  b->queue_cap = std::max(4096u, 8u * C);
-  for (int q = 0; q < fmd_batch::NSLOT; q++)
-    bad |= b->queue[q].alloc(b->queue_cap);
-  bad |= b->queue_counts.alloc(fmd_batch::NSLOT);
-  bad |= b->h_counts.alloc(fmd_batch::NSLOT);
+  bad |= b->groups.alloc_queues(std::max(4096u, 8u * C));
+  bad |= b->groups.alloc_counts();
   bad |= b->export_cursor.alloc(fmd_batch::kExportCursors);
   if (bad)
     return fail(FMD_ERR_DEVICE, std::string("device allocation failed: ") + hipGetErrorString(hipGetLastError()));
@@ -1635,44 +1724,63 @@ const char* const kRestartRegions[] = {
 };
 constexpr int kRestartRegionCount = int(sizeof(kRestartRegions) / sizeof(kRestartRegions[0]));
 
-/* restart_tab of a batch with buffers of its own, copying from the twin `tw` (one channel) */
+/* THE list of the carried regions of a batch with buffers of its own (or of the twin): group (index of
+ * kRestartRegions), base, rows, element size, and the elements between two rows and between two channels.  Every
+ * geometry gives the same entries in the same order, entries of no rows included (their users leave those out). */
+struct CarriedRegion
+{
+  int group;
+  void* base;
+  unsigned rows, esz;
+  size_t row, ch;
+};
+std::vector<CarriedRegion> carried_regions(const fmd_batch* x)
+{
+  const fmd::Design& d = x->des;
+  std::vector<CarriedRegion> v;
+  // time-major unless said otherwise: a row is CP elements, a channel's elements are neighbours
+  auto add = [&](int group, void* base, size_t rows, unsigned esz, size_t row = 0, size_t ch = 1) {
+    v.push_back(CarriedRegion{group, base, unsigned(rows), esz, row ? row : size_t(x->CP), ch});
+  };
+  add(0, x->fstate.p, fmd::F_SLOTS, 4);
+  add(0, x->istate.p, fmd::I_SLOTS, 4);
+  add(0, x->r_data.p, 4, 2);
+  for (int q = 0; q < 2; q++) // channel-major: element j of channel c at c * if_order + j
+    add(1, x->hist[q].p, d.if_order, 8, 1, d.if_order);
+  for (int q = 0; q < 2; q++)
+    add(2, x->brp(q), d.rs_order, 8);
+  for (int q = 0; q < 2; q++)
+    add(3, x->mix[q].p, d.hb[0].len - 1, 8);
+  for (size_t s = 1; s < d.hb.size(); s++)
+    add(4, x->hbbuf[s - 1].p, d.hb[s].len - 1, 8);
+  for (int q = 0; q < 2; q++)
+    add(5, x->rdsraw[q].p, d.rds_lpf_taps.size() - 1, 8);
+  add(5, x->org.p, 1, 4); // ring origin: the twin's is 0, the batch phase
+  add(6, x->rpll.p, d.rds_mf_taps.size() - 1, 4);
+  add(6, x->org.p + x->CP, 1, 4);
+  for (int q = 0; q < 2; q++)
+    add(7, x->rs[q].p, d.lpf_taps.size() - 1, 8);
+  return v;
+}
+
+/* restart_tab of a batch with buffers of its own, copying from the twin `tw` (one channel): its carried regions
+ * paired with the twin's, entry by entry */
 int build_restart_table(fmd_batch* x, const fmd_batch* tw)
 {
   const fmd::Design& d = x->des;
   fmd::RestartTable& t = x->restart_tab;
   t.n = 0;
-  auto add = [&](int group, void* dst, const void* src, unsigned rows, unsigned esz, size_t dst_row, size_t dst_ch,
-                 size_t src_row) {
-    if (t.n >= fmd::kRestartMaxRegions)
-      return -1;
-    if (rows == 0)
-      return 0;
-    x->restart_group[t.n] = group;
-    t.r[t.n++] = fmd::RestartRegion{dst, src, rows, esz, dst_row, dst_ch, src_row};
-    return 0;
-  };
-  auto rows2 = [&](int group, const DevBuf<float2>* mine, const DevBuf<float2>* its, unsigned rows) {
-    int bad = 0;
-    for (int q = 0; q < 2; q++)
-      bad |= add(group, mine[q].p, its[q].p, rows, 8, x->CP, 1, tw->CP);
-    return bad;
-  };
-  int bad = 0;
-  bad |= add(0, x->fstate.p, tw->fstate.p, fmd::F_SLOTS, 4, x->CP, 1, tw->CP);
-  bad |= add(0, x->istate.p, tw->istate.p, fmd::I_SLOTS, 4, x->CP, 1, tw->CP);
-  bad |= add(0, x->r_data.p, tw->r_data.p, 4, 2, x->CP, 1, tw->CP);
-  for (int q = 0; q < 2; q++) // channel-major: element j of channel c at c * if_order + j
-    bad |= add(1, x->hist[q].p, tw->hist[q].p, d.if_order, 8, 1, d.if_order, 1);
-  for (int q = 0; q < 2; q++)
-    bad |= add(2, x->brp(q), tw->brp(q), d.rs_order, 8, x->CP, 1, tw->CP);
-  bad |= rows2(3, x->mix, tw->mix, unsigned(d.hb[0].len - 1));
-  for (size_t s = 1; s < d.hb.size(); s++)
-    bad |= add(4, x->hbbuf[s - 1].p, tw->hbbuf[s - 1].p, unsigned(d.hb[s].len - 1), 8, x->CP, 1, tw->CP);
-  bad |= rows2(5, x->rdsraw, tw->rdsraw, unsigned(d.rds_lpf_taps.size() - 1));
-  bad |= add(5, x->org.p, tw->org.p, 1, 4, x->CP, 1, tw->CP); // ring origin: the twin's is 0, the batch phase
-  bad |= add(6, x->rpll.p, tw->rpll.p, unsigned(d.rds_mf_taps.size() - 1), 4, x->CP, 1, tw->CP);
-  bad |= add(6, x->org.p + x->CP, tw->org.p + tw->CP, 1, 4, x->CP, 1, tw->CP);
-  bad |= rows2(7, x->rs, tw->rs, unsigned(d.lpf_taps.size() - 1));
+  const std::vector<CarriedRegion> mine = carried_regions(x), its = carried_regions(tw);
+  bool bad = mine.size() != its.size();
+  for (size_t i = 0; i < mine.size() && !bad; i++)
+  {
+    const CarriedRegion &m = mine[i], &w = its[i];
+    bad = m.group != w.group || m.rows != w.rows || m.esz != w.esz || t.n >= fmd::kRestartMaxRegions;
+    if (bad || m.rows == 0)
+      continue;
+    x->restart_group[t.n] = m.group;
+    t.r[t.n++] = fmd::RestartRegion{m.base, w.base, m.rows, m.esz, m.row, m.ch, w.row};
+  }
   if (bad)
     return fail(FMD_ERR_ARG, "fmd_batch_enable_retune: this geometry has more carried regions than the restart takes");
   // staging of the new tuner rows (the edit lists' is the batch's own): a slot per call index mod NSLOT, at most
@@ -1829,17 +1937,6 @@ int submit_edits(fmd_batch* x, fmd_batch* tw, hipStream_t stream)
   return FMD_OK;
 }
 
-/* The batches with buffers of their own behind a caller-facing batch: its sub-batches, or itself */
-std::vector<fmd_batch*> buffer_batches(fmd_batch* b)
-{
-  std::vector<fmd_batch*> v;
-  for (auto& sb : b->subs)
-    v.push_back(sb.get());
-  if (v.empty())
-    v.push_back(b);
-  return v;
-}
-
 /* the shift channel c of the caller-facing batch b decodes with in call `ci` */
 int shift_at(fmd_batch* b, unsigned c, uint32_t ci)
 {
@@ -1957,9 +2054,10 @@ int ensure_map(fmd_batch* b, const char* who)
   if (b->map_on)
     return FMD_OK;
   HIPCHK(hipSetDevice(b->device));
-  const std::vector<fmd_batch*> xs = buffer_batches(b);
-  for (fmd_batch* x : xs)
+  const std::vector<Part> ps = parts(b);
+  for (const Part& p : ps)
   {
+    fmd_batch* x = p.x;
     if (x->d_walk.n < x->C && x->d_walk.alloc(x->C))
       return fail(FMD_ERR_DEVICE, std::string(who) + ": device allocation failed");
     if (x->h_walk.n < size_t(fmd_batch::NSLOT) * x->C && x->h_walk.alloc(size_t(fmd_batch::NSLOT) * x->C))
@@ -1969,13 +2067,12 @@ int ensure_map(fmd_batch* b, const char* who)
         HIPCHK(e.create());
   }
   const unsigned rows = b->C / b->cpc;
-  for (size_t k = 0; k < xs.size(); k++)
+  for (const Part& p : ps)
   {
-    fmd_batch* x = xs[k];
-    const unsigned ch0 = is_shell(b) ? b->sub_ch0[k] : 0u;
+    fmd_batch* x = p.x;
     x->cmap.resize(x->C);
     for (unsigned c = 0; c < x->C; c++)
-      x->cmap[c] = (ch0 + c) / b->cpc;
+      x->cmap[c] = (p.ch0 + c) / b->cpc;
     x->map_on = true;
     x->map_dirty = true;
     x->n_cap = rows;
@@ -2005,8 +2102,8 @@ static int process_any(fmd_batch* b, const Call& c)
   if (int rc = check_call(b, c, pl))
     return rc;
   fmd_batch* tw = b->twin.get();
-  for (fmd_batch* x : buffer_batches(b))
-    if (int rc = submit_edits(x, tw, static_cast<hipStream_t>(c.stream)))
+  for (const Part& p : parts(b))
+    if (int rc = submit_edits(p.x, tw, static_cast<hipStream_t>(c.stream)))
     {
       mark_failed(b, "a channel edit could not be submitted");
       return rc;
@@ -2050,11 +2147,9 @@ static int process_shell(fmd_batch* b, const Call& c)
     const size_t row0 = c.ciq_in() ? ch0 : b->map_on ? 0 : ch0 / b->cpc;
     sc.iq = static_cast<const char*>(c.iq) + row0 * c.iq_stride * c.in_esz();
     // (the sub-batch's first row of every output; every sub-batch counts the feed's frames for itself)
-    sc.audio = c.audio.from_channel(ch0, b->sel_audio.on);
+    for (FormatKind k : kOutKinds)
+      sc.out(k) = c.out(k).from_channel(ch0, b->sel[k].on);
     sc.audio.out = &nf;
-    sc.mpx = c.mpx.from_channel(ch0, b->sel_mpx.on);
-    sc.feed = c.feed.from_channel(ch0, b->sel_feed.on);
-    sc.ciq = c.ciq.from_channel(ch0, b->sel_ciq.on);
     const int rc = submit_call(sb, sc);
     if (rc != FMD_OK)
     { // the first sub-batch refuses what every one of them would refuse (same geometry, same positions): nothing
@@ -2147,14 +2242,14 @@ static int check_call_args(const char* who, CallWay way, fmd_batch* b, Call& c)
   if (dev && c.audio.fmt == FMD_PCM_S16 && c.iq && c.audio.p && !c.audio.rows_aligned())
     return refuse(FMD_ERR_ARG, "for FMD_PCM_S16 the audio pointer must be 16-byte aligned and audio_channel_stride a "
                                "multiple of 8 elements");
-  const unsigned m_rows = b->sel_mpx.on ? b->sel_mpx.n_total : b->C;
-  const unsigned f_rows = b->sel_feed.on ? b->sel_feed.n_total : b->C;
+  auto rows_of = [b](FormatKind k) { return b->sel[k].on ? b->sel[k].n_total : b->C; };
+  const unsigned m_rows = rows_of(FMT_MPX), f_rows = rows_of(FMT_FEED);
   if (m_rows == 0) // a selection of no rows: the call without the multiplex
     c.mpx.p = nullptr;
   if (c.mpx.out)
     *c.mpx.out = 0;
   c.feed.deliver = f_rows != 0;
-  const unsigned q_rows = b->sel_ciq.on ? b->sel_ciq.n_total : b->C;
+  const unsigned q_rows = rows_of(FMT_CIQ);
   if (q_rows == 0) // a selection of no rows: the call without the channel IQ
     c.ciq.p = nullptr;
   if (!c.mpx.p && !c.feed.p && !c.ciq.p)
@@ -2343,10 +2438,10 @@ int fmd_batch_debug_set_spin_limit(fmd_batch* b, unsigned limit)
 {
   if (!b)
     return fail(FMD_ERR_ARG, "null batch");
-  b->spin_limit = limit;
+  set_all(b, &fmd_batch::spin_limit, limit);
   b->st.spin_limit = limit;
   for (auto& sb : b->subs)
-    fmd_batch_debug_set_spin_limit(sb.get(), limit);
+    sb->st.spin_limit = limit;
   return FMD_OK;
 }
 
@@ -2361,9 +2456,7 @@ int fmd_batch_debug_restart_skip(fmd_batch* b, int region)
       names += std::string(names.empty() ? "" : ", ") + r;
     return fail(FMD_ERR_ARG, "fmd_batch_debug_restart_skip: -1 or the index of a region (" + names + ")");
   }
-  b->restart_skip = region;
-  for (auto& sb : b->subs)
-    sb->restart_skip = region;
+  set_all(b, &fmd_batch::restart_skip, region);
   return FMD_OK;
 }
 
@@ -2371,9 +2464,7 @@ int fmd_batch_debug_reset_keep_ring_phase(fmd_batch* b, int on)
 {
   if (!b)
     return fail(FMD_ERR_ARG, "null batch");
-  b->dbg_reset_keep_phase = on != 0;
-  for (auto& sb : b->subs)
-    sb->dbg_reset_keep_phase = on != 0;
+  set_all(b, &fmd_batch::dbg_reset_keep_phase, on != 0);
   return FMD_OK;
 }
 
@@ -2484,14 +2575,9 @@ int fmd_batch_enable_retune(fmd_batch* b)
   twin->concurrency = 2; // ordered by the restarts that read it, never by the caller's stream
   if (b->twin_iq.alloc(FMD_MAX_BLOCK) || b->twin_audio.alloc(fmd_batch_max_audio_floats(tw, FMD_MAX_BLOCK)))
     return fail(FMD_ERR_DEVICE, "fmd_batch_enable_retune: device allocation failed");
-  if (is_shell(b))
-  {
-    for (auto& sb : b->subs)
-      if (int rc = build_restart_table(sb.get(), tw))
-        return rc;
-  }
-  else if (int rc = build_restart_table(b, tw))
-    return rc;
+  for (const Part& p : parts(b))
+    if (int rc = build_restart_table(p.x, tw))
+      return rc;
   HIPCHK(hipDeviceSynchronize());
   {
     std::lock_guard<std::mutex> lk(b->log_mu);
@@ -2590,17 +2676,10 @@ int fmd_batch_set_channels_per_capture(fmd_batch* b, unsigned channels_per_captu
                                    ", which is not a multiple of it");
   HIPCHK(hipSetDevice(b->device));
   HIPCHK(hipDeviceSynchronize());
-  b->cpc = k;
-  for (auto& sb : b->subs)
-    sb->cpc = k;
+  set_all(b, &fmd_batch::cpc, k);
   // the contiguous rule replaces any capture map
-  b->map_on = false;
-  b->n_cap = 0;
-  for (auto& sb : b->subs)
-  {
-    sb->map_on = false;
-    sb->n_cap = 0;
-  }
+  set_all(b, &fmd_batch::map_on, false);
+  set_all(b, &fmd_batch::n_cap, 0u);
   return FMD_OK;
 }
 
@@ -2622,21 +2701,15 @@ int fmd_batch_set_capture_map(fmd_batch* b, const unsigned* capture_of_channel, 
   HIPCHK(hipDeviceSynchronize());
   if (!capture_of_channel) // one row per channel, as after creation
     return fmd_batch_set_channels_per_capture(b, 1);
-  b->cpc = 1;
-  for (auto& sb : b->subs)
-    sb->cpc = 1;
+  set_all(b, &fmd_batch::cpc, 1u);
   if (int rc = ensure_map(b, "fmd_batch_set_capture_map"))
     return rc;
-  const std::vector<fmd_batch*> xs = buffer_batches(b);
-  for (size_t k = 0; k < xs.size(); k++)
+  for (const Part& p : parts(b))
   {
-    fmd_batch* x = xs[k];
-    const unsigned ch0 = is_shell(b) ? b->sub_ch0[k] : 0u;
-    std::copy(capture_of_channel + ch0, capture_of_channel + ch0 + x->C, x->cmap.begin());
-    x->map_dirty = true;
-    x->n_cap = n_captures;
+    std::copy(capture_of_channel + p.ch0, capture_of_channel + p.ch0 + p.x->C, p.x->cmap.begin());
+    p.x->map_dirty = true;
   }
-  b->n_cap = n_captures;
+  set_all(b, &fmd_batch::n_cap, n_captures);
   return FMD_OK;
 }
 
@@ -2644,12 +2717,9 @@ int fmd_batch_debug_capture_walk(fmd_batch* b, int on)
 {
   if (!b)
     return fail(FMD_ERR_ARG, "fmd_batch_debug_capture_walk: null batch");
-  b->capture_walk = on != 0;
-  for (fmd_batch* x : buffer_batches(b))
-  { // the next call takes the walk in the new order (calls in flight keep theirs: the copy is ordered like a switch)
-    x->capture_walk = on != 0;
-    x->map_dirty = x->map_on;
-  }
+  set_all(b, &fmd_batch::capture_walk, on != 0);
+  for (const Part& p : parts(b)) // the next call takes the walk in the new order (calls in flight keep theirs: the
+    p.x->map_dirty = p.x->map_on; // copy is ordered like a switch)
   return FMD_OK;
 }
 
@@ -2685,7 +2755,7 @@ int fmd_batch_switch_captures(fmd_batch* b, const unsigned* channels, const unsi
 /* fmd_batch_select_audio / _mpx: checked as a whole, then every batch with buffers takes its part -- (local channel,
  * global row), sorted by channel: the audio table is indexed by channel anyway, and the multiplex writer's gathers
  * coalesce over neighbouring channels -- and builds a new table version in front of its next call (sel_table). */
-static int select_rows(fmd_batch* b, int which, const unsigned* channels, unsigned n, const char* who)
+static int select_rows(fmd_batch* b, FormatKind kind, const unsigned* channels, unsigned n, const char* who)
 {
   if (!b)
     return fail(FMD_ERR_ARG, std::string(who) + ": null batch");
@@ -2707,21 +2777,14 @@ static int select_rows(fmd_batch* b, int which, const unsigned* channels, unsign
   }
   else
     n = 0;
-  // which: 0 audio, 1 multiplex, 2 feed, 3 channel IQ
-  auto pick = [which](fmd_batch* y) -> fmd_batch::Selection& {
-    return which == 3 ? y->sel_ciq : which == 2 ? y->sel_feed : which == 1 ? y->sel_mpx : y->sel_audio;
-  };
-  fmd_batch::Selection& top = pick(b);
-  const std::vector<fmd_batch*> xs = buffer_batches(b);
-  for (size_t k = 0; k < xs.size(); k++)
+  fmd_batch::Selection& top = b->sel[kind];
+  for (const Part& p : parts(b))
   {
-    fmd_batch* x = xs[k];
-    const unsigned ch0 = is_shell(b) ? b->sub_ch0[k] : 0u;
-    fmd_batch::Selection& sel = pick(x);
+    fmd_batch::Selection& sel = p.x->sel[kind];
     sel.ent.clear();
     for (unsigned i = 0; i < n; i++)
-      if (channels[i] >= ch0 && channels[i] - ch0 < x->C)
-        sel.ent.push_back(make_int2(int(channels[i] - ch0), int(i)));
+      if (channels[i] >= p.ch0 && channels[i] - p.ch0 < p.x->C)
+        sel.ent.push_back(make_int2(int(channels[i] - p.ch0), int(i)));
     std::sort(sel.ent.begin(), sel.ent.end(), [](const int2& a, const int2& c) { return a.x < c.x; });
     sel.on = channels != nullptr;
     sel.n_total = n;
@@ -2736,12 +2799,11 @@ static int select_rows(fmd_batch* b, int which, const unsigned* channels, unsign
   return FMD_OK;
 }
 
-static int get_selection(fmd_batch* b, int which, unsigned* out, unsigned cap, const char* who)
+static int get_selection(fmd_batch* b, FormatKind kind, unsigned* out, unsigned cap, const char* who)
 {
   if (!b || (cap && !out))
     return fail(FMD_ERR_ARG, std::string(who) + ": null argument");
-  const fmd_batch::Selection& sel =
-      which == 3 ? b->sel_ciq : which == 2 ? b->sel_feed : which == 1 ? b->sel_mpx : b->sel_audio;
+  const fmd_batch::Selection& sel = b->sel[kind];
   const unsigned n = sel.on ? sel.n_total : b->C;
   for (unsigned i = 0; i < std::min(cap, n); i++)
     out[i] = sel.on ? sel.list[i] : i;
@@ -2750,42 +2812,42 @@ static int get_selection(fmd_batch* b, int which, unsigned* out, unsigned cap, c
 
 int fmd_batch_select_audio(fmd_batch* b, const unsigned* channels, unsigned n)
 {
-  return select_rows(b, 0, channels, n, "fmd_batch_select_audio");
+  return select_rows(b, FMT_PCM, channels, n, "fmd_batch_select_audio");
 }
 
 int fmd_batch_select_mpx(fmd_batch* b, const unsigned* channels, unsigned n)
 {
-  return select_rows(b, 1, channels, n, "fmd_batch_select_mpx");
+  return select_rows(b, FMT_MPX, channels, n, "fmd_batch_select_mpx");
 }
 
 int fmd_batch_get_audio_selection(fmd_batch* b, unsigned* out, unsigned cap)
 {
-  return get_selection(b, 0, out, cap, "fmd_batch_get_audio_selection");
+  return get_selection(b, FMT_PCM, out, cap, "fmd_batch_get_audio_selection");
 }
 
 int fmd_batch_get_mpx_selection(fmd_batch* b, unsigned* out, unsigned cap)
 {
-  return get_selection(b, 1, out, cap, "fmd_batch_get_mpx_selection");
+  return get_selection(b, FMT_MPX, out, cap, "fmd_batch_get_mpx_selection");
 }
 
 int fmd_batch_select_feed(fmd_batch* b, const unsigned* channels, unsigned n)
 {
-  return select_rows(b, 2, channels, n, "fmd_batch_select_feed");
+  return select_rows(b, FMT_FEED, channels, n, "fmd_batch_select_feed");
 }
 
 int fmd_batch_get_feed_selection(fmd_batch* b, unsigned* out, unsigned cap)
 {
-  return get_selection(b, 2, out, cap, "fmd_batch_get_feed_selection");
+  return get_selection(b, FMT_FEED, out, cap, "fmd_batch_get_feed_selection");
 }
 
 int fmd_batch_select_ciq(fmd_batch* b, const unsigned* channels, unsigned n)
 {
-  return select_rows(b, 3, channels, n, "fmd_batch_select_ciq");
+  return select_rows(b, FMT_CIQ, channels, n, "fmd_batch_select_ciq");
 }
 
 int fmd_batch_get_ciq_selection(fmd_batch* b, unsigned* out, unsigned cap)
 {
-  return get_selection(b, 3, out, cap, "fmd_batch_get_ciq_selection");
+  return get_selection(b, FMT_CIQ, out, cap, "fmd_batch_get_ciq_selection");
 }
 
 /* fmd_batch_set_feed: a setup call.  It waits for the calls in flight (the scratch they may still write is freed or
@@ -2810,8 +2872,9 @@ int fmd_batch_set_feed(fmd_batch* b, int divisor)
   HIPCHK(hipSetDevice(b->device));
   HIPCHK(hipDeviceSynchronize());
   const unsigned T = unsigned(taps.size());
-  for (fmd_batch* x : buffer_batches(b))
+  for (const Part& p : parts(b))
   {
+    fmd_batch* x = p.x;
     x->feed_div = 0; // (off until everything below is in place)
     x->feed_T = 0;
     x->feed_g = 0;
@@ -2867,8 +2930,7 @@ int fmd_batch_debug_ciq_in_skip_tile(fmd_batch* b, int on)
 {
   if (!b)
     return fail(FMD_ERR_ARG, "null batch");
-  for (fmd_batch* x : buffer_batches(b))
-    x->dbg_ciq_in_skip = on != 0;
+  set_all(b, &fmd_batch::dbg_ciq_in_skip, on != 0);
   return FMD_OK;
 }
 
@@ -2876,8 +2938,7 @@ int fmd_batch_debug_feed_skip_roll(fmd_batch* b, int on)
 {
   if (!b)
     return fail(FMD_ERR_ARG, "null batch");
-  for (fmd_batch* x : buffer_batches(b))
-    x->dbg_feed_skip_roll = on != 0;
+  set_all(b, &fmd_batch::dbg_feed_skip_roll, on != 0);
   return FMD_OK;
 }
 
@@ -2918,54 +2979,70 @@ static bool slot_to_drain(const fmd_batch* b, int q, int lag)
   return slot_eligible(b, q, lag) && b->drained_call[q] != b->slot_call[q];
 }
 
-/* Draining the RDS queues of one batch with buffers of its own, in the three steps between which the caller
- * synchronises the stream once for ALL the batches it drains (a shell: its sub-batches). */
-struct QueueDrain
-{
-  fmd_batch* b = nullptr;
-  unsigned ch0 = 0; // what the caller adds to the records' channel numbers
-  int todo[fmd_batch::NSLOT] = {}, ntodo = 0;
-  unsigned cnt[fmd_batch::NSLOT] = {};
-  size_t total = 0;
-};
+} // extern "C"
 
-static int drain_counts(QueueDrain& d, int lag, hipStream_t stream)
+namespace
 {
-  fmd_batch* b = d.b;
-  for (int q = 0; q < fmd_batch::NSLOT; q++)
-    if (slot_to_drain(b, q, lag)) // never used / already drained / its call may still be appending
-    {
-      HIPCHK(hipStreamWaitEvent(stream, b->cev[q][fmd_batch::EV_RDS], 0));
-      d.todo[d.ntodo++] = q;
-    }
-  if (d.ntodo)
-    HIPCHK(hipMemcpyAsync(b->h_counts.p, b->queue_counts.p, fmd_batch::NSLOT * sizeof(unsigned), hipMemcpyDeviceToHost,
-                          stream));
-  return FMD_OK;
-}
 
-static int drain_records(QueueDrain& d, hipStream_t stream)
-{ // (the counts have arrived)
-  fmd_batch* b = d.b;
-  for (int i = 0; i < d.ntodo; i++)
+/* One drain of a queue family (fmd_batch::groups or ::blocks) of every part of b: the stream behind EV_RDS of the
+ * slots that are `due`, one copy of the counts per part, ONE synchronisation, the records of the non-empty queues
+ * back to back, at most one more synchronisation; then `done` for every slot visited and `take` for every part's
+ * records.  Two synchronisations whatever the number of queues and of sub-batches; page-locked destinations: the
+ * copies are DMA transfers, not staging kernels that would queue up behind the decoder's own.
+ *
+ * Where the two families differ, as they always did -- decided here and by the two callers, nowhere else:
+ *  - which slots are due: the groups', whose newest call's groups were not taken yet (drained_call != slot_call,
+ *    shared with the device export); the blocks', that a mode-2 call has used since the last drain (rb_dirty).
+ *  - what overflow means: a queue keeps its first `cap` records in both; the groups' kernel has flagged the loss
+ *    (FMD_WARN_RDS_LOST), the block collect adds the family's `over` to what it reports as lost.
+ *  - how the staging grows: to the records found, and at least 2 C + 1024 groups / 4 C + 1024 block records.
+ *  - the second synchronisation: sync_if_visited (the blocks) makes it whenever a slot was visited, else (the
+ *    groups) only when records were copied. */
+template <typename Q, typename Due, typename Done, typename Take>
+int drain_queues(fmd_batch* b, Q fmd_batch::*family, hipStream_t stream, size_t grow_per_channel,
+                        bool sync_if_visited, const char* who, Due due, Done done, Take take)
+{
+  const std::vector<Part> ps = parts(b);
+  bool any = false, again = false;
+  for (const Part& p : ps)
   {
-    d.cnt[i] = std::min(b->h_counts.p[d.todo[i]], b->queue_cap); // overflow: the oldest queue_cap groups are kept
-    d.total += d.cnt[i];
+    Q& q = p.x->*family;
+    q.ntodo = 0;
+    for (int slot = 0; slot < kSlots; slot++)
+      if (due(p.x, slot)) // (not: never used / already drained / its call may still be appending)
+      {
+        HIPCHK(hipStreamWaitEvent(stream, p.x->cev[slot][fmd_batch::EV_RDS], 0));
+        q.todo[q.ntodo++] = slot;
+      }
+    HIPCHK(q.fetch_counts(stream));
+    any = any || q.ntodo > 0;
   }
-  if (d.total > b->h_recs.n && b->h_recs.alloc(std::max<size_t>(d.total, size_t(2) * b->C + 1024)))
-    return fail(FMD_ERR_DEVICE, "fmd_batch_collect_rds: page-locked staging allocation failed");
-  size_t at = 0;
-  for (int i = 0; i < d.ntodo; i++)
-    if (d.cnt[i])
-    {
-      const int q = d.todo[i];
-      HIPCHK(hipMemcpyAsync(b->h_recs.p + at, b->queue[q].p, size_t(d.cnt[i]) * sizeof(fmd::RdsGroupRec),
-                            hipMemcpyDeviceToHost, stream));
-      HIPCHK(hipMemsetAsync(b->qcount(q), 0, sizeof(unsigned), stream));
-      at += d.cnt[i];
-    }
+  if (!any)
+    return FMD_OK;
+  HIPCHK(hipStreamSynchronize(stream));
+  for (const Part& p : ps)
+  {
+    Q& q = p.x->*family;
+    if (const int bad = q.fetch_records(grow_per_channel * p.x->C + 1024, stream))
+      return fail(FMD_ERR_DEVICE, std::string(who) + (bad == -1 ? ": page-locked staging allocation failed"
+                                                                : ": a copy out of the record queues failed"));
+    again = again || (sync_if_visited ? q.ntodo > 0 : q.total > 0);
+  }
+  if (again)
+    HIPCHK(hipStreamSynchronize(stream));
+  for (const Part& p : ps)
+  {
+    Q& q = p.x->*family;
+    for (int i = 0; i < q.ntodo; i++)
+      done(p.x, q.todo[i]);
+    take(p, q);
+  }
   return FMD_OK;
 }
+
+} // namespace
+
+extern "C" {
 
 int fmd_batch_collect_rds_lagged(fmd_batch* b, fmd_rds_group* out, unsigned cap, int run_group_decoder,
                                  int lag, void* stream_)
@@ -2974,44 +3051,18 @@ int fmd_batch_collect_rds_lagged(fmd_batch* b, fmd_rds_group* out, unsigned cap,
     return fail(FMD_ERR_ARG, "fmd_batch_collect_rds: bad argument (lag must be 0..4)");
   hipStream_t stream = static_cast<hipStream_t>(stream_);
   HIPCHK(hipSetDevice(b->device));
-  /* Two synchronisations whatever the number of queues (and of sub-batches): all counts in one copy per batch,
-   * then the records of the non-empty queues back to back.  Page-locked destinations: the copies are DMA
-   * transfers, not staging kernels that would queue up behind the decoder's own. */
-  std::vector<QueueDrain> drains(is_shell(b) ? b->subs.size() : 1);
-  for (size_t k = 0; k < drains.size(); k++)
-  {
-    drains[k].b = is_shell(b) ? b->subs[k].get() : b;
-    drains[k].ch0 = is_shell(b) ? b->sub_ch0[k] : 0u;
-  }
-  bool any = false, any_recs = false;
-  for (auto& d : drains)
-  {
-    if (int rc = drain_counts(d, lag, stream))
-      return rc;
-    any = any || d.ntodo > 0;
-  }
   std::vector<fmd::RdsGroupRec> recs;
-  if (any)
-  {
-    HIPCHK(hipStreamSynchronize(stream));
-    for (auto& d : drains)
-    {
-      if (int rc = drain_records(d, stream))
-        return rc;
-      any_recs = any_recs || d.total > 0;
-    }
-    if (any_recs)
-      HIPCHK(hipStreamSynchronize(stream));
-    for (auto& d : drains)
-    {
-      for (int i = 0; i < d.ntodo; i++)
-        d.b->drained_call[d.todo[i]] = d.b->slot_call[d.todo[i]];
-      const size_t at = recs.size();
-      recs.insert(recs.end(), d.b->h_recs.p, d.b->h_recs.p + d.total);
-      for (size_t i = at; i < recs.size(); i++)
-        recs[i].channel += d.ch0;
-    }
-  }
+  if (int rc = drain_queues(
+          b, &fmd_batch::groups, stream, 2, false, "fmd_batch_collect_rds",
+          [lag](const fmd_batch* x, int q) { return slot_to_drain(x, q, lag); },
+          [](fmd_batch* x, int q) { x->drained_call[q] = x->slot_call[q]; },
+          [&recs](const Part& p, const auto& q) {
+            const size_t at = recs.size();
+            recs.insert(recs.end(), q.h_recs.p, q.h_recs.p + q.total);
+            for (size_t i = at; i < recs.size(); i++)
+              recs[i].channel += p.ch0;
+          }))
+    return rc;
   if (int rc = check_device_errors(b)) // the stream was synchronised above: covers the drained calls
     return rc;
   std::sort(recs.begin(), recs.end(), [](const fmd::RdsGroupRec& x, const fmd::RdsGroupRec& y) {
@@ -3060,8 +3111,8 @@ static int export_queues(fmd_batch* b, int32_t* d_records, unsigned cap, unsigne
     if (!slot_to_drain(b, q, lag))
       continue; // also: already exported for its call -- one launch per call, not one per slot
     HIPCHK(hipStreamWaitEvent(stream, b->cev[q][fmd_batch::EV_RDS], 0));
-    hipLaunchKernelGGL(fmd::k_rds_export, dim3(1), dim3(256), 0, stream, b->queue[q].p, b->qcount(q),
-                       b->queue_cap, reinterpret_cast<int4*>(d_records), cap, cursor, channel_offset, b->st.err);
+    hipLaunchKernelGGL(fmd::k_rds_export, dim3(1), dim3(256), 0, stream, b->groups.queue[q].p, b->groups.count(q),
+                       b->groups.cap, reinterpret_cast<int4*>(d_records), cap, cursor, channel_offset, b->st.err);
     HIPCHK(hipEventRecord(b->ev_drained[q], stream));
     b->drained_pending[q] = true;
     b->drained_call[q] = b->slot_call[q];
@@ -3079,14 +3130,9 @@ int fmd_batch_export_rds_device(fmd_batch* b, int32_t* d_records, unsigned cap, 
   HIPCHK(hipMemsetAsync(d_records, 0, size_t(cap) * 4 * sizeof(int32_t), stream));
   unsigned* const cursor = b->export_cursor.p + (b->export_seq++ % fmd_batch::kExportCursors);
   HIPCHK(hipMemsetAsync(cursor, 0, sizeof(unsigned), stream));
-  if (is_shell(b))
-  {
-    for (size_t k = 0; k < b->subs.size(); k++)
-      if (int rc = export_queues(b->subs[k].get(), d_records, cap, channel_offset + b->sub_ch0[k], lag, stream, cursor))
-        return rc;
-  }
-  else if (int rc = export_queues(b, d_records, cap, channel_offset, lag, stream, cursor))
-    return rc;
+  for (const Part& p : parts(b))
+    if (int rc = export_queues(p.x, d_records, cap, channel_offset + p.ch0, lag, stream, cursor))
+      return rc;
   HIPCHK(hipGetLastError());
   if (int rc = check_device_errors(b))
     return rc;
@@ -3136,28 +3182,17 @@ static int process_host_impl(fmd_batch* b, const Call& c)
   // element longer than fmd_batch_max_feed_samples)
   Call d = c;
   d.stream = nullptr;
-  StagedOut sa, sm, sf, sc;
-  if (int rc = sa.stage(b->h_audio, c.audio, b->sel_audio, C, fmd_batch_max_audio_floats(b, samples)))
-    return rc;
-  d.audio = sa.dev;
-  if (c.mpx.p)
-  {
-    if (int rc = sm.stage(b->h_mpx, c.mpx, b->sel_mpx, C, fmd_batch_max_mpx_samples(b, samples)))
-      return rc;
-    d.mpx = sm.dev;
-  }
-  if (c.feed.p)
-  {
-    if (int rc = sf.stage(b->h_feed, c.feed, b->sel_feed, C, size_t(fmd_batch_max_feed_samples(b, samples)) + 1))
-      return rc;
-    d.feed = sf.dev;
-  }
-  if (c.ciq.p)
-  {
-    if (int rc = sc.stage(b->h_ciq, c.ciq, b->sel_ciq, C, fmd_batch_max_mpx_samples(b, samples)))
-      return rc;
-    d.ciq = sc.dev;
-  }
+  const size_t caps[FMT_KINDS] = {0, fmd_batch_max_audio_floats(b, samples), fmd_batch_max_mpx_samples(b, samples),
+                                  size_t(fmd_batch_max_feed_samples(b, samples)) + 1,
+                                  fmd_batch_max_mpx_samples(b, samples)};
+  StagedOut so[FMT_KINDS];
+  for (FormatKind k : kOutKinds)
+    if (k == FMT_PCM || c.out(k).p)
+    {
+      if (int rc = so[k].stage(b->h_stage[k], c.out(k), b->sel[k], C, caps[k]))
+        return rc;
+      d.out(k) = so[k].dev;
+    }
   const size_t esz = c.in_esz(); // bytes per input sample
   const unsigned n_in = c.samples;
   // device copy: one row per channel, rows padded to a whole pair of samples (channel IQ rows: to 16 bytes)
@@ -3166,24 +3201,25 @@ static int process_host_impl(fmd_batch* b, const Call& c)
   // input rows: one per capture of the map, per channel, per cpc channels, or one
   const unsigned streams = !c.iq_stride ? 1u : c.ciq_in() ? C : b->map_on ? b->n_cap : C / b->cpc;
   const size_t iq_floats = (dev_row * streams + 3) / 4;
-  if (iq_floats > b->h_iq.n && b->h_iq.alloc(iq_floats))
+  DevBuf<float>& h_iq = b->h_stage[FMT_IQ];
+  if (iq_floats > h_iq.n && h_iq.alloc(iq_floats))
     return fail(FMD_ERR_DEVICE, "staging allocation failed");
-  d.iq = b->h_iq.p;
+  d.iq = h_iq.p;
   using clk = std::chrono::steady_clock;
   auto ms_since = [](clk::time_point t) { return std::chrono::duration<double, std::milli>(clk::now() - t).count(); };
   clk::time_point tp = clk::now();
   if (c.iq_stride)
-    HIPCHK(hipMemcpy2D(b->h_iq.p, dev_row, c.iq, c.iq_stride * esz, size_t(n_in) * esz, streams,
+    HIPCHK(hipMemcpy2D(h_iq.p, dev_row, c.iq, c.iq_stride * esz, size_t(n_in) * esz, streams,
                        hipMemcpyHostToDevice));
   else
-    HIPCHK(hipMemcpy(b->h_iq.p, c.iq, size_t(n_in) * esz, hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(h_iq.p, c.iq, size_t(n_in) * esz, hipMemcpyHostToDevice));
   b->host_ms[0] += ms_since(tp);
   tp = clk::now();
   int rc = process_any(b, d);
   if (rc != FMD_OK)
     return rc;
-  const unsigned nf = sa.n;
-  if (sa.rows > 1 && nf > c.audio.stride)
+  const unsigned nf = so[FMT_PCM].n;
+  if (so[FMT_PCM].rows > 1 && nf > c.audio.stride)
     return fail(FMD_ERR_ARG, "audio_channel_stride smaller than the audio produced");
   b->host_ms[1] += ms_since(tp);
   tp = clk::now();
@@ -3192,14 +3228,12 @@ static int process_host_impl(fmd_batch* b, const Call& c)
   rc = wait_impl(b, 0, nullptr, false); // the groups-lost flag is this call's to report, at its end
   if (rc < 0)
     return rc;
-  if ((rc = sa.fetch(c.audio)) || (rc = sm.fetch(c.mpx)) || (rc = sf.fetch(c.feed)) || (rc = sc.fetch(c.ciq)))
-    return rc;
-  if (c.mpx.out)
-    *c.mpx.out = sm.n;
-  if (c.feed.out)
-    *c.feed.out = sf.n;
-  if (c.ciq.out)
-    *c.ciq.out = sc.n;
+  for (FormatKind k : kOutKinds)
+    if ((rc = so[k].fetch(c.out(k))))
+      return rc;
+  for (FormatKind k : {FMT_MPX, FMT_FEED, FMT_CIQ}) // (the audio's count: at the call's end)
+    if (c.out(k).out)
+      *c.out(k).out = so[k].n;
   b->host_ms[2] += ms_since(tp);
   tp = clk::now();
   rc = fmd_batch_collect_rds(b, nullptr, 0, 1, nullptr);
@@ -3297,63 +3331,37 @@ int fmd_batch_read_pcm_clipped(fmd_batch* b, unsigned first_channel, unsigned n,
 static_assert(sizeof(fmd_rds_block) == 24 && sizeof(fmd_rds_quality) == 32, "the records of fmd.h");
 static_assert(sizeof(fmd_rds_quality) == fmd::RQ_N * sizeof(unsigned), "one word per counter, in the kernel's order");
 
-/* the batches with buffers of their own behind a caller-facing one */
-static std::vector<fmd_batch*> rb_owners(fmd_batch* b)
-{
-  std::vector<fmd_batch*> xs;
-  if (is_shell(b))
-    for (auto& sb : b->subs)
-      xs.push_back(sb.get());
-  else
-    xs.push_back(b);
-  return xs;
-}
-
 int fmd_batch_set_rds_blocks(fmd_batch* b, int mode, unsigned queue_records)
 {
   if (!b)
     return fail(FMD_ERR_ARG, "fmd_batch_set_rds_blocks: null batch");
   if (mode < FMD_RDS_BLOCKS_OFF || mode > FMD_RDS_BLOCKS_RECORD)
     return fail(FMD_ERR_ARG, "fmd_batch_set_rds_blocks: mode must be FMD_RDS_BLOCKS_OFF, _COUNT or _RECORD (0..2)");
-  if (queue_records && b->rb_cap && queue_records != b->rb_cap)
-    return fail(FMD_ERR_ARG, "fmd_batch_set_rds_blocks: the block queues hold " + std::to_string(b->rb_cap) +
+  // (every part's queues hold the same number of records where the caller named one; else the first part's stands
+  // for all in the refusal, as it always did)
+  const unsigned have = first_part(b)->blocks.cap;
+  if (queue_records && have && queue_records != have)
+    return fail(FMD_ERR_ARG, "fmd_batch_set_rds_blocks: the block queues hold " + std::to_string(have) +
                                  " records since the first call that enabled mode 2; " +
                                  std::to_string(queue_records) + " refused");
   if (mode != FMD_RDS_BLOCKS_OFF)
   {
     HIPCHK(hipSetDevice(b->device));
-    const std::vector<fmd_batch*> xs = rb_owners(b);
-    for (fmd_batch* x : xs)
-      if (!x->rb_quality.p && x->rb_quality.alloc(size_t(fmd::RQ_N) * x->CP))
+    const std::vector<Part> ps = parts(b);
+    for (const Part& p : ps)
+      if (!p.x->rb_quality.p && p.x->rb_quality.alloc(size_t(fmd::RQ_N) * p.x->CP))
         return fail(FMD_ERR_DEVICE, "fmd_batch_set_rds_blocks: allocation of the counters failed");
-    if (mode == FMD_RDS_BLOCKS_RECORD && !b->rb_cap)
-    {
-      for (fmd_batch* x : xs)
-      {
-        const unsigned cap = queue_records ? queue_records : std::max(8192u, 4u * x->C);
-        int bad = x->rb_counts.alloc(fmd_batch::NSLOT) | x->rb_h_counts.alloc(fmd_batch::NSLOT);
-        for (int q = 0; q < fmd_batch::NSLOT && !bad; q++)
-          bad |= x->rb_queue[q].alloc(size_t(2) * cap);
-        if (bad)
+    if (mode == FMD_RDS_BLOCKS_RECORD && !have)
+      for (const Part& p : ps)
+        if (p.x->blocks.alloc_counts() ||
+            p.x->blocks.alloc_queues(queue_records ? queue_records : std::max(8192u, 4u * p.x->C)))
         { // nothing half-made stays: the batch is as before the call
-          for (fmd_batch* y : xs)
-          {
-            for (auto& qb : y->rb_queue)
-              qb.release();
-            y->rb_counts.release();
-            y->rb_h_counts.release();
-            y->rb_cap = 0;
-          }
+          for (const Part& y : ps)
+            y.x->blocks.release();
           return fail(FMD_ERR_DEVICE, "fmd_batch_set_rds_blocks: allocation of the block queues failed");
         }
-        x->rb_cap = cap;
-      }
-      b->rb_cap = queue_records ? queue_records : xs[0]->rb_cap;
-    }
   }
-  b->rb_mode = mode;
-  for (auto& sb : b->subs)
-    sb->rb_mode = mode;
+  set_all(b, &fmd_batch::rb_mode, mode);
   return FMD_OK;
 }
 
@@ -3371,85 +3379,27 @@ int fmd_batch_collect_rds_blocks(fmd_batch* b, fmd_rds_block* out, unsigned cap,
     return fail(FMD_ERR_ARG, "fmd_batch_collect_rds_blocks: bad argument (lag must be 0..4)");
   if (lost)
     *lost = 0;
-  if (!b->rb_cap) // mode 2 was never enabled: no queue exists
+  if (!first_part(b)->blocks.cap) // mode 2 was never enabled: no queue exists
     return 0;
   hipStream_t stream = static_cast<hipStream_t>(stream_);
   HIPCHK(hipSetDevice(b->device));
-  // the same two synchronisations as fmd_batch_collect_rds_lagged, whatever the number of queues and sub-batches
-  struct Drain
-  {
-    fmd_batch* x;
-    unsigned ch0;
-    int todo[fmd_batch::NSLOT], ntodo = 0;
-    unsigned cnt[fmd_batch::NSLOT];
-    size_t total = 0;
-  };
-  std::vector<Drain> drains;
-  {
-    const std::vector<fmd_batch*> xs = rb_owners(b);
-    for (size_t k = 0; k < xs.size(); k++)
-      drains.push_back(Drain{xs[k], is_shell(b) ? b->sub_ch0[k] : 0u});
-  }
-  bool any = false, any_recs = false;
-  for (Drain& d : drains)
-  {
-    fmd_batch* x = d.x;
-    for (int q = 0; q < fmd_batch::NSLOT; q++)
-      if (x->rb_dirty[q] && slot_eligible(x, q, lag))
-      {
-        HIPCHK(hipStreamWaitEvent(stream, x->cev[q][fmd_batch::EV_RDS], 0));
-        d.todo[d.ntodo++] = q;
-      }
-    if (d.ntodo)
-      HIPCHK(hipMemcpyAsync(x->rb_h_counts.p, x->rb_counts.p, fmd_batch::NSLOT * sizeof(unsigned),
-                            hipMemcpyDeviceToHost, stream));
-    any = any || d.ntodo > 0;
-  }
   std::vector<fmd_rds_block> recs;
   uint64_t dropped = 0;
-  if (any)
-  {
-    HIPCHK(hipStreamSynchronize(stream));
-    for (Drain& d : drains)
-    {
-      fmd_batch* x = d.x;
-      for (int i = 0; i < d.ntodo; i++)
-      {
-        const unsigned n = x->rb_h_counts.p[d.todo[i]];
-        d.cnt[i] = std::min(n, x->rb_cap); // a full queue kept its first rb_cap records
-        dropped += n - d.cnt[i];
-        d.total += d.cnt[i];
-      }
-      if (2 * d.total > x->rb_h_recs.n && x->rb_h_recs.alloc(2 * std::max<size_t>(d.total, size_t(4) * x->C + 1024)))
-        return fail(FMD_ERR_DEVICE, "fmd_batch_collect_rds_blocks: page-locked staging allocation failed");
-      size_t at = 0;
-      for (int i = 0; i < d.ntodo; i++)
-      {
-        const int q = d.todo[i];
-        if (d.cnt[i])
-          HIPCHK(hipMemcpyAsync(x->rb_h_recs.p + 2 * at, x->rb_queue[q].p, size_t(d.cnt[i]) * 2 * sizeof(uint4),
-                                hipMemcpyDeviceToHost, stream));
-        if (x->rb_h_counts.p[q])
-          HIPCHK(hipMemsetAsync(x->rb_counts.p + q, 0, sizeof(unsigned), stream));
-        at += d.cnt[i];
-      }
-      any_recs = any_recs || d.ntodo > 0;
-    }
-    if (any_recs)
-      HIPCHK(hipStreamSynchronize(stream));
-    for (Drain& d : drains)
-    {
-      for (int i = 0; i < d.ntodo; i++)
-        d.x->rb_dirty[d.todo[i]] = false;
-      const size_t at = recs.size();
-      recs.resize(at + d.total);
-      for (size_t i = 0; i < d.total; i++)
-      { // the device record's first 24 bytes are the caller's record
-        std::memcpy(&recs[at + i], d.x->rb_h_recs.p + 2 * i, sizeof(fmd_rds_block));
-        recs[at + i].channel += d.ch0;
-      }
-    }
-  }
+  if (int rc = drain_queues(
+          b, &fmd_batch::blocks, stream, 4, true, "fmd_batch_collect_rds_blocks",
+          [lag](const fmd_batch* x, int q) { return x->rb_dirty[q] && slot_eligible(x, q, lag); },
+          [](fmd_batch* x, int q) { x->rb_dirty[q] = false; },
+          [&](const Part& p, const auto& q) {
+            dropped += q.over; // a full queue kept its first `cap` records
+            const size_t at = recs.size();
+            recs.resize(at + q.total);
+            for (size_t i = 0; i < q.total; i++)
+            { // the device record's first 24 bytes are the caller's record
+              std::memcpy(&recs[at + i], q.h_recs.p + 2 * i, sizeof(fmd_rds_block));
+              recs[at + i].channel += p.ch0;
+            }
+          }))
+    return rc;
   if (int rc = check_device_errors(b))
     return rc;
   std::sort(recs.begin(), recs.end(), [](const fmd_rds_block& x, const fmd_rds_block& y) {
@@ -3708,9 +3658,7 @@ int fmd_batch_set_debug_taps(fmd_batch* b, int enable)
 {
   if (!b)
     return fail(FMD_ERR_ARG, "null batch");
-  b->write_taps = enable != 0;
-  for (auto& sb : b->subs)
-    sb->write_taps = b->write_taps;
+  set_all(b, &fmd_batch::write_taps, enable != 0);
   return FMD_OK;
 }
 
@@ -3723,13 +3671,8 @@ int fmd_batch_set_profiling(fmd_batch* b, int level)
   // a change of execution mode starts from an idle device.
   HIPCHK(hipSetDevice(b->device));
   HIPCHK(hipDeviceSynchronize());
-  b->profiling = level < 0 ? 0 : (level > 2 ? 2 : level);
-  b->prof_calls = 0; // restart the averaging window
-  for (auto& sb : b->subs)
-  {
-    sb->profiling = b->profiling;
-    sb->prof_calls = 0;
-  }
+  set_all(b, &fmd_batch::profiling, level < 0 ? 0 : (level > 2 ? 2 : level));
+  set_all(b, &fmd_batch::prof_calls, 0u); // restart the averaging window
   return FMD_OK;
 }
 

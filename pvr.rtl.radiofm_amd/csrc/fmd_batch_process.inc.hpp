@@ -257,7 +257,7 @@ void launch_light_rds(Submit& x, hipStream_t s)
     mark_failed(b, "hipStreamWaitEvent failed in front of the bit recovery of a call");
   if (b->rb_mode == FMD_RDS_BLOCKS_OFF)
     hipLaunchKernelGGL(fmd::k_rds_bits, dim3(CP / 64), dim3(64, 1), 0, s, b->rmf.p, x.R, C, CP, k, b->st,
-                       x.ci, b->queue[x.es].p, b->qcount(x.es), b->queue_cap, b->tap_sync.p, b->write_taps);
+                       x.ci, b->groups.queue[x.es].p, b->groups.count(x.es), b->groups.cap, b->tap_sync.p, b->write_taps);
   else
   { // the observing forms (fmd_batch_set_rds_blocks): the same decoder, plus counters / block records
     fmd::RdsObs ob;
@@ -265,14 +265,14 @@ void launch_light_rds(Submit& x, hipStream_t s)
     const bool record = b->rb_mode == FMD_RDS_BLOCKS_RECORD;
     if (record)
     {
-      ob.blocks = b->rb_queue[x.es].p;
-      ob.block_count = b->rb_counts.p + x.es;
-      ob.block_cap = b->rb_cap;
+      ob.blocks = b->blocks.queue[x.es].p;
+      ob.block_count = b->blocks.count(x.es);
+      ob.block_cap = b->blocks.cap;
       b->rb_dirty[x.es] = true;
     }
     hipLaunchKernelGGL(record ? fmd::k_rds_bits_obs<true> : fmd::k_rds_bits_obs<false>, dim3(CP / 64), dim3(64, 1), 0,
-                       s, b->rmf.p, x.R, C, CP, k, b->st, x.ci, b->queue[x.es].p, b->qcount(x.es),
-                       b->queue_cap, b->tap_sync.p, b->write_taps, ob);
+                       s, b->rmf.p, x.R, C, CP, k, b->st, x.ci, b->groups.queue[x.es].p,
+                       b->groups.count(x.es), b->groups.cap, b->tap_sync.p, b->write_taps, ob);
   }
   if (!x.serial_mode && hipEventRecord(b->cev[x.es][fmd_batch::EV_RDS], s) != hipSuccess)
     mark_failed(b, "hipEventRecord failed behind the RDS part of a call");
@@ -375,7 +375,7 @@ void launch_feed(Submit& x, hipStream_t s)
   const unsigned tiles = (n + fmd::FEED_T - 1) / fmd::FEED_T;
   if (f.deliver && n)
     write_rows(
-        b, b->sel_feed, s,
+        b, b->sel[FMT_FEED], s,
         [&](const int2* ent, unsigned ns) { // (fmd_batch_select_feed): tiles of 64 entries
           const dim3 g((ns + 63) / 64, tiles);
           if (f.fmt == FMD_FEED_S16)
@@ -406,7 +406,7 @@ void launch_feed(Submit& x, hipStream_t s)
 void launch_light_audio(Submit& x, hipStream_t s)
 {
   fmd_batch* const b = x.b;
-  fmd_batch::Selection* const asel = b->sel_audio.on ? &b->sel_audio : nullptr;
+  fmd_batch::Selection* const asel = b->sel[FMT_PCM].on ? &b->sel[FMT_PCM] : nullptr;
   const fmd::Design& d = b->des;
   const unsigned C = b->C, CP = b->CP;
   if (!x.serial_mode && x.audio_after >= 0 && hipStreamWaitEvent(s, b->cev[x.es][x.audio_after], 0) != hipSuccess)
@@ -477,7 +477,7 @@ void launch_ciq(fmd_batch* b, const Out& o, int q, unsigned M, hipStream_t s)
   const unsigned per = fmd::CIQ_G * (s16 ? fmd::CiqS16::PER : fmd::CiqF32::PER); // samples of a workgroup
   const unsigned tiles = (M + per - 1) / per;
   write_rows(
-      b, b->sel_ciq, s,
+      b, b->sel[FMT_CIQ], s,
       [&](const int2* ent, unsigned n) { // (fmd_batch_select_ciq)
         if (s16)
           hipLaunchKernelGGL(fmd::k_ciq_out_sel<fmd::CiqS16>, dim3(n, tiles), dim3(fmd::CIQ_G), 0, s, b->demod[q].p,
@@ -550,7 +550,7 @@ int check_call(fmd_batch* b, const Call& c, fmd::CallPlan& pl)
   if (pl.A > b->Amax || pl.M > b->Mmax)
     return fail(FMD_ERR_STATE, "internal: plan exceeds buffer geometry");
   // (the stride lies between rows: one row per channel, or the rows of the selection)
-  if (size_t(2) * pl.A > c.audio.stride && (b->sel_audio.on ? b->sel_audio.n_total : b->C) > 1)
+  if (size_t(2) * pl.A > c.audio.stride && (b->sel[FMT_PCM].on ? b->sel[FMT_PCM].n_total : b->C) > 1)
     return fail(FMD_ERR_ARG, "audio_channel_stride smaller than the audio produced");
   if (c.mpx.p && c.mpx.stride < pl.M)
     return fail(FMD_ERR_ARG, "mpx_channel_stride smaller than the call's baseband length");
@@ -945,7 +945,7 @@ void stage_mpx(Submit& x, hipStream_t s)
   const hipEvent_t t0 = b->dbg_mpx_timing ? b->mpx_ev[x.es][0].e : nullptr;
   const hipEvent_t t1 = b->dbg_mpx_timing ? b->mpx_ev[x.es][1].e : nullptr;
   write_rows(
-      b, b->sel_mpx, s,
+      b, b->sel[FMT_MPX], s,
       [&](const int2* ent, unsigned n) { // (fmd_batch_select_mpx): tiles of 64 entries
         const dim3 g((n + 63) / 64, tiles);
         b->mpx_ev[x.es][0].in_use = t0 != nullptr;

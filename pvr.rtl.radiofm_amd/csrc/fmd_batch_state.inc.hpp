@@ -86,17 +86,16 @@ size_t host_rec_bytes()
 
 constexpr size_t kOscBytes = size_t(fmd_batch::kOscH) * sizeof(fmd::HbOsc);
 
-/* state_tab of a batch with buffers of its own: the restart's regions (build_restart_table) without a source, the
- * audio meter's rows of the float state as a group of their own, the status record, the clip counter */
+/* state_tab of a batch with buffers of its own: its carried regions (carried_regions, what a restart copies) with the
+ * audio meter's rows of the float state as a group of their own, then the status record and the clip counter */
 int ensure_state_table(fmd_batch* x)
 {
   if (x->state_tab.n)
     return FMD_OK;
-  const fmd::Design& d = x->des;
   fmd::StateTable t{};
   size_t off = 0;
   bool full = false;
-  auto add = [&](int group, void* base, unsigned rows, unsigned esz, size_t row, size_t ch) {
+  auto put = [&](int group, void* base, unsigned rows, unsigned esz, size_t row, size_t ch) {
     if (rows == 0)
       return;
     if (t.n >= fmd::kStateMaxRegions)
@@ -110,27 +109,16 @@ int ensure_state_table(fmd_batch* x)
   };
   const size_t CP = x->CP;
   static_assert(fmd::F_AUDIO_MEAN + 3 == fmd::F_SLOTS, "the audio meter's slots are the last three");
-  add(0, x->fstate.p, fmd::F_AUDIO_MEAN, 4, CP, 1);
-  add(kSkipMeter, x->st.F(fmd::F_AUDIO_MEAN), 3, 4, CP, 1);
-  add(0, x->istate.p, fmd::I_SLOTS, 4, CP, 1);
-  add(0, x->r_data.p, 4, 2, CP, 1);
-  for (int q = 0; q < 2; q++) // channel-major: element j of channel c at c * if_order + j
-    add(1, x->hist[q].p, d.if_order, 8, 1, d.if_order);
-  for (int q = 0; q < 2; q++)
-    add(2, x->brp(q), d.rs_order, 8, CP, 1);
-  for (int q = 0; q < 2; q++)
-    add(3, x->mix[q].p, unsigned(d.hb[0].len - 1), 8, CP, 1);
-  for (size_t s = 1; s < d.hb.size(); s++)
-    add(4, x->hbbuf[s - 1].p, unsigned(d.hb[s].len - 1), 8, CP, 1);
-  for (int q = 0; q < 2; q++)
-    add(5, x->rdsraw[q].p, unsigned(d.rds_lpf_taps.size() - 1), 8, CP, 1);
-  add(5, x->org.p, 1, 4, CP, 1);
-  add(6, x->rpll.p, unsigned(d.rds_mf_taps.size() - 1), 4, CP, 1);
-  add(6, x->org.p + CP, 1, 4, CP, 1);
-  for (int q = 0; q < 2; q++)
-    add(7, x->rs[q].p, unsigned(d.lpf_taps.size() - 1), 8, CP, 1);
-  add(kSkipStatus, x->d_status.p, fmd::HS_WORDS, 4, CP, 1);
-  add(kSkipMeter, x->pcm_clip.p, 1, 8, CP, 1);
+  for (const CarriedRegion& r : carried_regions(x))
+    if (r.base == x->fstate.p)
+    { // the audio meter belongs to the output: loads and imports may leave it out with the clip counter
+      put(r.group, r.base, fmd::F_AUDIO_MEAN, r.esz, r.row, r.ch);
+      put(kSkipMeter, x->st.F(fmd::F_AUDIO_MEAN), r.rows - fmd::F_AUDIO_MEAN, r.esz, r.row, r.ch);
+    }
+    else
+      put(r.group, r.base, r.rows, r.esz, r.row, r.ch);
+  put(kSkipStatus, x->d_status.p, fmd::HS_WORDS, 4, CP, 1);
+  put(kSkipMeter, x->pcm_clip.p, 1, 8, CP, 1);
   if (full)
     return fail(FMD_ERR_ARG, "this geometry has more carried regions than a state table takes");
   x->state_tab = t;
@@ -204,7 +192,7 @@ size_t blob_bytes(size_t per_channel, unsigned n, bool twin)
 /* checksum, build, geometry: everything a blob must pass before anything is touched */
 int check_blob(fmd_batch* b, const void* blob, size_t size, const char* who, StateView* v)
 {
-  fmd_batch* x0 = buffer_batches(b)[0];
+  fmd_batch* x0 = first_part(b);
   StateHeader h;
   std::memcpy(&h, blob, sizeof(h));
   const std::string w(who);
@@ -244,8 +232,8 @@ bool edits_waiting(fmd_batch* b)
 {
   if (b->edits_pending)
     return true;
-  for (fmd_batch* x : buffer_batches(b))
-    if (!x->edits.empty() || !x->imports.empty() || (x->map_on && x->map_dirty))
+  for (const Part& p : parts(b))
+    if (!p.x->edits.empty() || !p.x->imports.empty() || (p.x->map_on && p.x->map_dirty))
       return true;
   return false;
 }
@@ -282,7 +270,7 @@ const fmd::GroupDecoder* effective_gdec(fmd_batch* b, unsigned c, int* fresh)
 void write_host_part(fmd_batch* b, const unsigned* channels, unsigned n, uint32_t flags, char* blob, size_t total,
                      size_t* payload_at)
 {
-  fmd_batch* x0 = buffer_batches(b)[0];
+  fmd_batch* x0 = first_part(b);
   std::memset(blob, 0, sizeof(StateHeader) + kOscBytes + size_t(n) * host_rec_bytes());
   StateHeader h{};
   h.magic = kStateMagic;
@@ -296,8 +284,8 @@ void write_host_part(fmd_batch* b, const unsigned* channels, unsigned n, uint32_
   h.n_cap = b->map_on ? b->n_cap : 0;
   h.total_bytes = total;
   bool origins = false;
-  for (fmd_batch* x : buffer_batches(b))
-    origins = origins || x->origins_live;
+  for (const Part& p : parts(b))
+    origins = origins || p.x->origins_live;
   h.flags = flags | (origins ? SF_ORIGINS : 0u) | (x0->osc_on ? SF_OSC : 0u) | (b->map_on ? SF_MAP : 0u);
   char* p = blob + sizeof(StateHeader);
   if (x0->osc_on && x0->h_osc.p) // what the next call copies in front of its own entries (upload_oscillator)
@@ -362,13 +350,10 @@ fmd::StateTable table_without(const fmd_batch* x, int skip)
 /* the listed channels (null: all) of b, packed into dev[0 .. n * state_bytes): one launch per batch with buffers */
 int export_payload(fmd_batch* b, const unsigned* channels, unsigned n, char* dev)
 {
-  const std::vector<fmd_batch*> xs = buffer_batches(b);
   DevBuf<fmd::StateEdit> d_list;
   std::vector<fmd::StateEdit> list;
-  for (size_t k = 0; k < xs.size(); k++)
+  for (const auto& [x, ch0] : parts(b))
   {
-    fmd_batch* x = xs[k];
-    const unsigned ch0 = is_shell(b) ? b->sub_ch0[k] : 0u;
     if (!channels)
     {
       hipLaunchKernelGGL(fmd::k_channel_export, dim3(state_blocks(x->C), x->state_tab.n), dim3(256), 0, nullptr,
@@ -403,15 +388,15 @@ int save_impl(fmd_batch* b, const unsigned* channels, unsigned n, void* blob, si
                                    "applied yet): make the next call first");
   if (int rc = drain_batch(b))
     return rc;
-  for (fmd_batch* x : buffer_batches(b))
-    if (int rc = ensure_state_table(x))
+  for (const Part& p : parts(b))
+    if (int rc = ensure_state_table(p.x))
       return rc;
   const bool whole = channels == nullptr;
   fmd_batch* tw = whole ? b->twin.get() : nullptr;
   if (tw)
     if (int rc = ensure_state_table(tw))
       return rc;
-  const size_t per = buffer_batches(b)[0]->state_bytes;
+  const size_t per = first_part(b)->state_bytes;
   const size_t total = blob_bytes(per, n, tw != nullptr);
   if (written)
     *written = total;
@@ -506,8 +491,8 @@ void take_clock(fmd_batch* x, const StateView& v)
 /* the second half of a load: every write (load_impl has checked the blob and staged the payload at dev) */
 int load_replace(fmd_batch* b, const StateView& v, char* dev_p, const char* who)
 {
-  const std::vector<fmd_batch*> xs = buffer_batches(b);
-  const size_t per = xs[0]->state_bytes;
+  const std::vector<Part> ps = parts(b);
+  const size_t per = ps[0].x->state_bytes;
   const int skip = b->state_skip;
   const unsigned T = b->des.table_size;
   b->gdec_imports.clear();
@@ -520,10 +505,8 @@ int load_replace(fmd_batch* b, const StateView& v, char* dev_p, const char* who)
       log.clear();
   }
   std::fill(b->gdec_epoch.begin(), b->gdec_epoch.end(), 0u);
-  for (size_t k = 0; k < xs.size(); k++)
+  for (const auto& [x, ch0] : ps)
   {
-    fmd_batch* x = xs[k];
-    const unsigned ch0 = is_shell(b) ? b->sub_ch0[k] : 0u;
     const fmd::StateTable tab = table_without(x, skip);
     hipLaunchKernelGGL(fmd::k_channel_import, dim3(state_blocks(x->C), tab.n + 1), dim3(256), 0, nullptr, tab,
                        (const fmd::StateEdit*)nullptr, x->C, (const void*)dev_p, b->C, ch0, (const float2*)nullptr,
@@ -557,10 +540,10 @@ int load_replace(fmd_batch* b, const StateView& v, char* dev_p, const char* who)
     x->edits.clear();
     x->imports.clear();
     take_clock(x, v);
-    HIPCHK(hipMemset(x->queue_counts.p, 0, fmd_batch::NSLOT * sizeof(unsigned))); // queued groups are dropped
-    if (x->rb_counts.p) // ... and queued block records (the counters of the observation stay: not the decoder's)
+    HIPCHK(hipMemset(x->groups.counts.p, 0, fmd_batch::NSLOT * sizeof(unsigned))); // queued groups are dropped
+    if (x->blocks.counts.p) // ... and queued block records (the counters of the observation stay: not the decoder's)
     {
-      HIPCHK(hipMemset(x->rb_counts.p, 0, fmd_batch::NSLOT * sizeof(unsigned)));
+      HIPCHK(hipMemset(x->blocks.counts.p, 0, fmd_batch::NSLOT * sizeof(unsigned)));
       std::memset(x->rb_dirty, 0, sizeof(x->rb_dirty));
     }
     if (x->h_err.p)
@@ -586,54 +569,45 @@ int load_replace(fmd_batch* b, const StateView& v, char* dev_p, const char* who)
   HIPCHK(hipDeviceSynchronize());
   // a destination that keeps the oscillator sequence where the source did not: the sequence's state is every
   // channel's own copy of it (k_demod_serial leaves it in F_OSC_RE / F_OSC_IM in either form)
-  for (fmd_batch* x : xs)
-    if (x->osc_warm)
+  for (const Part& p : ps)
+    if (p.x->osc_warm)
     {
-      HIPCHK(hipMemcpy(&x->osc_re, x->st.F(fmd::F_OSC_RE), sizeof(float), hipMemcpyDeviceToHost));
-      HIPCHK(hipMemcpy(&x->osc_im, x->st.F(fmd::F_OSC_IM), sizeof(float), hipMemcpyDeviceToHost));
+      HIPCHK(hipMemcpy(&p.x->osc_re, p.x->st.F(fmd::F_OSC_RE), sizeof(float), hipMemcpyDeviceToHost));
+      HIPCHK(hipMemcpy(&p.x->osc_im, p.x->st.F(fmd::F_OSC_IM), sizeof(float), hipMemcpyDeviceToHost));
     }
   // the capture map as the next call reads it
   if (v.h->flags & SF_MAP)
   {
-    b->cpc = 1;
-    for (fmd_batch* x : xs)
-      x->cpc = 1;
+    set_all(b, &fmd_batch::cpc, 1u);
     if (int rc = ensure_map(b, who))
       return rc;
-    for (size_t k = 0; k < xs.size(); k++)
+    for (const auto& [x, ch0] : ps)
     {
-      fmd_batch* x = xs[k];
-      const unsigned ch0 = is_shell(b) ? b->sub_ch0[k] : 0u;
       for (unsigned c = 0; c < x->C; c++)
       {
         StateHostRec r;
         std::memcpy(&r, v.recs + size_t(ch0 + c) * host_rec_bytes(), sizeof(r));
         x->cmap[c] = r.capture;
       }
-      x->n_cap = v.h->n_cap;
       x->map_dirty = true; // (part of the load: the next call uploads the walk like any call behind a switch)
     }
-    b->n_cap = v.h->n_cap;
+    set_all(b, &fmd_batch::n_cap, v.h->n_cap);
   }
   else
   {
-    b->cpc = v.h->cpc;
-    b->map_on = false;
-    b->n_cap = 0;
-    for (fmd_batch* x : xs)
-    {
-      x->cpc = v.h->cpc;
-      x->map_on = false;
-      x->map_dirty = false;
-      x->n_cap = 0;
-    }
+    set_all(b, &fmd_batch::cpc, v.h->cpc);
+    set_all(b, &fmd_batch::map_on, false);
+    set_all(b, &fmd_batch::n_cap, 0u);
+    for (const Part& p : ps)
+      p.x->map_dirty = false;
   }
   if (is_shell(b))
   {
-    __atomic_store_n(&b->call_index, xs[0]->call_index, __ATOMIC_RELAXED);
-    b->lastM = xs[0]->lastM;
-    b->lastA = xs[0]->lastA;
-    b->lastR = xs[0]->lastR;
+    const fmd_batch* x0 = ps[0].x;
+    __atomic_store_n(&b->call_index, x0->call_index, __ATOMIC_RELAXED);
+    b->lastM = x0->lastM;
+    b->lastA = x0->lastA;
+    b->lastR = x0->lastR;
   }
   b->failed = false;
   b->fail_msg.clear();
@@ -644,9 +618,8 @@ int load_impl(fmd_batch* b, const void* blob, size_t size)
 {
   const char* who = "fmd_batch_load_state";
   HIPCHK(hipSetDevice(b->device));
-  const std::vector<fmd_batch*> xs = buffer_batches(b);
-  for (fmd_batch* x : xs)
-    if (int rc = ensure_state_table(x))
+  for (const Part& p : parts(b))
+    if (int rc = ensure_state_table(p.x))
       return rc;
   if (b->twin)
     if (int rc = ensure_state_table(b->twin.get()))
@@ -669,7 +642,7 @@ int load_impl(fmd_batch* b, const void* blob, size_t size)
     return fail(FMD_ERR_ARG, std::string(who) + ": the blob's channels per capture do not divide the channel count");
   (void)wait_impl(b, 0, nullptr, false); // (a failed batch may be loaded into)
   HIPCHK(hipDeviceSynchronize());
-  const size_t per = xs[0]->state_bytes;
+  const size_t per = first_part(b)->state_bytes;
   DevBuf<char> dev;
   if (dev.alloc(size_t(b->C) * per + per))
     return fail(FMD_ERR_DEVICE, std::string(who) + ": device allocation failed");
@@ -719,9 +692,9 @@ int import_impl(fmd_batch* b, const unsigned* channels, unsigned n, const void* 
   if (int rc = check_channel_list(b, channels, nullptr, n, who))
     return rc;
   HIPCHK(hipSetDevice(b->device));
-  const std::vector<fmd_batch*> xs = buffer_batches(b);
-  for (fmd_batch* x : xs)
-    if (int rc = ensure_state_table(x))
+  const std::vector<Part> ps = parts(b);
+  for (const Part& p : ps)
+    if (int rc = ensure_state_table(p.x))
       return rc;
   StateView v;
   if (int rc = check_blob(b, blob, size, who, &v))
@@ -729,12 +702,12 @@ int import_impl(fmd_batch* b, const unsigned* channels, unsigned n, const void* 
   if (v.h->n_channels != n)
     return fail(FMD_ERR_ARG, std::string(who) + ": the blob holds " + std::to_string(v.h->n_channels) +
                                  " channels, the list names " + std::to_string(n));
-  if (const char* word = clock_difference(xs[0], v))
+  if (const char* word = clock_difference(ps[0].x, v))
     return fail(FMD_ERR_STATE, std::string(who) + ": the blob's clock differs from the batch's in front of its next "
                                                   "call, first in " + word +
                                    ": a decoder continues only in a batch fed the same sequence of call sizes");
   const unsigned T = b->des.table_size;
-  const size_t per = xs[0]->state_bytes;
+  const size_t per = ps[0].x->state_bytes;
   // ---- per batch with buffers: its channels of the list, sorted, and the tuner rows they need ----
   struct Plan
   {
@@ -743,10 +716,8 @@ int import_impl(fmd_batch* b, const unsigned* channels, unsigned n, const void* 
     std::vector<int> row_shift;
   };
   std::vector<Plan> plans;
-  for (size_t k = 0; k < xs.size(); k++)
+  for (const auto& [x, ch0] : ps)
   {
-    fmd_batch* x = xs[k];
-    const unsigned ch0 = is_shell(b) ? b->sub_ch0[k] : 0u;
     Plan pl{x, {}, {}};
     std::map<int, int> row_of;
     for (unsigned i = 0; i < n; i++)
@@ -886,10 +857,10 @@ size_t fmd_batch_state_size(const fmd_batch* b, unsigned n_channels)
   fmd_batch* m = const_cast<fmd_batch*>(b);
   if (hipSetDevice(b->device) != hipSuccess)
     return 0;
-  for (fmd_batch* x : buffer_batches(m))
-    if (ensure_state_table(x))
+  for (const Part& p : parts(m))
+    if (ensure_state_table(p.x))
       return 0;
-  return blob_bytes(buffer_batches(m)[0]->state_bytes, n_channels, n_channels == b->C && b->twin != nullptr);
+  return blob_bytes(first_part(m)->state_bytes, n_channels, n_channels == b->C && b->twin != nullptr);
 }
 
 int fmd_batch_save_state(fmd_batch* b, void* blob, size_t cap, size_t* written)
@@ -959,9 +930,7 @@ int fmd_batch_debug_state_skip(fmd_batch* b, int region)
     return fail(FMD_ERR_ARG, "fmd_batch_debug_state_skip: -1 or the index of a region (" + names +
                                  "status record, group decoder, audio meter / clip counter)");
   }
-  b->state_skip = region;
-  for (auto& sb : b->subs)
-    sb->state_skip = region;
+  set_all(b, &fmd_batch::state_skip, region);
   if (b->twin)
     b->twin->state_skip = region;
   return FMD_OK;

@@ -586,6 +586,146 @@ void other_geometries()
     r.wait();
   }
 }
+/* one line per state blob: its size and a 64-bit FNV-1a of its bytes (the header carries the state table's
+ * fingerprint, the payload every region's bytes: rows, element sizes, offsets and groups of the table are pinned) */
+void blob_line(const char* what, const void* p, size_t n)
+{
+  uint64_t h = 1469598103934665603ull;
+  for (size_t i = 0; i < n; i++)
+    h = (h ^ static_cast<const unsigned char*>(p)[i]) * 1099511628211ull;
+  printf("blob %s %zu bytes fnv1a %016llx\n", what, n, static_cast<unsigned long long>(h));
+}
+
+/* The host code around the call path: the walk over a batch's parts (a plain batch, C = 192; a shell over two
+ * sub-batches, C = 8200), the record queues' drains, the carried regions of save / load / export / import and of a
+ * retune, and the settings a shell mirrors into its sub-batches. */
+void parts_regions_queues()
+{
+  {
+    Run r("parts C=8200 set_rds_blocks 2, collect_rds_blocks lag 0 and 2", kRef, 8200, 2);
+    OK(fmd_batch_set_rds_blocks(r.b, 2, 0));
+    r.calls(kSizes, 3);
+    std::vector<fmd_rds_block> out(64);
+    unsigned lost = 0;
+    OK(fmd_batch_collect_rds_blocks(r.b, out.data(), 64, 0, nullptr, &lost));
+    r.calls(kSizes + 1, 3);
+    OK(fmd_batch_collect_rds_blocks(r.b, out.data(), 64, 2, nullptr, &lost));
+    r.call(kSizes[0]);
+    OK(fmd_batch_collect_rds_blocks(r.b, out.data(), 64, 0, nullptr, &lost));
+    r.call(kSizes[1]);
+    r.wait();
+  }
+  for (unsigned C : {192u, 8200u})
+    for (int lag : {0, 2})
+    {
+      {
+        Run r(nm("parts C=%u collect_rds_lagged lag %d", C, lag), kRef, C, 2);
+        r.calls(kSizes, 3);
+        std::vector<fmd_rds_group> out(64);
+        OK(fmd_batch_collect_rds_lagged(r.b, out.data(), 64, 1, lag, nullptr));
+        r.call(kSizes[3]);
+        OK(fmd_batch_collect_rds_lagged(r.b, out.data(), 64, 0, lag, nullptr)); // (the slots the first one left)
+        r.call(kSizes[0]);
+        r.wait();
+      }
+      {
+        Run r(nm("parts C=%u export_rds_device lag %d", C, lag), kRef, C, 2);
+        const unsigned cap = 256;
+        void* d_records = rows(size_t(cap) * 16); // (real memory: the double's hipMemsetAsync writes it)
+        r.calls(kSizes, 3);
+        OK(fmd_batch_export_rds_device(r.b, static_cast<int32_t*>(d_records), cap, 1000, lag, nullptr));
+        r.call(kSizes[3]);
+        r.scenario(nm("parts C=%u export_rds_device lag %d, the drained slots come round again", C, lag));
+        rec_busy(1); // (the drained events have not completed: the calls that reuse the slots wait for them)
+        for (int i = 0; i < 8; i++)
+          r.call(kSizes[i % 4]);
+        rec_busy(0);
+        OK(fmd_batch_export_rds_device(r.b, static_cast<int32_t*>(d_records), cap, 0, lag, nullptr));
+        r.call(kSizes[1]);
+        r.wait();
+        free(d_records);
+      }
+    }
+  for (unsigned C : {8200u, 192u})
+  { // channels on both sides of the sub-batch border (C = 8200: 4224 + 3976); C = 192: with a retune in front
+    Run r(nm("parts C=%u export_channels, import_channels, save_state, load_state%s", C,
+             C == 192 ? " behind a retune" : ""),
+          kRef, C, 2);
+    if (C == 192)
+      OK(fmd_batch_enable_retune(r.b));
+    r.calls(kSizes, 3);
+    if (C == 192)
+    {
+      const unsigned ch[2] = {3, 190};
+      const int sh[2] = {5, -9};
+      OK(fmd_batch_retune_channels(r.b, ch, sh, 2));
+      r.calls(kSizes + 1, 2);
+    }
+    const unsigned ch[4] = {C - 1, 7, C / 2 + 200 < C ? C / 2 + 200 : 100, C / 2 - 50};
+    const unsigned to[4] = {8, C - 2, 9, C / 2 + 30};
+    std::vector<char> blob(fmd_batch_state_size(r.b, 4));
+    size_t got = 0, all_n = 0;
+    OK(fmd_batch_export_channels(r.b, ch, 4, blob.data(), blob.size(), &got));
+    blob_line("export_channels", blob.data(), got);
+    OK(fmd_batch_import_channels(r.b, to, 4, blob.data(), got));
+    r.calls(kSizes + 1, 3);
+    std::vector<char> all(fmd_batch_state_size(r.b, C));
+    OK(fmd_batch_save_state(r.b, all.data(), all.size(), &all_n));
+    blob_line("save_state", all.data(), all_n);
+    OK(fmd_batch_load_state(r.b, all.data(), all_n));
+    r.calls(kSizes, 2);
+    r.scenario(nm("parts C=%u debug_state_skip 4, import and load again", C));
+    OK(fmd_batch_debug_state_skip(r.b, 4));
+    OK(fmd_batch_export_channels(r.b, ch, 4, blob.data(), blob.size(), &got)); // (a blob of the batch's clock)
+    OK(fmd_batch_import_channels(r.b, to, 4, blob.data(), got));
+    r.calls(kSizes, 2);
+    OK(fmd_batch_load_state(r.b, all.data(), all_n));
+    r.calls(kSizes + 2, 2);
+    OK(fmd_batch_save_state(r.b, all.data(), all.size(), &all_n));
+    blob_line("save_state behind the skipped load", all.data(), all_n);
+    r.wait();
+  }
+  { // every setter that mirrors a setting into the sub-batches; two calls behind each
+    Run r("parts C=8200 set_debug_taps", kRef, 8200, 2);
+    OK(fmd_batch_enable_retune(r.b));
+    r.calls(kSizes, 2);
+    OK(fmd_batch_set_debug_taps(r.b, 1));
+    r.calls(kSizes, 2);
+    r.scenario("parts C=8200 set_profiling 1");
+    OK(fmd_batch_set_profiling(r.b, 1));
+    r.calls(kSizes + 1, 2);
+    float ms[32];
+    OK(fmd_batch_get_stage_ms(r.b, ms, 32));
+    OK(fmd_batch_set_profiling(r.b, 0));
+    r.scenario("parts C=8200 set_channels_per_capture 8");
+    OK(fmd_batch_set_channels_per_capture(r.b, 8));
+    r.iq_stride = 65536;
+    r.calls(kSizes + 2, 2);
+    OK(fmd_batch_set_channels_per_capture(r.b, 1));
+    r.iq_stride = 0;
+    r.scenario("parts C=8200 debug_restart_skip 2, retunes on both sides of the border");
+    OK(fmd_batch_debug_restart_skip(r.b, 2));
+    const unsigned ch[3] = {1, 4300, 8199};
+    const int sh[3] = {5, -9, 2};
+    OK(fmd_batch_retune_channels(r.b, ch, sh, 3));
+    r.calls(kSizes, 2);
+    OK(fmd_batch_debug_restart_skip(r.b, -1));
+    r.scenario("parts C=8200 debug_state_skip 1, an import on both sides of the border");
+    std::vector<char> blob(fmd_batch_state_size(r.b, 3));
+    size_t got = 0;
+    OK(fmd_batch_export_channels(r.b, ch, 3, blob.data(), blob.size(), &got));
+    blob_line("export_channels", blob.data(), got);
+    OK(fmd_batch_debug_state_skip(r.b, 1));
+    OK(fmd_batch_import_channels(r.b, ch, 3, blob.data(), got));
+    r.calls(kSizes + 1, 2);
+    OK(fmd_batch_debug_state_skip(r.b, -1));
+    r.scenario("parts C=8200 debug_reset_keep_ring_phase 1, resets on both sides of the border");
+    OK(fmd_batch_debug_reset_keep_ring_phase(r.b, 1));
+    OK(fmd_batch_reset_channels(r.b, ch, 3));
+    r.calls(kSizes + 2, 2);
+    r.wait();
+  }
+}
 } // namespace
 
 int main()
@@ -603,5 +743,6 @@ int main()
   busy_caller();
   short_calls();
   other_geometries();
+  parts_regions_queues();
   return 0;
 }

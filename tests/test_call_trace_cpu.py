@@ -8,7 +8,9 @@ a SHA-256 of the whole scenario (setup calls included) and the trace of the last
 few lines in which it differs from an earlier scenario's), has to equal tests/golden/call_trace.txt byte for byte.
 The golden was recorded from the csrc/ of the commit in front of the one that split the call path into stages and schedules, and is the record of which kernel goes to which stream behind
 which event: a change of the submission order shows up here as a readable diff, and is either a bug or comes with a
-new golden and a GPU run.
+new golden and a GPU run.  The scenarios of the driver's parts_regions_queues (collects, the device export, state blobs
+with their size and hash, the settings a shell mirrors) were added to it from the csrc/ of the commit in front of the
+one that brought parts(), carried_regions() and drain_queues(): lines added, none changed.
 
 What is not pinned: kernel arguments (which buffer a launch gets) -- the bit-exact GPU tests hold those.
 
