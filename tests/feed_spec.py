@@ -20,6 +20,14 @@ def s16(y):
     return np.where(np.isnan(v), 0, r).astype(np.int16)
 
 
+def mpx16(x):
+    """FMD_MPX_S16 and both parts of FMD_CIQ_S16: saturate_int16(round_half_even(x * 8192.0f)), NaN gives 0"""
+    y = np.asarray(x, F32) * F32(8192.0)
+    with np.errstate(invalid="ignore"):
+        r = np.clip(np.rint(y), -32768.0, 32767.0)
+    return np.where(np.isnan(y), 0, r).astype(np.int16)
+
+
 def mono(audio):
     """x of interleaved L, R float32 rows [..., 2 A] -> [..., A]: (L + R) * 0.5f in float32"""
     a = np.asarray(audio, F32)

@@ -16,7 +16,7 @@ import pytest
 
 import edit_model as em
 from __graft_entry__ import load_package
-from test_mpx_cabi_cpu import mpx16
+from feed_spec import mpx16
 
 pytestmark = pytest.mark.gpu
 

@@ -17,7 +17,7 @@ import pytest
 
 import feed_spec
 from __graft_entry__ import load_package
-from test_mpx_cabi_cpu import mpx16
+from feed_spec import mpx16
 
 pytestmark = pytest.mark.gpu
 

@@ -14,19 +14,13 @@ import numpy as np
 import pytest
 
 from __graft_entry__ import load_package
+from feed_spec import mpx16
 
 pytestmark = pytest.mark.gpu
 
 N = 65536
 FILL16 = 0x5A5A
 FILL32 = 0x5A5A5A5A
-
-
-def mpx16(x):
-    y = np.asarray(x, np.float32) * np.float32(8192.0)
-    with np.errstate(invalid="ignore"):
-        r = np.clip(np.rint(y), -32768.0, 32767.0)
-    return np.where(np.isnan(y), 0, r).astype(np.int16)
 
 
 def value_sets():

@@ -13,18 +13,12 @@ import numpy as np
 import pytest
 
 from __graft_entry__ import PKG_DIR, ROOT, load_package
+from feed_spec import mpx16
 
 FMD_ERR_ARG = -1
 SYMBOLS = ("fmd_batch_process_device_mpx", "fmd_batch_process_host_mpx", "fmd_process_stream_mpx",
            "fmd_batch_max_mpx_samples", "fmd_batch_mpx_rate")
 PROCESS = SYMBOLS[:3]
-
-
-def mpx16(x):
-    y = np.asarray(x, np.float32) * np.float32(8192.0)
-    with np.errstate(invalid="ignore"):
-        r = np.clip(np.rint(y), -32768.0, 32767.0)
-    return np.where(np.isnan(y), 0, r).astype(np.int16)
 
 
 def value_sets():
