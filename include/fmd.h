@@ -1247,6 +1247,84 @@ int fmd_split_process_device(fmd_split* s, const void* d_in, int iq_format, size
 int fmd_split_process_host(fmd_split* s, const void* in, int iq_format, size_t in_capture_stride, unsigned samples,
                            void* out, size_t out_row_stride, unsigned* out_samples);
 
+/* ---- polyphase channeliser: a wideband capture's stations as channel IQ rows ------------- */
+/* All stations of a wideband capture sit on one raster (100 kHz) and share one prototype low-pass: the capture is
+ * filtered ONCE into its N branch sums, and every wanted station is one rotation of them -- a polyphase filter bank.
+ * The rows leave at fs / D as complex64 channel IQ, what a FMD_IN_CIQ_F32 call takes in place of the IF stage: wide
+ * capture -> channeliser -> FMD_IN_CIQ_F32 call, with no band rows, no capture map and no IF stage in between.  Like
+ * the splitter, a channeliser owns no stream and touches no fmd_batch; it runs asynchronously on the caller's stream.
+ *
+ * Geometry: G = n_captures, B = n_rows_per_capture, G B output rows; row r = g B + b reads capture g and carries bin
+ * shifts[r], any int, taken mod N: its centre is -shift fs / N (the convention of fmd_batch_create's tuning_shifts
+ * with table_size N).  Duplicate shifts in a capture are allowed.
+ * Definition (exact arithmetic).  q counts a capture's input samples since create / reset; x[q] is the input sample
+ * converted as the decoder converts FMD_IQ_*; x[q] = 0 for q < 0; c[1..K] = fmd_design_lanczos(K, cutoff)[1..K], taken
+ * as data.  For every q that is a multiple of D
+ *     y_s[q] = out_scale * sum_{j = 1..K} x[q - j] c[j] 2 exp(+2 pi i s ((q - j) mod N) / N)
+ * -- the reference's cFineTuner (table size N, shift s) followed by cDownsampleFilter, the splitter's definition with
+ * T = N and R = D.  What is computed is the polyphase identity
+ *     u_q[r] = sum over j with (q - j) = r (mod N) of c[j] x[q - j],   y_s[q] = 2 out_scale sum_r u_q[r] e^{2 pi i s r / N}
+ * in float32, so the rows are NOT bit for bit the reference's (a filter bank cannot sum in its order); they are no less
+ * accurate than the reference's own float32 arithmetic (against the definition in float64: a row's RMS error is at most
+ * that of the reference's arithmetic on that row).
+ * A call of `samples` >= 1 delivers to every row the outputs whose q falls inside the call -- the same count for all
+ * rows, known on the host when the call returns (*out_samples).  History and phase carry over calls of any size.  Row
+ * elements beyond the count are not written.
+ * The carried state is the RAW history (the last K input samples of every capture) and q: fmd_chan_set_shifts makes
+ * every row, from the next call submitted, bit for bit the row of a channeliser that always had those shifts, without
+ * waiting for the device; fmd_chan_reset gives the rows of a new one.
+ * Determinism: a row's bits depend on its capture's sample stream, its own shift and the parameters alone -- not on G,
+ * B, the other rows' shifts, the row's index, the call sizes, the tiling, the stream or the entry point.
+ * Non-finite input: an output whose window holds a non-finite sample is non-finite (NaN or inf, not specified) in
+ * every row of that capture; every other output of that capture and every other capture keep their bits.
+ * Errors, worded like the splitter's: FMD_ERR_ARG (with a sentence naming the field) for null arguments, a parameter
+ * out of range, a geometry whose tile (31 D + K window samples and N branch sums of 32 output times) does not fit a
+ * workgroup's LDS, a format outside FMD_IQ_* (FMD_REAL_* and FMD_IN_CIQ_* get a sentence of their own), a stride
+ * shorter than the call with more than one capture or row, a misaligned pointer -- all before the HIP runtime is
+ * touched; FMD_ERR_DEVICE "no HIP device" without a GPU; FMD_ERR_SIZE for samples of 0 or above FMD_CHAN_MAX_SAMPLES.
+ * A refused call leaves the channeliser as it was.  One thread at a time per channeliser; its calls go on one stream
+ * (or streams the caller orders).
+ * Not offered: real-sampled input (FMD_REAL_*), int16 rows, saving a channeliser's state, a form for N above 256. */
+#define FMD_CHAN_MAX_SAMPLES 16777216u /* input samples per capture and call */
+typedef struct fmd_chan_params
+{
+  double sample_rate_in; /* > 0 */
+  unsigned n_bins;       /* N: 2..256, any integer (96, 100, 192, 200 are the real ones); the raster is fs / N */
+  unsigned decimation;   /* D: 2..256; the rows leave at fs / D; no relation to N is required */
+  unsigned filter_order; /* K: 2..4096; 0 = 8 D, the reference's rule (FmDecode.cpp:262) */
+  double cutoff;         /* fraction of the input rate, (0, 0.5]; 0 = 0.6 / D, the reference's */
+  float out_scale;       /* any finite float; 0 = 1.0f: the rows carry the tuner's factor 2, as FMD_IN_CIQ_* wants */
+} fmd_chan_params;
+typedef struct fmd_chan fmd_chan;
+
+/* n_captures, n_rows_per_capture >= 1, at most 65535 captures and 2^20 rows; shifts[n_captures * n_rows_per_capture] */
+int fmd_chan_create(const fmd_chan_params* p, unsigned n_captures, unsigned n_rows_per_capture, const int* shifts,
+                    int device, fmd_chan** out);
+void fmd_chan_destroy(fmd_chan* c);
+/* zero history, q = 0 (asynchronously on stream) */
+int fmd_chan_reset(fmd_chan* c, void* stream);
+/* new shifts for all n_rows = G B rows, from the next call submitted; returns without waiting for the device */
+int fmd_chan_set_shifts(fmd_chan* c, const int* shifts, unsigned n_rows);
+/* G B;  fs / D;  the most outputs per row a call of `samples` can deliver: ceil(samples / D) */
+int fmd_chan_rows(const fmd_chan* c);
+double fmd_chan_out_rate(const fmd_chan* c);
+unsigned fmd_chan_max_out_samples(const fmd_chan* c, unsigned samples);
+/* the K taps in use (c[1..K]); returns K, nothing past cap is written */
+int fmd_chan_get_taps(const fmd_chan* c, float* out, unsigned cap);
+/* Testing aid, no part of the contract: the input samples one workgroup's tile of outputs covers (32 D). */
+unsigned fmd_chan_tile_samples(const fmd_chan* c);
+/* Capture g starts g * in_capture_stride IQ samples of iq_format (FMD_IQ_F32 / _U8 / _S8 / _S16) behind d_in (pointer
+ * and stride: multiples of two IQ samples, as fmd_split_process_device); row r starts r * out_row_stride complex64
+ * samples behind d_out, which must be 16-byte aligned, out_row_stride even and >= the call's count
+ * (fmd_chan_max_out_samples always is, rounded up to even): exactly the rows a FMD_IN_CIQ_F32 device call takes, so a
+ * row buffer is handed over on the same stream without a copy.  *out_samples (optional) = the count. */
+int fmd_chan_process_device(fmd_chan* c, const void* d_in, int iq_format, size_t in_capture_stride, unsigned samples,
+                            void* d_out, size_t out_row_stride, unsigned* out_samples, void* stream);
+/* The same from and to pageable host memory, any alignment; out_row_stride any value >= the count, odd ones too.  It
+ * waits. */
+int fmd_chan_process_host(fmd_chan* c, const void* in, int iq_format, size_t in_capture_stride, unsigned samples,
+                          void* out, size_t out_row_stride, unsigned* out_samples);
+
 /* ---- host-only pieces (no GPU needed) ----------------------------------------------- */
 /* UECP group decoder = cRDSGroupDecoder (RDSGroupDecoder.cpp:166-1001). */
 typedef struct fmd_group_decoder fmd_group_decoder;

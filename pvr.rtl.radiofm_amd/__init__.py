@@ -144,6 +144,12 @@ class FmdSplitParams(C.Structure):
                 ("cutoff", C.c_double), ("table_size", C.c_uint), ("out_scale", C.c_float)]
 
 
+class FmdChanParams(C.Structure):
+    """fmd_chan_params (include/fmd.h): 0 = the field's default (n_bins and decimation have none)."""
+    _fields_ = [("sample_rate_in", C.c_double), ("n_bins", C.c_uint), ("decimation", C.c_uint),
+                ("filter_order", C.c_uint), ("cutoff", C.c_double), ("out_scale", C.c_float)]
+
+
 class FmdScanCandidate(C.Structure):
     _fields_ = [("shift", C.c_int32), ("offset_hz", C.c_float), ("power_db", C.c_float), ("snr_db", C.c_float)]
 
@@ -262,6 +268,9 @@ EXPORTS = [
     "fmd_split_out_rate", "fmd_split_max_out_samples", "fmd_split_get_taps", "fmd_split_tile_samples",
     "fmd_split_debug_table_versions", "fmd_split_process_device", "fmd_split_process_host",
     "fmd_split_create_real",
+    "fmd_chan_create", "fmd_chan_destroy", "fmd_chan_reset", "fmd_chan_set_shifts", "fmd_chan_rows",
+    "fmd_chan_out_rate", "fmd_chan_max_out_samples", "fmd_chan_get_taps", "fmd_chan_tile_samples",
+    "fmd_chan_process_device", "fmd_chan_process_host",
 ]
 
 
@@ -456,6 +465,21 @@ def lib():
         L.fmd_split_debug_table_versions.argtypes = [vp]
         L.fmd_split_process_device.argtypes = [vp, vp, i, C.c_size_t, u, vp, C.c_size_t, C.POINTER(u), vp]
         L.fmd_split_process_host.argtypes = [vp, vp, i, C.c_size_t, u, vp, C.c_size_t, C.POINTER(u)]
+        L.fmd_chan_create.argtypes = [C.POINTER(FmdChanParams), u, u, vp, i, C.POINTER(vp)]
+        L.fmd_chan_destroy.argtypes = [vp]
+        L.fmd_chan_destroy.restype = None
+        L.fmd_chan_reset.argtypes = [vp, vp]
+        L.fmd_chan_set_shifts.argtypes = [vp, vp, u]
+        L.fmd_chan_rows.argtypes = [vp]
+        L.fmd_chan_out_rate.restype = C.c_double
+        L.fmd_chan_out_rate.argtypes = [vp]
+        L.fmd_chan_max_out_samples.restype = u
+        L.fmd_chan_max_out_samples.argtypes = [vp, u]
+        L.fmd_chan_get_taps.argtypes = [vp, vp, u]
+        L.fmd_chan_tile_samples.restype = u
+        L.fmd_chan_tile_samples.argtypes = [vp]
+        L.fmd_chan_process_device.argtypes = [vp, vp, i, C.c_size_t, u, vp, C.c_size_t, C.POINTER(u), vp]
+        L.fmd_chan_process_host.argtypes = [vp, vp, i, C.c_size_t, u, vp, C.c_size_t, C.POINTER(u)]
         _LIB = L
     return _LIB
 

@@ -1702,6 +1702,7 @@ void build_walk(const fmd_batch* b, uint2* out)
 #include "fmd_batch_process.inc.hpp" // submit_call: one call on the batch's streams, stage by stage
 #include "fmd_scan.inc.hpp"          // fmd_scan_*: the band scan (its own object, the caller's stream)
 #include "fmd_split.inc.hpp"         // fmd_split_*: the band splitter (its own object, the caller's stream)
+#include "fmd_chan.inc.hpp"          // fmd_chan_*: the polyphase channeliser (likewise)
 
 namespace
 {
