@@ -1284,12 +1284,38 @@ int fmd_split_process_host(fmd_split* s, const void* in, int iq_format, size_t i
  * touched; FMD_ERR_DEVICE "no HIP device" without a GPU; FMD_ERR_SIZE for samples of 0 or above FMD_CHAN_MAX_SAMPLES.
  * A refused call leaves the channeliser as it was.  One thread at a time per channeliser; its calls go on one stream
  * (or streams the caller orders).
- * Not offered: real-sampled input (FMD_REAL_*), int16 rows, saving a channeliser's state, a form for N above 256. */
+ * Not offered by fmd_chan_create and fmd_chan_process_device / _host as such: real-sampled input (FMD_REAL_*),
+ * int16 rows, saving a channeliser's state, a form for N above 256.  The first two, and N above 256 for real
+ * captures, are the paragraph below.
+ *
+ * Real-sampled captures (fmd_chan_create_real) and rows of 16-bit integers (the _fmt entry points).  A channeliser is
+ * real or complex for life.  A real one takes the same fmd_chan_params (sample_rate_in is the real sample rate; n_bins
+ * 2..512, every other range and default as above) and FMD_REAL_F32 / _S8 / _S16 input, one element per sample; strides
+ * and `samples` count real samples, and on the device path pointer and capture stride are multiples of FOUR samples,
+ * as the real band splitter's (the host path takes any alignment).  Definition: x[q] = (convert(v[q]), +0.0f), then
+ * everything above -- the output count, history and phase over calls of any size, fmd_chan_set_shifts without a wait,
+ * reset, the determinism rule, the non-finite rule.  The other kind's formats are FMD_ERR_ARG with a sentence that
+ * says which kind this channeliser is, and leave it as it was.
+ * Contract of a real channeliser's rows.  N <= 256: a row equals, bit for bit (NaN matching NaN), the row of a complex
+ * channeliser of the same parameters fed the pairs (v, +0) -- what is computed is that channeliser's chain of fmas
+ * with the terms that are products of the zero imaginary parts left out, and those terms change no partial sum.  One
+ * exception: an output that is a ZERO may differ in its sign (a partial sum that underflows to -0 keeps that sign only
+ * until the next +0 term is added, and the two forms add different numbers of them); compare zeros with ==.
+ * N in 257..512 has no complex twin: the contract is the one above -- no less accurate than the reference's float32
+ * arithmetic against the definition in float64, and the determinism rule.
+ * out_format belongs to the call: FMD_CIQ_F32 (complex64, what fmd_chan_process_device / _host mean; they work on both
+ * kinds) or FMD_CIQ_S16: int16 re, im per sample, host byte order, fmd_f32_to_mpx16 (saturate(round_half_even(x *
+ * 8192)), NaN gives 0, infinities saturate) of each part of the float the FMD_CIQ_F32 call would have stored -- exact.
+ * S16 device rows: d_out 16-byte aligned, out_row_stride in complex samples, a multiple of 4 and >= the count -- the
+ * rule of a FMD_IN_CIQ_S16 device call, which takes the buffer on the same stream without a copy; elements beyond the
+ * count are not written.  The host path takes any stride >= the count.  Formats may change from call to call.
+ * Still not offered: unsigned real samples, saving a channeliser's state, N above 256 for complex input, N above 512. */
 #define FMD_CHAN_MAX_SAMPLES 16777216u /* input samples per capture and call */
 typedef struct fmd_chan_params
 {
   double sample_rate_in; /* > 0 */
-  unsigned n_bins;       /* N: 2..256, any integer (96, 100, 192, 200 are the real ones); the raster is fs / N */
+  unsigned n_bins;       /* N: 2..256 (fmd_chan_create_real: 2..512), any integer (96, 100, 192, 200 are the real
+                            ones); the raster is fs / N */
   unsigned decimation;   /* D: 2..256; the rows leave at fs / D; no relation to N is required */
   unsigned filter_order; /* K: 2..4096; 0 = 8 D, the reference's rule (FmDecode.cpp:262) */
   double cutoff;         /* fraction of the input rate, (0, 0.5]; 0 = 0.6 / D, the reference's */
@@ -1324,6 +1350,17 @@ int fmd_chan_process_device(fmd_chan* c, const void* d_in, int iq_format, size_t
  * waits. */
 int fmd_chan_process_host(fmd_chan* c, const void* in, int iq_format, size_t in_capture_stride, unsigned samples,
                           void* out, size_t out_row_stride, unsigned* out_samples);
+/* A channeliser of real-sampled captures (FMD_REAL_*; the section's last paragraph): the same parameters, n_bins up to
+ * 512. */
+int fmd_chan_create_real(const fmd_chan_params* p, unsigned n_captures, unsigned n_rows_per_capture,
+                         const int* shifts, int device, fmd_chan** out);
+/* The two calls above with the rows' format, out_format = FMD_CIQ_F32 or FMD_CIQ_S16 (S16 device rows: out_row_stride
+ * a multiple of 4 complex samples); either kind of channeliser, iq_format of its kind. */
+int fmd_chan_process_device_fmt(fmd_chan* c, const void* d_in, int iq_format, size_t in_capture_stride,
+                                unsigned samples, void* d_out, int out_format, size_t out_row_stride,
+                                unsigned* out_samples, void* stream);
+int fmd_chan_process_host_fmt(fmd_chan* c, const void* in, int iq_format, size_t in_capture_stride, unsigned samples,
+                              void* out, int out_format, size_t out_row_stride, unsigned* out_samples);
 
 /* ---- host-only pieces (no GPU needed) ----------------------------------------------- */
 /* UECP group decoder = cRDSGroupDecoder (RDSGroupDecoder.cpp:166-1001). */

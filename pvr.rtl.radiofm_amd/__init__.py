@@ -271,6 +271,7 @@ EXPORTS = [
     "fmd_chan_create", "fmd_chan_destroy", "fmd_chan_reset", "fmd_chan_set_shifts", "fmd_chan_rows",
     "fmd_chan_out_rate", "fmd_chan_max_out_samples", "fmd_chan_get_taps", "fmd_chan_tile_samples",
     "fmd_chan_process_device", "fmd_chan_process_host",
+    "fmd_chan_create_real", "fmd_chan_process_device_fmt", "fmd_chan_process_host_fmt",
 ]
 
 
@@ -480,6 +481,9 @@ def lib():
         L.fmd_chan_tile_samples.argtypes = [vp]
         L.fmd_chan_process_device.argtypes = [vp, vp, i, C.c_size_t, u, vp, C.c_size_t, C.POINTER(u), vp]
         L.fmd_chan_process_host.argtypes = [vp, vp, i, C.c_size_t, u, vp, C.c_size_t, C.POINTER(u)]
+        L.fmd_chan_create_real.argtypes = [C.POINTER(FmdChanParams), u, u, vp, i, C.POINTER(vp)]
+        L.fmd_chan_process_device_fmt.argtypes = [vp, vp, i, C.c_size_t, u, vp, i, C.c_size_t, C.POINTER(u), vp]
+        L.fmd_chan_process_host_fmt.argtypes = [vp, vp, i, C.c_size_t, u, vp, i, C.c_size_t, C.POINTER(u)]
         _LIB = L
     return _LIB
 
