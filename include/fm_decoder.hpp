@@ -209,6 +209,24 @@ public:
     return fmd_batch_read_rds_quality(fmd_decoder_batch(m_dec), 0, 1, out) == FMD_OK;
   }
 
+  /* Not in the reference: ITU-R BS.1770 loudness blocks of the audio (fmd.h, "loudness blocks").  SetLoudness: the
+   * meter of every ProcessStream from now on (block_frames 0: 100 ms, ring_blocks 0: 64; fixed the first time it is
+   * turned on); CollectLoudness: the blocks completed and not yet collected, in order, into `out` (returns their
+   * number; *first_block: the index of the first; *lost: blocks the ring had overwritten).  fmd_loudness_window /
+   * fmd_loudness_integrated turn them into LUFS. */
+  bool SetLoudness(bool on, unsigned int block_frames = 0, unsigned int ring_blocks = 0)
+  {
+    return fmd_batch_set_loudness(fmd_decoder_batch(m_dec), on ? FMD_LOUDNESS_ON : FMD_LOUDNESS_OFF, block_frames,
+                                  ring_blocks) == FMD_OK;
+  }
+  unsigned int CollectLoudness(fmd_loud_block* out, unsigned int cap_blocks, uint64_t* first_block = nullptr,
+                               unsigned int* lost = nullptr)
+  {
+    const int n =
+        fmd_batch_collect_loudness(fmd_decoder_batch(m_dec), out, cap_blocks, 0, 1, 0, nullptr, first_block, lost);
+    return n > 0 ? static_cast<unsigned int>(n) : 0u;
+  }
+
 private:
   unsigned int ChannelIqCall(const float* ciq, unsigned int m, void* audio, int pcm_format, float* mpx,
                              unsigned int* mpx_samples)

@@ -655,6 +655,82 @@ int fmd_batch_collect_rds_blocks(fmd_batch* b, fmd_rds_block* out, unsigned cap,
 /* The counters of channels [first_channel, first_channel + n).  Synchronous, like fmd_batch_read_pcm_clipped. */
 int fmd_batch_read_rds_quality(fmd_batch* b, unsigned first_channel, unsigned n, fmd_rds_quality* out);
 
+/* ---- ITU-R BS.1770 loudness blocks of every channel ----
+ *
+ * Loudness logging (EBU R 128: momentary, short-term, integrated) needs both audio channels at the PCM rate through
+ * the K-weighting filter.  The audio tail has them in registers; with the meter on it also runs the filter and leaves
+ * one 16-byte record per channel and block (100 ms by default): the block's sums of squares and sample peaks.  What
+ * follows is the definition; it is exact -- the device computes these bits, there is no tolerance on its side.
+ *
+ * Design.  With fs = sample_rate_pcm, two biquads, designed in double and rounded once to float.
+ *   Stage 1, high shelf: f0 = 1681.974450955533, G = 3.999843853973347 dB, Q = 0.7071752369554196,
+ *     K = tan(pi f0 / fs), Vh = 10^(G/20), Vb = Vh^0.4996667741545416, a0 = 1 + K/Q + K^2,
+ *     b0 = (Vh + Vb K/Q + K^2)/a0, b1 = 2 (K^2 - Vh)/a0, b2 = (Vh - Vb K/Q + K^2)/a0,
+ *     a1 = 2 (K^2 - 1)/a0, a2 = (1 - K/Q + K^2)/a0.
+ *   Stage 2, high-pass: f0 = 38.13547087602444, Q = 0.5003270373238773, the same K and a0 formulas,
+ *     b = (1, -2, 1), a1 = 2 (K^2 - 1)/a0, a2 = (1 - K/Q + K^2)/a0.
+ *   At 48 000 Hz these are the coefficients printed in BS.1770-4 (to 1e-15).
+ * Filter form.  Each stage, for L and R separately, is transposed direct form II in float; every multiply, add and
+ * subtract is rounded on its own (no fused multiply-add), in exactly this order:
+ *     y  = b0*x + s1
+ *     s1 = (b1*x - a1*y) + s2
+ *     s2 = b2*x - a2*y
+ *   Stage 2 takes stage 1's y.  The input x is the float audio sample of the call, before any PCM conversion: a
+ *   FMD_PCM_S16 call and a channel without an audio row are metered like every other.
+ * Blocks.  Frames are numbered g = 0, 1, ... over the calls submitted with the meter on.  Block j is frames
+ *   [j Bf, (j + 1) Bf), Bf = block_frames.  Its record is { z_l, z_r, peak_l, peak_r }: z = the sum of y2^2 over the
+ *   block in frame order in float (acc = acc + y2*y2, both operations rounded); peak = fmaxf(peak, fabsf(x)) of the
+ *   unweighted sample, from 0 -- a NaN sample leaves the peak and makes z NaN.  Filter states and partial sums start at
+ *   +0 when the meter is first turned on.  Denormals are kept: a station that falls silent decays through them.
+ * tests/loud_spec.py restates all of this in numpy.
+ *
+ * Ownership.  The meter belongs to the slot's output, like the clip counter and the feed: fmd_batch_reset,
+ * fmd_batch_reset_channels, retunes, capture switches, fmd_batch_import_channels and fmd_batch_load_state leave its
+ * states, sums and frame count alone; no state blob carries it (the blob's record format is unchanged).  Every channel
+ * is metered, whatever the audio selection says.
+ *
+ * Out of scope: loudness range (EBU Tech 3342) and true peak (4x oversampling; peak_l / peak_r are sample peaks). */
+typedef struct fmd_loud_block { /* 16 bytes */
+  float z_l, z_r, peak_l, peak_r;
+} fmd_loud_block;
+
+#define FMD_LOUDNESS_OFF 0
+#define FMD_LOUDNESS_ON 1
+/* The mode of every call submitted from now on; it travels with the call like fmd_batch_set_rds_blocks' mode: nothing
+ * waits, calls in flight keep theirs.  A mode-0 call launches what a batch without this launches, and it is a splice:
+ * the meter does not hear it -- g, states and partial sums stand still.  block_frames: 0 = round(fs / 10) (100 ms),
+ * else 16 .. 1048576.  ring_blocks: the blocks of history the device keeps per channel, 0 = 64, else 8 .. 4096.  Both
+ * are fixed by the first call that turns the meter on, which allocates (48 + 16 ring_blocks bytes per channel); a
+ * later different non-zero value is refused (FMD_ERR_ARG). */
+int fmd_batch_set_loudness(fmd_batch* b, int mode, unsigned block_frames, unsigned ring_blocks);
+int fmd_batch_get_loudness(const fmd_batch* b); /* the mode, or a negative error */
+/* Bf: the fixed value, or before the meter was ever on the default it would take. */
+unsigned fmd_batch_loudness_block_frames(const fmd_batch* b);
+/* out = b0 b1 b2 a1 a2 of stage 1, then of stage 2: the floats the kernels use. */
+int fmd_batch_get_loudness_coeffs(const fmd_batch* b, float out[10]);
+/* Copies the not-yet-collected blocks completed by calls at least `lag` (0..4) calls old, for channels
+ * [first_channel, first_channel + n_channels) -- global numbers, also above 8192 channels -- to out, block-major:
+ * out[k * n_channels + i] is block *first_block + k of channel first_channel + i.  Returns the number of blocks
+ * (<= cap_blocks); waits for `stream` and for those calls.  All channels of a batch tick alike and the host knows at
+ * submission which call completes which blocks: there is one cursor per batch (a collect takes the blocks for the
+ * channels it names and moves it), and nothing is read back to find them.
+ * The ring holds the last ring_blocks blocks completed by the calls SUBMITTED so far, in flight or not.  Blocks older
+ * than that are skipped and counted in *lost (may be null).  None is lost while, at every collect,
+ *     (frames of the calls submitted since the last collected block ended) < ring_blocks * Bf,
+ * i.e. collect at least once per (ring_blocks - 1) * Bf frames of mode-1 calls, the `lag` newest calls counted in: with
+ * the defaults (64 blocks of 100 ms) once per 6.3 s of audio, some 230 calls of 65 536 samples at 2.4 MS/s.
+ * A single decoder: through fmd_decoder_batch. */
+int fmd_batch_collect_loudness(fmd_batch* b, fmd_loud_block* out, unsigned cap_blocks, unsigned first_channel,
+                               unsigned n_channels, int lag, void* stream, uint64_t* first_block, unsigned* lost);
+/* Host arithmetic over block records, in double; no device.
+ * fmd_loudness_window: -0.691 + 10 log10((sum z_l + sum z_r) / (n block_frames)) over n consecutive blocks of one
+ * channel (summed in block order, z_l then z_r of each): n = 4 momentary, n = 30 short-term loudness (LUFS).
+ * fmd_loudness_integrated: BS.1770-4 gating over windows of four consecutive blocks stepping by one (75 % overlap):
+ * absolute gate at -70 LUFS, relative gate 10 LU under the loudness of the survivors' mean power; -HUGE_VAL when
+ * nothing survives or n_blocks < 4.  A window with a NaN block passes no gate. */
+double fmd_loudness_window(const fmd_loud_block* blk, unsigned n, unsigned block_frames);
+double fmd_loudness_integrated(const fmd_loud_block* blk, unsigned n_blocks, unsigned block_frames);
+
 /* Copies the queued RDS groups (all channels, call order) to `out`, waits for `stream`.
  * Returns the number of groups (<= cap) or a negative error.  When run_group_decoder != 0
  * each group is also fed to that channel's UECP group decoder (callbacks fire).  The return value is
@@ -995,6 +1071,10 @@ int fmd_batch_debug_reset_keep_ring_phase(fmd_batch* b, int on);
  * in front of a call's frames stay what they were -- the first feed sample that reaches back over a call boundary is
  * then wrong.  An entry point of its own: the fmd_batch_debug_set key table is held to 14 keys. */
 int fmd_batch_debug_feed_skip_roll(fmd_batch* b, int on);
+/* Test aid (mutation test of the loudness meter's tests): on = 1 makes every mode-1 call start its block in progress
+ * from +0 -- the carried partial sums and peaks are dropped at the call boundary, so exactly the blocks that span one
+ * are wrong.  An entry point of its own, like the one above. */
+int fmd_batch_debug_loud_skip_carry(fmd_batch* b, int on);
 /* Test aid (mutation test of FMD_IN_CIQ_*): the input copy leaves out every row's last tile. */
 int fmd_batch_debug_ciq_in_skip_tile(fmd_batch* b, int on);
 /* Test aid: out[i] = the host build of FMD_IN_CIQ_S16's conversion of in[i], (float)v * 2^-13; no device is touched. */

@@ -117,6 +117,9 @@ assert C.sizeof(FmdRdsBlock) == 24 and RDS_BLOCK_DTYPE.itemsize == 24
 assert C.sizeof(FmdRdsQuality) == 32 and RDS_QUALITY_DTYPE.itemsize == 32
 # block observation modes (include/fmd.h FMD_RDS_BLOCKS_*)
 FMD_RDS_BLOCKS_OFF, FMD_RDS_BLOCKS_COUNT, FMD_RDS_BLOCKS_RECORD = 0, 1, 2
+# a loudness block record (include/fmd.h fmd_loud_block)
+LOUD_BLOCK_DTYPE = np.dtype([("z_l", "<f4"), ("z_r", "<f4"), ("peak_l", "<f4"), ("peak_r", "<f4")])
+assert LOUD_BLOCK_DTYPE.itemsize == 16
 
 class FmdAudioLevel(C.Structure):
     _fields_ = [("mean", C.c_float), ("rms", C.c_float), ("level", C.c_float)]
@@ -264,6 +267,9 @@ EXPORTS = [
     "fmd_batch_select_audio", "fmd_batch_select_mpx", "fmd_batch_get_audio_selection", "fmd_batch_get_mpx_selection",
     "fmd_batch_set_rds_blocks", "fmd_batch_get_rds_blocks", "fmd_batch_collect_rds_blocks",
     "fmd_batch_read_rds_quality",
+    "fmd_batch_set_loudness", "fmd_batch_get_loudness", "fmd_batch_loudness_block_frames",
+    "fmd_batch_get_loudness_coeffs", "fmd_batch_collect_loudness", "fmd_loudness_window", "fmd_loudness_integrated",
+    "fmd_batch_debug_loud_skip_carry",
     "fmd_split_create", "fmd_split_destroy", "fmd_split_reset", "fmd_split_set_shifts", "fmd_split_rows",
     "fmd_split_out_rate", "fmd_split_max_out_samples", "fmd_split_get_taps", "fmd_split_tile_samples",
     "fmd_split_debug_table_versions", "fmd_split_process_device", "fmd_split_process_host",
@@ -449,6 +455,17 @@ def lib():
         L.fmd_batch_get_rds_blocks.argtypes = [vp]
         L.fmd_batch_collect_rds_blocks.argtypes = [vp, vp, u, i, vp, C.POINTER(u)]
         L.fmd_batch_read_rds_quality.argtypes = [vp, u, u, vp]
+        L.fmd_batch_set_loudness.argtypes = [vp, i, u, u]
+        L.fmd_batch_get_loudness.argtypes = [vp]
+        L.fmd_batch_loudness_block_frames.restype = u
+        L.fmd_batch_loudness_block_frames.argtypes = [vp]
+        L.fmd_batch_get_loudness_coeffs.argtypes = [vp, vp]
+        L.fmd_batch_collect_loudness.argtypes = [vp, vp, u, u, u, i, vp, C.POINTER(C.c_uint64), C.POINTER(u)]
+        L.fmd_loudness_window.restype = C.c_double
+        L.fmd_loudness_window.argtypes = [vp, u, u]
+        L.fmd_loudness_integrated.restype = C.c_double
+        L.fmd_loudness_integrated.argtypes = [vp, u, u]
+        L.fmd_batch_debug_loud_skip_carry.argtypes = [vp, i]
         L.fmd_split_create.argtypes = [C.POINTER(FmdSplitParams), u, u, vp, i, C.POINTER(vp)]
         L.fmd_split_create_real.argtypes = [C.POINTER(FmdSplitParams), u, u, vp, i, C.POINTER(vp)]
         L.fmd_split_destroy.argtypes = [vp]
@@ -1158,6 +1175,48 @@ class Batch:
         out = np.zeros(max(n, 1), dtype=RDS_QUALITY_DTYPE)
         _check(lib().fmd_batch_read_rds_quality(self._h, first, n, out.ctypes.data))
         return out[:n]
+
+    def set_loudness(self, on, block_frames=0, ring_blocks=0):
+        """The loudness meter of every call submitted from now on (fmd_batch_set_loudness): BS.1770 K-weighted block
+        sums and sample peaks of every channel.  block_frames 0: 100 ms; ring_blocks 0: 64; both are fixed by the first
+        call that turns the meter on."""
+        _check(lib().fmd_batch_set_loudness(self._h, 1 if on else 0, int(block_frames), int(ring_blocks)))
+        if on and not getattr(self, "_loud_ring", 0):
+            self._loud_ring = int(ring_blocks) or 64
+
+    def loudness(self):
+        return _check(lib().fmd_batch_get_loudness(self._h))
+
+    def loudness_block_frames(self):
+        return int(lib().fmd_batch_loudness_block_frames(self._h))
+
+    def loudness_coeffs(self):
+        """float32[10]: b0 b1 b2 a1 a2 of the high shelf, then of the high-pass."""
+        out = np.zeros(10, dtype=np.float32)
+        _check(lib().fmd_batch_get_loudness_coeffs(self._h, out.ctypes.data))
+        return out
+
+    def collect_loudness(self, lag=0, channels=None, cap=None, stream=None, with_lost=False):
+        """(blocks, first): the not-yet-collected block records completed by calls at least `lag` old as a structured
+        array [blocks, channels] (LOUD_BLOCK_DTYPE) and the index of the first (fmd_batch_collect_loudness).  channels:
+        (first, n), default every channel.  cap: the most blocks one collect takes, default the ring_blocks given to
+        set_loudness (64): what the ring can hold.  with_lost: (blocks, first, lost) -- blocks the ring had
+        overwritten.  The staging buffer is kept and grown as needed, not allocated per collect."""
+        first_ch, n_ch = (0, self.n_channels) if channels is None else (int(channels[0]), int(channels[1]))
+        cap = int(getattr(self, "_loud_ring", 0) or 64) if cap is None else int(cap)
+        need = max(cap, 1) * max(n_ch, 1)
+        buf = getattr(self, "_loud_buf", None)
+        if buf is None or buf.size < need:
+            buf = self._loud_buf = np.empty(need, dtype=LOUD_BLOCK_DTYPE)
+        first, lost = C.c_uint64(0), C.c_uint(0)
+        n = _check(lib().fmd_batch_collect_loudness(self._h, buf.ctypes.data, cap, first_ch, n_ch, lag, stream,
+                                                    C.byref(first), C.byref(lost)))
+        out = buf[:n * n_ch].reshape(n, n_ch).copy()
+        return (out, first.value, lost.value) if with_lost else (out, first.value)
+
+    def debug_loud_skip_carry(self, on):
+        """Test aid: drop the block in progress at every call boundary (fmd_batch_debug_loud_skip_carry)."""
+        _check(lib().fmd_batch_debug_loud_skip_carry(self._h, int(on)))
 
     def collect_rds_array(self, cap=65536, run_group_decoder=False, stream=None, lag=0):
         """Queued RDS groups as a numpy structured array (channel, call_index, blocks[4])."""

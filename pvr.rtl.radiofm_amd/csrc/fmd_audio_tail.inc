@@ -9,6 +9,11 @@
  * The feed forms (k_audio_tail*_feed) also define FMD_TAIL_FEED: the first of the call's rows in the feed's time-major
  * scratch ([A][CP] floats from there).  Every lane that has a channel, selected or not, stores the mono mix
  * (o.x + o.y) * 0.5f of frame i into row i: one 4-byte store a lane, 256 contiguous bytes a wave.
+ * The loudness forms (fmd_k_loud.hip.h) also define FMD_TAIL_LOUD: the meter's record (LoudArgs).  Every lane,
+ * selected or not, takes the float frame through the K-weighting biquads and the block sums (include/fmd.h: every
+ * operation rounded on its own, in the order written there); the frame that ends a block is the same for all lanes
+ * (left0, block_frames: wave-uniform), and there a lane that has a channel stores the block's 16-byte record into
+ * row `slot` of the time-major ring -- 1 KB contiguous a wave -- and starts the next block from +0.
  */
   __builtin_amdgcn_s_setprio(3);
   const unsigned lane = threadIdx.x;
@@ -58,6 +63,36 @@
     vsumsq += o.y * o.y;
     return o;
   };
+#ifdef FMD_TAIL_LOUD
+  const LoudArgs& ld = FMD_TAIL_LOUD;
+  float* const __restrict__ ld_st = ld.state + c;
+  const size_t ld_CP = CP;
+  float ld_s[8]; // the delay words, in LoudRow order
+#pragma unroll
+  for (int r = 0; r < 8; r++)
+    ld_s[r] = ld_st[r * ld_CP];
+  float ld_zl = ld_st[LD_Z_L * ld_CP], ld_zr = ld_st[LD_Z_R * ld_CP];
+  float ld_pl = ld_st[LD_PEAK_L * ld_CP], ld_pr = ld_st[LD_PEAK_R * ld_CP];
+  unsigned ld_left = ld.left0, ld_slot = ld.slot0; // scalar: the same in every lane
+  auto meter = [&](float2 f) {
+    const float l1 = loud_biquad(f.x, ld.b0[0], ld.b1[0], ld.b2[0], ld.a1[0], ld.a2[0], ld_s[LD_S1_1L], ld_s[LD_S2_1L]);
+    const float r1 = loud_biquad(f.y, ld.b0[0], ld.b1[0], ld.b2[0], ld.a1[0], ld.a2[0], ld_s[LD_S1_1R], ld_s[LD_S2_1R]);
+    const float l2 = loud_biquad(l1, ld.b0[1], ld.b1[1], ld.b2[1], ld.a1[1], ld.a2[1], ld_s[LD_S1_2L], ld_s[LD_S2_2L]);
+    const float r2 = loud_biquad(r1, ld.b0[1], ld.b1[1], ld.b2[1], ld.a1[1], ld.a2[1], ld_s[LD_S1_2R], ld_s[LD_S2_2R]);
+    ld_zl = __fadd_rn(ld_zl, __fmul_rn(l2, l2));
+    ld_zr = __fadd_rn(ld_zr, __fmul_rn(r2, r2));
+    ld_pl = fmaxf(ld_pl, fabsf(f.x)); // (a NaN sample leaves the peak)
+    ld_pr = fmaxf(ld_pr, fabsf(f.y));
+    if (--ld_left == 0)
+    { // the block ends behind this frame
+      if (active)
+        ld.ring[(size_t)ld_slot * ld_CP + c] = make_float4(ld_zl, ld_zr, ld_pl, ld_pr);
+      ld_zl = ld_zr = ld_pl = ld_pr = 0.0f;
+      ld_left = ld.block_frames;
+      ld_slot = ld_slot + 1 == ld.ring_blocks ? 0u : ld_slot + 1;
+    }
+  };
+#endif
   typename OUT::frame_t* __restrict__ o = reinterpret_cast<typename OUT::frame_t*>(audio + (size_t)row * audio_stride);
   typename OUT::State os;
 
@@ -81,6 +116,9 @@
     for (unsigned u = 0; u < AT_STEPS; u++)
     {
       const float2 f = frame(vin[u]);
+#ifdef FMD_TAIL_LOUD
+      meter(f);
+#endif
 #ifdef FMD_TAIL_FEED
       if (active)
         FMD_TAIL_FEED[(size_t)(i0 + u) * CP + c] = (f.x + f.y) * 0.5f;
@@ -99,6 +137,9 @@
       if (u < cnt)
       {
         const float2 f = frame(vnext[u]);
+#ifdef FMD_TAIL_LOUD
+        meter(f);
+#endif
 #ifdef FMD_TAIL_FEED
         if (active)
           FMD_TAIL_FEED[(size_t)(i0 + u) * CP + c] = (f.x + f.y) * 0.5f;
@@ -112,6 +153,15 @@
   }
   if (active)
   {
+#ifdef FMD_TAIL_LOUD
+#pragma unroll
+    for (int r = 0; r < 8; r++)
+      ld_st[r * ld_CP] = ld_s[r];
+    ld_st[LD_Z_L * ld_CP] = ld_zl;
+    ld_st[LD_Z_R * ld_CP] = ld_zr;
+    ld_st[LD_PEAK_L * ld_CP] = ld_pl;
+    ld_st[LD_PEAK_R * ld_CP] = ld_pr;
+#endif
     st.F(F_DE_RE)[c] = de_re;
     st.F(F_DE_IM)[c] = de_im;
     st.F(F_N_W1A)[c] = w1a;

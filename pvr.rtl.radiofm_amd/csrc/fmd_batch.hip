@@ -28,6 +28,7 @@
 #include "fmd_design.hpp"
 #include "fmd_groups.hpp"
 #include "fmd_kernels.hip.h"
+#include "fmd_loud.hpp"
 #include "fmd_receiver.hpp"
 
 namespace
@@ -523,6 +524,21 @@ struct fmd_batch
   hipStream_t feed_stream = nullptr;
   int dbg_feed_skip_roll = 0;     // fmd_batch_debug_feed_skip_roll (mutation test): the history rows stay stale
   int dbg_ciq_in_skip = 0;        // fmd_batch_debug_ciq_in_skip_tile (mutation test): the input copy's last tile is left out
+  /* The loudness meter (fmd_batch_set_loudness).  Every batch knows the mode of its next
+   * call, the block length, the ring's rows and the ten coefficients.  A batch with buffers of its own holds the
+   * meter's state ([LOUD_STATE_ROWS][CP], +0 at the first mode-1 setting), the time-major ring of block records and
+   * loud_g, the frames of its mode-1 calls so far: where a call's blocks end follows from it on the host, at
+   * submission -- all channels tick alike.  loud_done[k]: blocks completed by the calls at least k calls old (shifted
+   * by every call, whatever its mode), what a lagged collect may take.  The caller-facing batch holds loud_taken, the
+   * blocks collected or counted lost so far.  The meter belongs to the output: resets, retunes, capture switches,
+   * imports and loads leave all of this alone. */
+  int loud_mode = 0;
+  unsigned loud_bf = 0, loud_ring = 0;
+  float loud_coef[10] = {};
+  DevBuf<float> loud_state;
+  DevBuf<float4> loud_blocks;
+  uint64_t loud_g = 0, loud_done[5] = {}, loud_taken = 0;
+  int dbg_loud_skip_carry = 0;    // fmd_batch_debug_loud_skip_carry (mutation test): a call starts its block from +0
   /* The channel IQ (the _call entry points): demod[q]'s rows as an output.  It has no state
    * of its own -- a selection of the multiplex's form (sel[FMT_CIQ]) and the host call's staging. */
   bool decoder_owned = false;     // the one-channel batch behind an fmd_decoder: it takes no selection
@@ -3454,6 +3470,164 @@ int fmd_batch_read_rds_quality(fmd_batch* b, unsigned first_channel, unsigned n,
     c += run;
   }
   return FMD_OK;
+}
+
+/* ---- the loudness meter (fmd.h) ---- */
+static_assert(sizeof(fmd_loud_block) == 16 && sizeof(fmd_loud_block) == sizeof(float4), "the ring's record is fmd.h's");
+
+int fmd_batch_set_loudness(fmd_batch* b, int mode, unsigned block_frames, unsigned ring_blocks)
+{
+  // (the arguments' own ranges first: they are refused whatever the batch)
+  if (mode < FMD_LOUDNESS_OFF || mode > FMD_LOUDNESS_ON)
+    return fail(FMD_ERR_ARG, "fmd_batch_set_loudness: mode must be FMD_LOUDNESS_OFF or FMD_LOUDNESS_ON (0..1)");
+  if (block_frames && (block_frames < 16u || block_frames > (1u << 20)))
+    return fail(FMD_ERR_ARG, "fmd_batch_set_loudness: block_frames must be 0 (100 ms) or 16 .. 1048576; " +
+                                 std::to_string(block_frames) + " refused");
+  if (ring_blocks && (ring_blocks < 8u || ring_blocks > 4096u))
+    return fail(FMD_ERR_ARG, "fmd_batch_set_loudness: ring_blocks must be 0 (64) or 8 .. 4096; " +
+                                 std::to_string(ring_blocks) + " refused");
+  if (!b)
+    return fail(FMD_ERR_ARG, "fmd_batch_set_loudness: null batch");
+  if (b->loud_bf && block_frames && block_frames != b->loud_bf)
+    return fail(FMD_ERR_ARG, "fmd_batch_set_loudness: a block is " + std::to_string(b->loud_bf) +
+                                 " frames since the first call that turned the meter on; " +
+                                 std::to_string(block_frames) + " refused");
+  if (b->loud_bf && ring_blocks && ring_blocks != b->loud_ring)
+    return fail(FMD_ERR_ARG, "fmd_batch_set_loudness: the ring holds " + std::to_string(b->loud_ring) +
+                                 " blocks since the first call that turned the meter on; " +
+                                 std::to_string(ring_blocks) + " refused");
+  if (mode != FMD_LOUDNESS_OFF && !fmd::loud_tail_launch) // (never in the library: fmd_loud.hip)
+    return fail(FMD_ERR_STATE, "fmd_batch_set_loudness: this build has no loudness kernels");
+  if (mode != FMD_LOUDNESS_OFF && !b->loud_bf)
+  {
+    HIPCHK(hipSetDevice(b->device));
+    const unsigned bf = block_frames ? block_frames : unsigned(std::lround(b->params.sample_rate_pcm / 10.0));
+    const unsigned ring = ring_blocks ? ring_blocks : 64u;
+    if (bf < 16u || bf > (1u << 20))
+      return fail(FMD_ERR_ARG, "fmd_batch_set_loudness: 100 ms at this PCM rate is no block of 16 .. 1048576 frames");
+    float coef[10];
+    fmd::loud_design(b->params.sample_rate_pcm, coef);
+    const std::vector<Part> ps = parts(b);
+    for (const Part& p : ps)
+      if (p.x->loud_state.alloc(size_t(fmd::LOUD_STATE_ROWS) * p.x->CP) ||
+          p.x->loud_blocks.alloc(size_t(ring) * p.x->CP))
+      { // nothing half-made stays: the batch is as before the call
+        for (const Part& y : ps)
+        {
+          y.x->loud_state.release();
+          y.x->loud_blocks.release();
+        }
+        return fail(FMD_ERR_DEVICE, "fmd_batch_set_loudness: allocation of the meter's state and ring failed");
+      }
+    set_all(b, &fmd_batch::loud_bf, bf);
+    set_all(b, &fmd_batch::loud_ring, ring);
+    std::copy(coef, coef + 10, b->loud_coef);
+    for (auto& sb : b->subs)
+      std::copy(coef, coef + 10, sb->loud_coef);
+  }
+  set_all(b, &fmd_batch::loud_mode, mode);
+  return FMD_OK;
+}
+
+int fmd_batch_get_loudness(const fmd_batch* b)
+{
+  if (!b)
+    return fail(FMD_ERR_ARG, "fmd_batch_get_loudness: null batch");
+  return b->loud_mode;
+}
+
+unsigned fmd_batch_loudness_block_frames(const fmd_batch* b)
+{
+  if (!b)
+    return 0;
+  return b->loud_bf ? b->loud_bf : unsigned(std::lround(b->params.sample_rate_pcm / 10.0));
+}
+
+int fmd_batch_get_loudness_coeffs(const fmd_batch* b, float out[10])
+{
+  if (!b || !out)
+    return fail(FMD_ERR_ARG, "fmd_batch_get_loudness_coeffs: null argument");
+  fmd::loud_design(b->params.sample_rate_pcm, out);
+  return FMD_OK;
+}
+
+int fmd_batch_debug_loud_skip_carry(fmd_batch* b, int on)
+{
+  if (!b)
+    return fail(FMD_ERR_ARG, "null batch");
+  set_all(b, &fmd_batch::dbg_loud_skip_carry, on != 0);
+  return FMD_OK;
+}
+
+int fmd_batch_collect_loudness(fmd_batch* b, fmd_loud_block* out, unsigned cap_blocks, unsigned first_channel,
+                               unsigned n_channels, int lag, void* stream_, uint64_t* first_block, unsigned* lost)
+{
+  if (!b || lag < 0 || lag > 4 || (!out && cap_blocks && n_channels))
+    return fail(FMD_ERR_ARG, "fmd_batch_collect_loudness: bad argument (lag must be 0..4)");
+  if (first_channel > b->C || n_channels > b->C - first_channel)
+    return fail(FMD_ERR_ARG, "fmd_batch_collect_loudness: channels [" + std::to_string(first_channel) + ", " +
+                                 std::to_string(size_t(first_channel) + n_channels) + ") out of range (" +
+                                 std::to_string(b->C) + " channels)");
+  if (lost)
+    *lost = 0;
+  if (first_block)
+    *first_block = b->loud_taken;
+  if (!b->loud_bf) // the meter was never on: no ring exists
+    return 0;
+  // the blocks the calls at least `lag` old have completed; of those, the ring still holds the ones that no call
+  // submitted so far -- in flight or not -- has overwritten: the last loud_ring of all
+  const fmd_batch* fp = first_part(b);
+  const uint64_t avail = fp->loud_done[lag], total = fp->loud_done[0], ring = b->loud_ring;
+  uint64_t start = b->loud_taken;
+  const uint64_t oldest = std::min(avail, total > ring ? total - ring : uint64_t(0));
+  if (oldest > start)
+  {
+    if (lost)
+      *lost = unsigned(std::min<uint64_t>(oldest - start, 0xFFFFFFFFu));
+    start = oldest;
+  }
+  const unsigned n = unsigned(std::min<uint64_t>(avail - start, cap_blocks));
+  if (first_block)
+    *first_block = start;
+  hipStream_t stream = static_cast<hipStream_t>(stream_);
+  HIPCHK(hipSetDevice(b->device));
+  if (n && n_channels)
+  {
+    if (int rc = wait_impl(b, lag, stream_, false); rc < 0)
+      return rc;
+    HIPCHK(hipStreamSynchronize(stream));
+    const size_t rec = sizeof(fmd_loud_block);
+    for (unsigned c = first_channel; c < first_channel + n_channels;)
+    { // run by run of channels with one owner (a shell: its sub-batches); the ring's rows in one or two pieces
+      unsigned lc = 0;
+      const fmd_batch* ob = owner_of(b, c, &lc);
+      const unsigned run = std::min(first_channel + n_channels - c, ob->C - lc);
+      for (unsigned k = 0; k < n;)
+      {
+        const unsigned row = unsigned((start + k) % ring);
+        const unsigned rows = std::min(n - k, unsigned(ring) - row);
+        HIPCHK(hipMemcpy2D(out + size_t(k) * n_channels + (c - first_channel), size_t(n_channels) * rec,
+                           ob->loud_blocks.p + size_t(row) * ob->CP + lc, size_t(ob->CP) * rec, size_t(run) * rec,
+                           rows, hipMemcpyDeviceToHost));
+        k += rows;
+      }
+      c += run;
+    }
+  }
+  else if (int rc = check_device_errors(b))
+    return rc;
+  b->loud_taken = start + n;
+  return int(n);
+}
+
+double fmd_loudness_window(const fmd_loud_block* blk, unsigned n, unsigned block_frames)
+{
+  return fmd::loud_window(blk, n, block_frames);
+}
+
+double fmd_loudness_integrated(const fmd_loud_block* blk, unsigned n_blocks, unsigned block_frames)
+{
+  return fmd::loud_integrated(blk, n_blocks, block_frames);
 }
 
 int fmd_batch_process_host(fmd_batch* b, const float* iq, size_t iq_channel_stride, unsigned samples,

@@ -439,6 +439,31 @@ void launch_light_audio(Submit& x, hipStream_t s)
   };
   if (asel && !rows)
     ; // (the batch has failed: its state is void, the tail is left out)
+  else if (b->loud_mode)
+  { // a call submitted with the meter on (fmd_batch_set_loudness): the loudness forms (fmd_loud.hip), the meter's
+    // record behind the form's own arguments.  State and ring are the tail's alone, in the stream order the channel state relies on.
+    fmd::LoudArgs la;
+    for (int sgi = 0; sgi < 2; sgi++)
+    {
+      la.b0[sgi] = b->loud_coef[5 * sgi];
+      la.b1[sgi] = b->loud_coef[5 * sgi + 1];
+      la.b2[sgi] = b->loud_coef[5 * sgi + 2];
+      la.a1[sgi] = b->loud_coef[5 * sgi + 3];
+      la.a2[sgi] = b->loud_coef[5 * sgi + 4];
+    }
+    la.state = b->loud_state.p;
+    la.ring = b->loud_blocks.p;
+    la.block_frames = b->loud_bf;
+    la.left0 = b->loud_bf - unsigned(b->loud_g % b->loud_bf);
+    la.ring_blocks = b->loud_ring;
+    la.slot0 = unsigned((b->loud_g / b->loud_bf) % b->loud_ring);
+    if (b->dbg_loud_skip_carry && // (mutation test: the block in progress is dropped at the call boundary)
+        hipMemsetAsync(b->loud_state.p + size_t(fmd::LD_Z_L) * CP, 0, size_t(4) * CP * sizeof(float), s) != hipSuccess)
+      mark_failed(b, "hipMemsetAsync failed in front of the loudness form of the audio tail");
+    fmd::loud_tail_launch((s16 ? 1u : 0u) | (asel ? 2u : 0u) | (x.c.feed.p ? 4u : 0u), CP, s, x.tl0, x.tl1,
+                          b->alp[x.q].p, x.A, C, k, b->st, x.c.audio.p, x.c.audio.stride, unsigned(x.sq), x.ci,
+                          b->pcm_clip.p, rows, feed_rows, la);
+  }
   else if (x.c.feed.p && asel)
     s16 ? tail(fmd::k_audio_tail_s16_sel_feed, b->pcm_clip.p, rows, feed_rows)
         : tail(fmd::k_audio_tail_sel_feed, rows, feed_rows);
@@ -1236,6 +1261,14 @@ void commit_call(Submit& x)
     *c.mpx.out = c.mpx.p ? x.M : 0;
   if (c.feed.p)
     b->feed_g += x.A;
+  if (b->loud_bf)
+  { // the meter's frame count (mode-1 calls only: a mode-0 call is a splice) and what a lagged collect may take
+    if (b->loud_mode)
+      b->loud_g += x.A;
+    for (int k = 4; k > 0; k--)
+      b->loud_done[k] = b->loud_done[k - 1];
+    b->loud_done[0] = b->loud_g / b->loud_bf;
+  }
   if (c.feed.out)
     *c.feed.out = (c.feed.p && c.feed.deliver) ? pl.feed_n : 0;
   if (c.ciq.out)

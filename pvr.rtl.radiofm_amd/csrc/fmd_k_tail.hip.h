@@ -75,6 +75,7 @@ struct OutS16
   }
 };
 
+#ifndef FMD_TAIL_POLICIES_ONLY // (fmd_loud.hip takes the policies above and instantiates kernels of its own)
 /* One lane per channel.  The channel-major output ([C][stride], what ProcessStream's caller gets) is
  * written by every lane into its own channel's row, one frame (8 B) per store: the 16 stores that
  * fill a 128-byte line follow each other within ~2000 cycles and meet in the L2.  (Until round 4 the
@@ -411,5 +412,6 @@ __global__ void k_roll(const T* src, T* dst, unsigned H, unsigned n, unsigned CP
       dst[(size_t)r * CP + c] = src[(size_t)(r + n) * CP + c];
   }
 }
+#endif // FMD_TAIL_POLICIES_ONLY
 
 } // namespace fmd

@@ -25,6 +25,7 @@
 #include "fmd_k_rds.hip.h"
 #include "fmd_k_resample.hip.h"
 #include "fmd_k_tail.hip.h"
+#include "fmd_k_loud.hip.h"
 #include "fmd_k_mpx.hip.h"
 #include "fmd_k_feed.hip.h"
 #include "fmd_k_ciq.hip.h"
