@@ -13,7 +13,9 @@
  *      they read consecutive window samples and consecutive taps (conflict-free), and write U at a row stride of 33
  *      floats (conflict-free again).  Real and imaginary parts lie in two planes, 32 banks apart.
  *   3. The bins: Y[2 B x 32] = A[2 B x 2 N] U[2 N x 32] in real arithmetic on v_mfma_f32_32x32x2_f32, whose result is
- *      bit for bit an fma chain in k order.  Row 2 b of A is (Wre[0], -Wim[0], Wre[1], ...), row 2 b + 1 is (Wim[0],
+ *      bit for bit an fma chain in k order (tests/test_gpu_chan_shapes.py holds the device's rows to a numpy model of
+ *      these chains in bits: 5, 16, 17, 33, 37 and 70 rows a capture; N = 2, 3, 4, 5, 8, 9, 16, 24, 64, 192, 255, 256,
+ *      real 2, 3, 5, 24, 192, 511).  Row 2 b of A is (Wre[0], -Wim[0], Wre[1], ...), row 2 b + 1 is (Wim[0],
  *      Wre[0], ...), W[r] = exp(+2 pi i s_b r / N) from the host's table (rounded once from double); k = 2 r + part.
  *      A wave owns blocks of 32 rows of A (16 rows of the channeliser); the chain runs in two independent halves, r in
  *      [0, N / 2) and [N / 2, N), that are added at the end -- the same form for every B, call size and tile, so a
